@@ -4,12 +4,15 @@
   python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N ranks, one per GPU, before any GPU call)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W --full                  (also the sub-batched rate and the CPU-oracle baseline)
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR      (also writes the last timed step's outputs as DIR/<name>.npy)
 
 One process per GPU; every rank owns `--envs` (default 8192) environments, i.e. the env batch is sharded
 by index with per-GPU work fixed ("weak" scaling).  A step = one `rsr_step` launch =
 AutoReset/Episode wrappers + ctrl shaping + 4 physics substeps + reward/obs for every env of the rank.
 Inputs (state records, per-env domain-randomised model leaves, K pre-generated action tensors) are resident
-in HBM before the timed region.  Rank 0 prints one JSON line.
+in HBM before the timed region.  Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+line; whatever takes runs of its own (the sub-batched rate, the CPU-oracle baseline) runs only with --full.
 """
 from __future__ import annotations
 
@@ -31,6 +34,7 @@ VALU_PEAK_WAVE_INST_S = 256 * 4 * 2.4e9 / 2.0   # 1024 SIMDs, one wave64 VALU in
 
 
 PROFILE_ROUND = "round3"
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: at most this many bytes in all
 
 
 def csrc_sha16() -> str:
@@ -69,6 +73,55 @@ def pmc_profile(workload: str, n: int, dr_on: bool, sha: str):
     if "FETCH_SIZE" not in vals or "WRITE_SIZE" not in vals:
         return None, "PMC summaries lack FETCH_SIZE / WRITE_SIZE"
     return vals, f"profiles/{PROFILE_ROUND}_pmc_{{fetch,write,inst}}_{workload}.csv, collected on kernel sources {sha}"
+
+
+def state_arrays(state) -> dict:
+    """The tensors of the State a caller of env.step receives (obs, reward, done, pipeline_state.*, metrics.*, info.*, ...), by
+    dotted name.  An object reached twice under two names (Go2: state.data is state.pipeline_state) is kept under the first."""
+    import torch
+    out, seen = {}, set()
+
+    def walk(name, v):
+        if id(v) in seen:
+            return
+        seen.add(id(v))
+        if torch.is_tensor(v):
+            out[name] = v
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{name}.{k}", x)
+        elif hasattr(v, "__dict__"):
+            for k, x in vars(v).items():
+                walk(f"{name}.{k}" if name else k, x)
+    walk("", state)
+    return out
+
+
+def dump_outputs(outdir: str, per_env: dict, shared: dict, n_envs: int, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """Writes every array of `per_env` (leading dimension n_envs) and of `shared` as outdir/<name>.npy: float64 stays float64,
+    everything else becomes float32.  Over `limit` bytes in all, every per-env array keeps the same fixed, seeded sample of env
+    rows, whose indices go to env_index.npy; shared arrays are written whole."""
+    def host(v):
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        return a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    rows = {k: host(v) for k, v in per_env.items()}
+    whole = {k: host(v) for k, v in shared.items()}
+    for k, a in rows.items():
+        if a.ndim == 0 or a.shape[0] != n_envs:
+            raise ValueError(f"{k}: shape {a.shape} is not per env ({n_envs} rows)")
+    rows_bytes = sum(a.nbytes for a in rows.values())
+    whole_bytes = sum(a.nbytes for a in whole.values())
+    if rows_bytes + whole_bytes > limit:
+        row_bytes = rows_bytes / n_envs + 8          # + 8: the row's entry in env_index
+        m = int((limit - whole_bytes) // row_bytes)
+        if m < 1:
+            raise ValueError(f"outputs of {rows_bytes + whole_bytes} bytes do not fit in {limit} bytes even at one env")
+        idx = np.sort(np.random.default_rng(0).choice(n_envs, m, replace=False))
+        rows = {k: a[idx] for k, a in rows.items()}
+        whole["env_index"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in {**rows, **whole}.items():
+        np.save(os.path.join(outdir, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def self_launch(args) -> int:
@@ -204,14 +257,20 @@ def main():
     ap.add_argument("--no-dr", action="store_true", help="disable domain randomisation")
     ap.add_argument("--workload", default="cube", choices=["cube", "tshape", "go2", "go2rough", "handstand"],
                     help="cube = BASELINE headline (configs[1] family); tshape / go2 / go2rough = configs[2] / [3] / [4] families")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="length of the bounded CPU-oracle sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="length of the bounded CPU-oracle sample (with --full)")
     ap.add_argument("--sub-batches", type=int, default=2,
-                    help="also report the rate with the same envs stepped as this many independent sub-batches on their own HIP "
-                         "streams (0 = skip); `value` is always the lock-step figure")
+                    help="with --full, also report the rate with the same envs stepped as this many independent sub-batches on their "
+                         "own HIP streams (0 = skip); `value` is always the lock-step figure")
     ap.add_argument("--replicated-dr", action="store_true",
                     help="every GPU draws the same domain-randomisation key set, as the reference does (RSR/train.py:212-217); "
                          "default: one global key fan-out sliced per rank, so env i is the same env for any GPU count")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the sub-batched rate (--sub-batches) and the CPU-oracle baseline "
+                         "(--no-cpu-baseline, --cpu-seconds); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the State tensors env.step returns, "
+                         "and the rollout metrics) as DIR/<name>.npy; rank 0's envs")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: ranks rendezvous over gloo and run the launcher, the barrier / MAX-over-ranks timing and the "
                          "end-of-rollout gather on synthetic per-rank metrics (CPU test of the N > 1 plumbing)")
@@ -298,6 +357,8 @@ def main():
     elapsed = float(t.item())
     env_steps = float(metrics_all[:, 0].sum().item()) * args.steps
     timeouts = env.handoff_timeouts()         # outside the timed region: the work queue's sticky error word (0 on a healthy run)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state_arrays(state), {"rollout_metrics": metrics_all}, n)
 
     if rank == 0:
         bytes_per = {"cube": BYTES_PER_ENV_STEP if args.no_dr else BYTES_PER_ENV_STEP_DR, "tshape": 560, "go2": 2536, "go2rough": 2536, "handstand": 1580}[args.workload]
@@ -355,9 +416,9 @@ def main():
                         "(SURVEY.md 8d); the HBM fraction is reported because the metric names it, the VALU fraction beside it",
             },
         }
-        if args.sub_batches > 1 and world == 1 and n % args.sub_batches == 0:      # single-GPU extra; multi-GPU runs stay lean
+        if args.full and args.sub_batches > 1 and world == 1 and n % args.sub_batches == 0:   # single-GPU extra; multi-GPU runs stay lean
             out["sub_batched"] = sub_batched_rate(envdef, keys, dr, n, ep_len, actions, args.sub_batches, args.steps, args.warmup)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(env.blob, dr, seconds=args.cpu_seconds, nu=nu, act_std=act_std)
         print(json.dumps(out), flush=True)
     if world > 1:

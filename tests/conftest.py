@@ -8,8 +8,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REF = "/root/reference"
-CUBE_XML = os.path.join(REF, "ppo_train/airbot_training/cube.xml")
 ASSETS = os.path.join(ROOT, "rsr_mjx_amd", "assets")
 
 

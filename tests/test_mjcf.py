@@ -2,9 +2,8 @@
 import os
 
 import numpy as np
-import pytest
 
-from conftest import CUBE_XML, make_blob
+from conftest import make_blob
 from rsr_mjx_amd import mjcf
 from rsr_mjx_amd.model import topology_tables, unpack_blob
 
@@ -37,13 +36,82 @@ def test_cube_model_dimensions_and_layout(cube_model):
     np.testing.assert_allclose(A["pair_solref"][p], [0.015, 1.0])
 
 
-@pytest.mark.skipif(not os.path.exists(CUBE_XML), reason="reference tree not present (GPU box)")
-def test_committed_asset_is_the_compiler_output(cube_model):
-    fresh = mjcf.compile_mjcf(CUBE_XML)
-    assert set(fresh.arrays) == set(cube_model.arrays)
-    for k, v in fresh.arrays.items():
-        np.testing.assert_allclose(v, cube_model.arrays[k], rtol=1e-12, atol=1e-14, err_msg=k)
-    assert fresh.names == cube_model.names
+def test_compiler_output_of_a_stored_model():
+    """compile_mjcf on a stored input (tests/golden/compiler_pusher.xml, written for this test): analytic values of defaults,
+    orientations, inertia, joints, pairs, actuators and options, then every array and name against the stored output
+    (tests/golden/compiler_pusher.npz, tests/golden/make_compiler_golden.py) at rtol 1e-12."""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    m = mjcf.compile_mjcf(os.path.join(golden, "compiler_pusher.xml"))
+    A = m.arrays
+    assert m.name == "compiler_pusher"
+    assert (m.nq, m.nv, m.nu, m.nbody, m.njnt, m.ngeom, m.nsite, m.npair) == (19, 17, 4, 8, 7, 11, 2, 17)
+    # joints: hinge ranges and ref in degrees, free joints 7 qpos / 6 dofs, an unranged hinge is not limited
+    assert A["jnt_type"].tolist() == [mjcf.JNT_HINGE] * 3 + [mjcf.JNT_SLIDE, mjcf.JNT_FREE, mjcf.JNT_FREE, mjcf.JNT_HINGE]
+    assert A["jnt_qposadr"].tolist() == [0, 1, 2, 3, 4, 11, 18] and A["jnt_limited"].tolist() == [1, 1, 1, 1, 0, 0, 0]
+    np.testing.assert_allclose(A["jnt_range"][:3], np.deg2rad([[-170, 170], [-90, 90], [-120, 10]]), rtol=1e-12)
+    np.testing.assert_allclose(A["jnt_range"][3], [0, 0.05], rtol=1e-12)              # slide: metres, not converted
+    np.testing.assert_allclose(A["qpos0"][:4], [0, 0, np.deg2rad(5), 0], rtol=1e-12)
+    np.testing.assert_allclose(A["qpos0"][4:11], [0.5, 0.1, 0.45, 1, 0, 0, 0], rtol=1e-12)
+    np.testing.assert_allclose(A["qpos0"][14:18], [np.sqrt(0.5), 0, np.sqrt(0.5), 0], atol=1e-12)      # zaxis="1 0 0"
+    # defaults: class "arm" via childclass, <freejoint> takes no defaults, <joint type="free"> takes the main class
+    np.testing.assert_allclose(A["dof_damping"], [1.0] * 4 + [0.0] * 6 + [0.1] * 7)
+    np.testing.assert_allclose(A["dof_armature"], [0.02] * 4 + [0.0] * 13)
+    # orientations: euler (degrees, intrinsic xyz), axisangle, xyaxes, site quat
+    c15, s15, c10, s10 = np.cos(np.deg2rad(15)), np.sin(np.deg2rad(15)), np.cos(np.deg2rad(10)), np.sin(np.deg2rad(10))
+    np.testing.assert_allclose(A["body_quat"][m.id("body", "upper")], [c15, 0, s15, 0], atol=1e-12)
+    np.testing.assert_allclose(A["body_quat"][m.id("body", "fore")], [c10, 0, 0, s10], atol=1e-12)
+    np.testing.assert_allclose(mjcf.quat_to_mat(A["body_quat"][m.id("body", "finger")]), [[1, 0, 0], [0, 0, -1], [0, 1, 0]], atol=1e-12)
+    np.testing.assert_allclose(A["site_quat"][m.id("site", "tip")], [0, 0, 0, 1])
+    # fromto box: half length along the segment, centred on it, z axis along from - to
+    g = m.id("geom", "upper_bar")
+    np.testing.assert_allclose(A["geom_size"][g], [0.02, 0.02, 0.15], rtol=1e-12)
+    np.testing.assert_allclose(A["geom_pos"][g], [0.15, 0, 0], atol=1e-12)
+    np.testing.assert_allclose(mjcf.quat_to_mat(A["geom_quat"][g])[:, 2], [-1, 0, 0], atol=1e-12)
+    # inertia: <inertial> wins over geoms; geoms by density or mass; fullinertia diagonalised in decreasing order
+    crate, ball, fore, wheel, finger = (m.id("body", b) for b in ("crate", "ball", "fore", "wheel", "finger"))
+    np.testing.assert_allclose(A["body_mass"][m.id("body", "base")], 2.0)
+    np.testing.assert_allclose(A["body_mass"][crate], 500 * 0.08 ** 3, rtol=1e-12)
+    np.testing.assert_allclose(A["body_inertia"][crate], 500 * 0.08 ** 3 * 2 * 0.04 ** 2 / 3, rtol=1e-12)
+    np.testing.assert_allclose(A["body_inertia"][ball], 0.4 * 0.2 * 0.05 ** 2, rtol=1e-12)
+    bar = 700 * 8 * 0.1 * 0.015 * 0.015
+    np.testing.assert_allclose(A["body_mass"][fore], bar + 0.3, rtol=1e-12)
+    np.testing.assert_allclose(A["body_ipos"][fore], [(bar * 0.1 + 0.3 * 0.2) / (bar + 0.3), 0, 0], atol=1e-12)
+    np.testing.assert_allclose(A["body_mass"][wheel], 800 * np.pi * 0.1 ** 2 * 0.04 + 1000 * 4 / 3 * np.pi * 0.03 * 0.02 * 0.01, rtol=1e-12)
+    full = np.array([[1e-4, 1e-5, 0], [1e-5, 2e-4, 0], [0, 0, 3e-4]])
+    np.testing.assert_allclose(A["body_inertia"][finger], np.sort(np.linalg.eigvalsh(full))[::-1], rtol=1e-10)
+    # collision pairs: kinds by geom type, contype / conaffinity filter, <exclude>, parent filter, priority and solmix mixing
+    pairs = {(int(a), int(b)): (int(k), float(r), int(c)) for a, b, k, r, c in
+             zip(A["pair_geom1"], A["pair_geom2"], A["pair_kind"], A["pair_solref"][:, 0], A["pair_condim"])}
+    gid = lambda n: m.id("geom", n)
+    assert pairs[(gid("ground"), gid("ball_geom"))][0] == mjcf.PAIR_PLANE_SPHERE
+    assert pairs[(gid("ground"), gid("wheel_disc"))][0] == mjcf.PAIR_PLANE_CYLINDER
+    assert pairs[(gid("ground"), gid("crate_box"))][0] == mjcf.PAIR_PLANE_BOX
+    assert pairs[(gid("bench"), gid("crate_box"))][0] == mjcf.PAIR_BOX_BOX
+    assert not any(gid(n) in p for p in pairs for n in ("fore_bar", "roller", "wheel_weight") if (gid("ground") in p or gid("bench") in p))
+    assert (gid("base_plate"), gid("upper_bar")) not in pairs and gid("roller") not in {x for p in pairs for x in p}
+    np.testing.assert_allclose(pairs[(gid("ground"), gid("base_plate"))][1], 0.5 * 0.01 + 0.5 * 0.015, rtol=1e-12)
+    np.testing.assert_allclose(pairs[(gid("bench"), gid("base_plate"))][1], 0.75 * 0.03 + 0.25 * 0.015, rtol=1e-12)
+    assert pairs[(gid("bench"), gid("crate_box"))][1:] == (0.015, 4)                  # priority: the crate's parameters
+    # actuators: position (class kv, own kp), motor (gear, force limit), velocity, general with inheritrange
+    np.testing.assert_allclose(A["actuator_gainprm"][:, 0], [50, 1, 3, 40])
+    np.testing.assert_allclose(A["actuator_biasprm"], [[0, -50, -2], [0, 0, 0], [0, 0, -3], [0, -40, -1]])
+    np.testing.assert_allclose(A["actuator_gear"], [1, 20, 1, 1])
+    np.testing.assert_allclose(A["actuator_ctrlrange"], [[-3, 3], [-1, 1], [0, 0], [0, 0.05]])
+    assert A["actuator_ctrllimited"].tolist() == [1, 1, 0, 1] and A["actuator_forcelimited"].tolist() == [0, 1, 0, 0]
+    # equality, keyframe, options
+    np.testing.assert_allclose(A["eq_data"], [[0, -0.5, 0, 0, 0]])
+    assert A["eq_obj1id"].tolist() == [2] and A["eq_obj2id"].tolist() == [1]
+    np.testing.assert_allclose(A["key_ctrl"], [[0, 0, 0, 0.02]])
+    np.testing.assert_allclose(A["key_qpos"], A["qpos0"][None])
+    assert A["opt_timestep"][0] == 0.004 and A["opt_iterations"][0] == 8 and A["opt_ls_iterations"][0] == 12
+    assert A["opt_integrator"][0] == mjcf.INT_IMPLICITFAST and A["opt_impratio"][0] == 1.5 and A["opt_disable_eulerdamp"][0] == 1
+    np.testing.assert_allclose(A["opt_gravity"], [0, 0, -9.8])
+    # everything else, as stored
+    stored = mjcf.CompiledModel.load(os.path.join(golden, "compiler_pusher.npz"))
+    assert set(A) == set(stored.arrays)
+    for k, v in A.items():
+        np.testing.assert_allclose(v, stored.arrays[k], rtol=1e-12, atol=1e-14, err_msg=k)
+    assert m.names == stored.names and m.name == stored.name
 
 
 def test_blob_roundtrip_and_topology(cube_model):

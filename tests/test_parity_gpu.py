@@ -267,10 +267,10 @@ def test_full_size_properties(setup):
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the fields the driver reads, the roofline and cpu_baseline objects included."""
+    """bench.py --full prints ONE JSON line with the fields the driver reads, the roofline and cpu_baseline objects included."""
     import json, subprocess, sys, os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--cpu-seconds", "1.0"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--cpu-seconds", "1.0", "--full"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -291,6 +291,36 @@ def test_bench_line_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == "env-steps/s" and "oracle" in c["sample"]
     assert d["value"] > 20 * c["value"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench run times the headline only (no sub-batched rate, no CPU baseline); --dump-outputs writes the State of the
+    last timed step, and two runs with the same arguments write the same arrays."""
+    import json, subprocess, sys, os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append([l for l in out.stdout.splitlines() if l.strip()])
+        assert len(lines[-1]) == 1, lines[-1]
+    d = json.loads(lines[0][0])
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "env-steps/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 8192 * 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-6
+    assert "cpu_baseline" not in d and "sub_batched" not in d
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"obs.npy", "reward.npy", "done.npy", "pipeline_state.qpos.npy", "rollout_metrics.npy"} <= set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64), f
+        np.testing.assert_array_equal(a, b, err_msg=f)
+    obs = np.load(tmp_path / "a" / "obs.npy")
+    assert obs.shape[0] == 8192 and np.isfinite(obs).all()
+    assert np.load(tmp_path / "a" / "rollout_metrics.npy")[0, 0] == 8192
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end evidence on the GPU box for the workloads: rocprofv3 kernel-trace stats of a bench run, then the PMC passes
 # (each in its own run with --kernel-trace only, as the pool requires), summarised into profiles/<round>_*_<workload>.csv with
-# the hash of the kernel sources (tools/rocpd_summary.py), then the plain bench lines.
+# the hash of the kernel sources (tools/rocpd_summary.py), then the bench lines with --full and three plain headline lines.
 # usage: ROUND=round3 tools/gpu_final_profile.sh [workloads...]      (default: cube tshape go2 go2rough handstand)
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
@@ -29,10 +29,10 @@ for w in $WL; do
   done
   echo "$w pmc done"
 done
-# the plain bench lines quote the PMC summaries of THIS run (bench.py binds them to the hash of the kernel sources)
+# the --full bench lines quote the PMC summaries of THIS run (bench.py binds them to the hash of the kernel sources)
 cp $P/${ROUND}_pmc_*.csv $R/profiles/
 cd $R
-for w in $WL; do timeout -k 10 200 python3 bench.py --workload $w --steps 300 --warmup 50 > $P/${ROUND}_bench_$w.json 2> $O/bench_$w.err; echo "$w bench done"; done
+for w in $WL; do timeout -k 10 200 python3 bench.py --workload $w --steps 300 --warmup 50 --full > $P/${ROUND}_bench_$w.json 2> $O/bench_$w.err; echo "$w bench done"; done
 # the headline under the driver's protocol (20 timed steps after 5 warm-up steps: the transient after reset), three times
 for i in 1 2 3; do timeout -k 10 100 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --sub-batches 0 2>/dev/null; done > $P/${ROUND}_bench_cube_20_5.jsonl
 ls $P
