@@ -36,6 +36,13 @@ DR_FIELDS = [
     "body_ipos", "qpos0", "dof_armature", "actuator_gainprm", "actuator_biasprm",
 ]
 
+# enum rsr_physics_field (include/rsr_physics.h), in order
+PHYS_FIELDS = ["qacc", "actuator_force", "xquat", "ncon", "contact", "ncon_dropped"]
+
+# every symbol include/rsr_physics.h declares
+PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step", "rsr_physics_forward", "rsr_physics_forward_envs",
+                "rsr_physics_view"]
+
 SYMBOLS = [
     "rsr_model_create", "rsr_model_dims", "rsr_model_destroy", "rsr_batch_create", "rsr_batch_destroy",
     "rsr_batch_set_dr", "rsr_batch_set_dr_field", "rsr_batch_set_schedule", "rsr_batch_set_whole_envs", "rsr_batch_set_priority", "rsr_batch_set_action_repeat", "rsr_batch_check", "rsr_batch_set_fault_injection", "rsr_rollout_metrics", "rsr_reset", "rsr_step", "rsr_view", "rsr_batch_set_debug",
@@ -69,6 +76,13 @@ def lib() -> C.CDLL:
     L.rsr_reset.argtypes = [vp, vp, vp]
     L.rsr_step.argtypes = [vp, vp, vp]
     L.rsr_view.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p]
+    L.rsr_physics_create.argtypes = [vp, C.POINTER(vp)]
+    L.rsr_physics_destroy.argtypes = [vp]
+    L.rsr_physics_destroy.restype = None
+    L.rsr_physics_step.argtypes = [vp, vp, i32, vp]
+    L.rsr_physics_forward.argtypes = [vp, vp]
+    L.rsr_physics_forward_envs.argtypes = [vp, vp, i32, vp]
+    L.rsr_physics_view.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

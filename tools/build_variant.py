@@ -18,12 +18,24 @@ else:
         for f in ("rsr_mjx_amd/csrc/rsr_mjx.hip", "rsr_mjx_amd/csrc/rsr_device.hpp", "rsr_mjx_amd/csrc/rsr_solver.hpp", "include/rsr_mjx.h"):
             dst = os.path.join(tmp, f); os.makedirs(os.path.dirname(dst), exist_ok=True)
             open(dst, "wb").write(subprocess.check_output(["git", "-C", ROOT, "show", f"{rev}:{f}"]))
+        physics = True           # revisions with the physics-level API compile every unit from csrc/physics/rsr_physics.hip
+        for f in ("rsr_mjx_amd/csrc/physics/rsr_physics.hip", "include/rsr_physics.h"):
+            try:
+                src = subprocess.check_output(["git", "-C", ROOT, "show", f"{rev}:{f}"], stderr=subprocess.DEVNULL)
+            except subprocess.CalledProcessError:
+                physics = False
+                continue
+            dst = os.path.join(tmp, f); os.makedirs(os.path.dirname(dst), exist_ok=True)
+            open(dst, "wb").write(src)
         csrc = os.path.join(tmp, "rsr_mjx_amd", "csrc")
-        old = B.CSRC; B.CSRC = csrc
+        old, old_src = B.CSRC, B.SOURCES
+        B.CSRC = csrc
+        if not physics:
+            B.SOURCES = ["rsr_mjx.hip"]
         try:
             B.compile_lib(os.path.join(csrc, "lib.so"), extra_flags=args)
         finally:
-            B.CSRC = old
+            B.CSRC, B.SOURCES = old, old_src
         shutil.copy(os.path.join(csrc, "lib.so"), out)
     finally:
         shutil.rmtree(tmp)
