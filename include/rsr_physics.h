@@ -5,6 +5,8 @@
  *   rsr_physics_forward <- mjx_env.init(model, qpos, qvel, ctrl): one mjx.forward on the record's qpos / qvel / ctrl
  *                          (qacc_warmstart as the record holds it; the caller zeroes it first to match init).
  *   rsr_physics_step    <- mjx_env.step(model, data, ctrl, n_substeps): writes ctrl into the record, then nsteps x mjx.step.
+ *   rsr_physics_rollout <- mujoco.rollout.rollout / lax.scan(mjx.step): T control steps in one launch, trajectories [N, T, w].
+ *   rsr_physics_set_sensors: the site sensors of data.sensordata (RSR_P_SENSORDATA, and a rollout's sensordata rows).
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
@@ -47,12 +49,62 @@ int rsr_physics_forward_envs(rsr_physics* p, const int32_t* env_ids, int count, 
  *   RSR_P_NCON            [1]               active contacts kept (at most ncon_max), as float
  *   RSR_P_CONTACT         [ncon_max*9]      per contact slot: dist, pos[3], frame normal[3], geom1, geom2 (geoms as float);
  *                                           slots >= ncon hold zeros and geom ids -1
- *   RSR_P_NCON_DROPPED    [1]               active contacts beyond ncon_max that the kernel dropped, as float */
+ *   RSR_P_NCON_DROPPED    [1]               active contacts beyond ncon_max that the kernel dropped, as float
+ *   RSR_P_SENSORDATA      [nsensordata]     data.sensordata of the sensor table (rsr_physics_set_sensors) at the last physics
+ *                                           call; width 0 while no table is set.  Row stride RSR_MAX_SENSORDATA, its own
+ *                                           buffer: the view's pointer does not move when the table changes */
 enum rsr_physics_field {
-  RSR_P_QACC = 0, RSR_P_ACTUATOR_FORCE, RSR_P_XQUAT, RSR_P_NCON, RSR_P_CONTACT, RSR_P_NCON_DROPPED,
+  RSR_P_QACC = 0, RSR_P_ACTUATOR_FORCE, RSR_P_XQUAT, RSR_P_NCON, RSR_P_CONTACT, RSR_P_NCON_DROPPED, RSR_P_SENSORDATA,
   RSR_P_COUNT
 };
 int rsr_physics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
+
+/* Site sensors (data.sensordata), MuJoCo's definitions for objtype "site".  R, p: the site's frame and position; v, w: its
+ * linear and angular velocity in the world frame (object velocity at the site); ref: a second site.
+ *   RSR_S_GYRO           [3]   R^T w
+ *   RSR_S_VELOCIMETER    [3]   R^T v
+ *   RSR_S_ACCELEROMETER  [3]   R^T (linear acceleration at the site, from cacc) + (R^T w) x (R^T v).  Go2 models only, and only on
+ *                              a site of the body whose acceleration bias the kernels track (the IMU's); one such site per table
+ *   RSR_S_FRAMEPOS       [3]   p, or R_ref^T (p - p_ref) with a ref site
+ *   RSR_S_FRAMEXAXIS     [3]   first column of R
+ *   RSR_S_FRAMEZAXIS     [3]   third column of R
+ *   RSR_S_FRAMEQUAT      [4]   xquat[body] * site_quat (w, x, y, z), not canonicalised
+ *   RSR_S_FRAMELINVEL    [3]   v
+ *   RSR_S_FRAMEANGVEL    [3]   w
+ * Only framepos takes a ref site. */
+enum rsr_sensor_type {
+  RSR_S_GYRO = 0, RSR_S_VELOCIMETER, RSR_S_ACCELEROMETER, RSR_S_FRAMEPOS, RSR_S_FRAMEXAXIS, RSR_S_FRAMEZAXIS, RSR_S_FRAMEQUAT,
+  RSR_S_FRAMELINVEL, RSR_S_FRAMEANGVEL,
+  RSR_S_COUNT
+};
+#define RSR_MAX_SENSORDATA 64
+
+/* The sensor table: nsensor rows of 4 int32 (host memory): type, site id, ref site id or -1, address (first column in sensordata;
+ * row i starts where row i-1 ends, row 0 at 0).  At most RSR_MAX_SENSORDATA floats in all.  nsensor = 0 clears the table.
+ * Everything is checked before any device work (bad ids, types, addresses, ref sites: RSR_ERR_ARG; an accelerometer the kernels
+ * cannot evaluate: RSR_ERR_UNSUPPORTED); on error the previous table stays.  Waits for the device (the table is read by launches
+ * in flight).  With a table set, rsr_physics_step / _forward / _forward_envs also fill RSR_P_SENSORDATA after their last forward
+ * pass; with none set they run exactly as before. */
+int rsr_physics_set_sensors(rsr_physics* p, const int32_t* table, int nsensor);
+
+/* Trajectory buffers of rsr_physics_rollout, device float32, env-major [num_envs, T, width]; a NULL pointer is not recorded.
+ *   qpos [nq], qvel [nv], time [1]                   the state after control step t
+ *   actuator_force [nu], ncon [1], sensordata [nsensordata]   the last forward pass of control step t, before its final
+ *                                                             integration (as the side buffer after rsr_physics_step) */
+typedef struct rsr_rollout_out {
+  float* qpos;
+  float* qvel;
+  float* time;
+  float* actuator_force;
+  float* ncon;
+  float* sensordata;
+} rsr_rollout_out;
+
+/* T control steps in one launch: for t = 0 .. T-1, ctrl[:, t, :] then nsteps x mjx.step, then the rows t of `out`.  ctrl: device
+ * float32 [num_envs, T, nu].  Leaves the record, the side buffer and RSR_P_SENSORDATA exactly as T calls of rsr_physics_step
+ * with ctrl[:, t, :] would.  out may be NULL (nothing recorded).  RSR_ERR_ARG: null handle or ctrl, T < 1, nsteps < 1,
+ * sensordata requested with no sensor table set. */
+int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int nsteps, const rsr_rollout_out* out, void* hip_stream);
 
 #ifdef __cplusplus
 }

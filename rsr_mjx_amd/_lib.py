@@ -37,11 +37,23 @@ DR_FIELDS = [
 ]
 
 # enum rsr_physics_field (include/rsr_physics.h), in order
-PHYS_FIELDS = ["qacc", "actuator_force", "xquat", "ncon", "contact", "ncon_dropped"]
+PHYS_FIELDS = ["qacc", "actuator_force", "xquat", "ncon", "contact", "ncon_dropped", "sensordata"]
 
 # every symbol include/rsr_physics.h declares
 PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step", "rsr_physics_forward", "rsr_physics_forward_envs",
-                "rsr_physics_view"]
+                "rsr_physics_view", "rsr_physics_set_sensors", "rsr_physics_rollout"]
+
+# enum rsr_sensor_type (include/rsr_physics.h), in order, with each type's width
+SENSOR_TYPES = ["gyro", "velocimeter", "accelerometer", "framepos", "framexaxis", "framezaxis", "framequat", "framelinvel",
+                "frameangvel"]
+SENSOR_WIDTH = {"gyro": 3, "velocimeter": 3, "accelerometer": 3, "framepos": 3, "framexaxis": 3, "framezaxis": 3, "framequat": 4,
+                "framelinvel": 3, "frameangvel": 3}
+MAX_SENSORDATA = 64
+
+
+class RolloutOut(C.Structure):
+    """struct rsr_rollout_out (include/rsr_physics.h): device pointers, NULL = not recorded."""
+    _fields_ = [(n, C.c_void_p) for n in ("qpos", "qvel", "time", "actuator_force", "ncon", "sensordata")]
 
 SYMBOLS = [
     "rsr_model_create", "rsr_model_dims", "rsr_model_destroy", "rsr_batch_create", "rsr_batch_destroy",
@@ -83,6 +95,8 @@ def lib() -> C.CDLL:
     L.rsr_physics_forward.argtypes = [vp, vp]
     L.rsr_physics_forward_envs.argtypes = [vp, vp, i32, vp]
     L.rsr_physics_view.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p]
+    L.rsr_physics_set_sensors.argtypes = [vp, vp, i32]
+    L.rsr_physics_rollout.argtypes = [vp, vp, i32, i32, vp, vp]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

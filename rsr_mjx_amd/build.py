@@ -12,7 +12,7 @@ LIB = os.path.join(CSRC, "librsrmjx.so")
 # physics-level API (include/rsr_physics.h) with each family's physics kernels in that family's unit.
 SOURCES = [os.path.join("physics", "rsr_physics.hip")]
 HEADERS = ["rsr_mjx.hip", "rsr_device.hpp", "rsr_solver.hpp", os.path.join("..", "..", "include", "rsr_mjx.h"),
-           os.path.join("..", "..", "include", "rsr_physics.h")]
+           os.path.join("..", "..", "include", "rsr_physics.h"), os.path.join("physics", "rsr_sensors.hpp")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # Three translation units from the one source: the cube kernels + the C ABI; the T-shape kernels and the Go2 kernels each on their own
 # with the SLP vectoriser off (its packed-fp32 pairing costs the Go2 and T-shape kernels ~3 % and gains the cube kernels ~0.5 %;

@@ -21,6 +21,7 @@ import numpy as np
 from .. import _lib, prng
 from ..mjcf import CompiledModel, compile_mjcf
 from ..model import model_fields, pack_blob
+from ..sensors import AIRBOT_ENDPOINT_SENSORS
 from . import config as cfg
 
 _ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -93,6 +94,12 @@ class AirbotPlayBase:
     @property
     def action_size(self) -> int:
         return self.sys.nu
+
+    @property
+    def sensors(self):
+        """a Physics sensor spec (rsr_mjx_amd/sensors.py): the Airbot models declare no sensors; the endpoint site's world position
+        and velocity as an example"""
+        return list(AIRBOT_ENDPOINT_SENSORS)
 
     @property
     def dt(self) -> float:

@@ -18,6 +18,7 @@ import numpy as np
 from .. import prng
 
 from ..mjcf import CompiledModel, compile_mjcf
+from ..sensors import GO2_FULL_SENSORS, GO2_JOYSTICK_SENSORS
 from . import config as cfg
 from .airbot import BatchedEnv, State, _ASSETS
 
@@ -49,6 +50,7 @@ class Joystick:
 
     _obs_dim = cfg.GO2_OBS_DIM
     _metrics = cfg.GO2_METRICS
+    _sensors = GO2_JOYSTICK_SENSORS          # go2_mjx_feetonly*.xml
 
     def __init__(self, task: str = "flat_terrain", config: Optional[dict] = None,
                  config_overrides: Optional[Dict[str, Any]] = None, model_path: Optional[str] = None, device: str = "cuda:0"):
@@ -82,6 +84,11 @@ class Joystick:
     @property
     def action_size(self) -> int:
         return self.sys.nu
+
+    @property
+    def sensors(self):
+        """the model's <sensor> list as a Physics sensor spec (rsr_mjx_amd/sensors.py)"""
+        return list(self._sensors)
 
     @property
     def dt(self) -> float:
@@ -192,6 +199,7 @@ class Handstand(Joystick):
     go2_mjx.xml: 4 foot spheres, 20 capsules, 6 cylinders against the floor plane): 45-dim `state`, 94-dim `privileged_state`,
     eleven reward terms, termination on a fall, an unwanted contact or the energy threshold."""
 
+    _sensors = GO2_FULL_SENSORS              # go2_mjx.xml
     _obs_dim = cfg.HANDSTAND_OBS_DIM
     _priv_dim = cfg.HANDSTAND_PRIV_OBS_DIM
     _metrics = cfg.HANDSTAND_METRICS

@@ -2,6 +2,8 @@
 
     mjx_env.init(model, qpos, qvel, ctrl)      ->  Physics.set_state(qpos, qvel, ctrl)   (one mjx.forward)
     mjx_env.step(model, data, ctrl, n_substeps) ->  Physics.step(ctrl, nsteps)           (nsteps x mjx.step)
+    mujoco.rollout.rollout / lax.scan(mjx.step)  ->  Physics.rollout(ctrl [N, T, nu])     (one launch, trajectories [N, T, w])
+    mjx_env.get_sensor_data(model, data, name)  ->  Physics.sensor(name)                 (site sensors, Physics.set_sensors)
 
 `Physics(env)` shares the batch of a BatchedEnv (Airbot cube / sf / T-shape, Go2 joystick, handstand / footstand): the same model,
 the same per-env domain randomisation, the same record and the same stream.  The pipeline fields it exposes are the record's own
@@ -12,9 +14,12 @@ of the last forward pass, before the final integration.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Any, Dict, Optional
+from typing import Any, Dict, Optional, Sequence
 
 from . import _lib
+from . import sensors as _sensors
+
+ROLLOUT_FIELDS = ("qpos", "qvel", "time", "actuator_force", "ncon", "sensordata")
 
 
 class _DevArray:
@@ -25,10 +30,18 @@ class _DevArray:
                                              strides=tuple(4 * int(s) for s in strides_elems))
 
 
-class Physics:
-    """Physics-only stepping, forward and state setting on the envs of `env` (a BatchedEnv)."""
+def _view(ptr, shape, stride, device):
+    import torch
+    if shape[1] == 0:                              # (sensordata while no sensors are set)
+        return torch.empty((shape[0], 0), dtype=torch.float32, device=device)
+    return torch.as_tensor(_DevArray(ptr.value, (shape[0], shape[1]), (stride[0], stride[1])), device=device)
 
-    def __init__(self, env):
+
+class Physics:
+    """Physics-only stepping, forward, rollouts and state setting on the envs of `env` (a BatchedEnv).  `sensors`: a sensor spec
+    (see set_sensors), e.g. the env definition's `sensors`; None: no sensor stage."""
+
+    def __init__(self, env, sensors: Optional[Sequence[tuple]] = None):
         import torch
         self.env = env
         self.num_envs = env.num_envs
@@ -48,11 +61,15 @@ class Physics:
         for fid, name in enumerate(_lib.PHYS_FIELDS):
             ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
             _lib.check(_lib.lib().rsr_physics_view(self._h, fid, C.byref(ptr), shape, stride))
-            side[name] = torch.as_tensor(_DevArray(ptr.value, (shape[0], shape[1]), (stride[0], stride[1])), device=self.device)
+            side[name] = _view(ptr, shape, stride, self.device)
         self._side = side
         self.qacc = side["qacc"]
         self.actuator_force = side["actuator_force"]
         self.xquat = side["xquat"].unflatten(1, (d.nbody, 4))
+        self._sensor_adr: Dict[str, tuple] = {}
+        self.sensordata = side["sensordata"]
+        if sensors is not None:
+            self.set_sensors(sensors)
 
     def __del__(self):
         try:
@@ -74,6 +91,81 @@ class Physics:
 
     def _stream(self):
         return self.env._stream()
+
+    def _accel_site(self) -> Optional[int]:
+        """the site whose body's acceleration the kernels track (env_ids[0] of the Go2 family: the IMU), or None"""
+        from .envs import config as cfg
+        if int(self.dims.env_kind) in (cfg.ENV_GO2, cfg.ENV_GO2_HANDSTAND):
+            return self.env.sys.id("site", "imu")
+        return None
+
+    def set_sensors(self, spec: Optional[Sequence[tuple]]) -> None:
+        """Sets the sensor table: `spec` is a list of (name, type, site, ref_site=None), sites by name, types of
+        _lib.SENSOR_TYPES (None or []: no sensors).  From then on step / forward / set_state also fill `sensordata`
+        [N, nsensordata] (MuJoCo's sensordata layout, sensors in spec order), and rollout can record it."""
+        import torch
+        spec = list(spec or [])
+        table, where = _sensors.sensor_table(self.env.sys, spec, self._accel_site())
+        _lib.check(_lib.lib().rsr_physics_set_sensors(self._h, table.ctypes.data_as(C.c_void_p) if len(table) else None, len(table)))
+        self._sensor_adr = where
+        ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
+        _lib.check(_lib.lib().rsr_physics_view(self._h, _lib.PHYS_FIELDS.index("sensordata"), C.byref(ptr), shape, stride))
+        self.sensordata = _view(ptr, shape, stride, self.device)
+        self._side["sensordata"] = self.sensordata
+
+    @property
+    def nsensordata(self) -> int:
+        return int(self.sensordata.shape[1])
+
+    def sensor(self, name: str, data=None):
+        """The columns of sensor `name` in `data` (default: the current sensordata [N, nsensordata]; a rollout's
+        sensordata [N, T, nsensordata] works too): mjx_env.get_sensor_data."""
+        if name not in self._sensor_adr:
+            raise KeyError(f"no sensor {name!r}; set: {list(self._sensor_adr)}")
+        adr, w = self._sensor_adr[name]
+        data = self.sensordata if data is None else data
+        return data[..., adr:adr + w]
+
+    def rollout(self, ctrl, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), qpos0=None, qvel0=None,
+                ctrl0=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """T control steps in one launch: for t < T, ctrl[:, t] then `nsteps` (default n_substeps) x mjx.step.  ctrl is
+        [num_envs, T, nu].  With qpos0 / qvel0 / ctrl0, set_state runs first (mjx_env.init).  Returns {field: [N, T, w]} for
+        `fields` (ROLLOUT_FIELDS): qpos, qvel, time after each control step; actuator_force, ncon, sensordata of its last forward
+        pass.  `out`: caller-owned float32 tensors to fill instead of new ones.  Afterwards the record and the side buffer hold
+        what T calls of step would leave."""
+        import torch
+        nsteps = self.n_substeps if nsteps is None else int(nsteps)
+        if nsteps < 1:
+            raise ValueError(f"rollout: nsteps must be >= 1, got {nsteps}")
+        c = torch.as_tensor(ctrl, dtype=torch.float32, device=self.device)
+        if c.dim() != 3 or c.shape[0] != self.num_envs or c.shape[2] != self.dims.nu or c.shape[1] < 1:
+            raise ValueError(f"rollout expects ctrl of shape ({self.num_envs}, T >= 1, {self.dims.nu}), got {tuple(c.shape)}")
+        T = int(c.shape[1])
+        fields = tuple(fields)
+        bad = [f for f in fields if f not in ROLLOUT_FIELDS]
+        if bad:
+            raise ValueError(f"rollout: unknown fields {bad}; recordable: {ROLLOUT_FIELDS}")
+        if "sensordata" in fields and self.nsensordata == 0:
+            raise ValueError("rollout: sensordata requested but no sensors are set (set_sensors)")
+        d = self.dims
+        width = dict(qpos=d.nq, qvel=d.nv, time=1, actuator_force=d.nu, ncon=1, sensordata=self.nsensordata)
+        res, ptrs = {}, _lib.RolloutOut()
+        out = out or {}
+        for f in fields:
+            shape = (self.num_envs, T, width[f])
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=torch.float32, device=self.device)
+            elif (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != c.device):
+                raise ValueError(f"rollout: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {c.device}")
+            res[f] = t
+            setattr(ptrs, f, t.data_ptr())
+        if qpos0 is not None or qvel0 is not None or ctrl0 is not None:
+            self.set_state(qpos0, qvel0, ctrl0)
+        c = c.contiguous()
+        self._ctrl_in = c                          # kept alive until the next call (the launch is asynchronous)
+        _lib.check(_lib.lib().rsr_physics_rollout(self._h, C.c_void_p(c.data_ptr()), T, nsteps, C.byref(ptrs), self._stream()))
+        return res
 
     def forward(self) -> None:
         """mjx.forward on every env: refreshes xpos, xquat, site_xpos, qacc (and qacc_warmstart), actuator_force and the contacts
