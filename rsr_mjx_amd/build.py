@@ -8,23 +8,27 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "librsrmjx.so")
-# Every unit is compiled from physics/rsr_physics.hip, which includes the env kernels and C ABI of rsr_mjx.hip and adds the
-# physics-level API (include/rsr_physics.h) with each family's physics kernels in that family's unit.
-SOURCES = [os.path.join("physics", "rsr_physics.hip")]
-HEADERS = ["rsr_mjx.hip", "rsr_device.hpp", "rsr_solver.hpp", os.path.join("..", "..", "include", "rsr_mjx.h"),
-           os.path.join("..", "..", "include", "rsr_physics.h"), os.path.join("physics", "rsr_sensors.hpp")]
+# One translation unit per source: the kernels of one model family each (cube, T-shape, Go2: rsr_launch.hpp) and the two host
+# units (the C ABI of include/rsr_mjx.h and of include/rsr_physics.h).  The T-shape and Go2 units are built with the SLP vectoriser
+# off (its packed-fp32 pairing costs the Go2 and T-shape kernels ~3 % and gains the cube kernels ~0.5 %; measured A/B on one box).
+# Kernels of one unit also perturb each other's register allocation: a unit holds one model family.
+UNITS = [("rsr_cube.hip", []), ("rsr_tshape.hip", ["-fno-slp-vectorize"]), ("rsr_go2.hip", ["-fno-slp-vectorize"]),
+         ("rsr_mjx.hip", []), (os.path.join("physics", "rsr_physics.hip"), [])]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
-# Three translation units from the one source: the cube kernels + the C ABI; the T-shape kernels and the Go2 kernels each on their own
-# with the SLP vectoriser off (its packed-fp32 pairing costs the Go2 and T-shape kernels ~3 % and gains the cube kernels ~0.5 %;
-# measured A/B on one box).  Kernels of one unit also perturb each other's register allocation: a unit holds one model family.
-UNITS = [("rsr_main.o", []), ("rsr_tshape.o", ["-DRSR_TU_TSHAPE", "-fno-slp-vectorize"]), ("rsr_go2.o", ["-DRSR_TU_GO2", "-fno-slp-vectorize"])]
+
+
+def _sources() -> list:
+    """Every file the library is built from: csrc/ and csrc/physics/ sources and headers, and include/."""
+    inc = os.path.join(_HERE, "..", "include")
+    dirs = [CSRC, os.path.join(CSRC, "physics"), inc]
+    return [os.path.join(d, f) for d in dirs for f in sorted(os.listdir(d)) if f.endswith((".hip", ".hpp", ".h"))]
 
 
 def _stale(lib: str) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS) or os.path.getmtime(__file__) > t
+    return any(os.path.getmtime(f) > t for f in _sources()) or os.path.getmtime(__file__) > t
 
 
 def compile_lib(lib: str = LIB, extra_flags=(), verbose: bool = False) -> str:
@@ -32,9 +36,9 @@ def compile_lib(lib: str = LIB, extra_flags=(), verbose: bool = False) -> str:
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     stem = os.path.splitext(os.path.basename(lib))[0]
     objs, procs = [], []
-    for obj, flags in UNITS:
-        o = os.path.join(CSRC, f"{stem}.{obj}")
-        cmd = [hipcc] + HIPCC_FLAGS + list(flags) + list(extra_flags) + ["-c", os.path.join(CSRC, SOURCES[0]), "-o", o]
+    for src, flags in UNITS:
+        o = os.path.join(CSRC, f"{stem}.{os.path.splitext(os.path.basename(src))[0]}.o")
+        cmd = [hipcc] + HIPCC_FLAGS + list(flags) + list(extra_flags) + ["-c", os.path.join(CSRC, src), "-o", o]
         if verbose:
             cmd.append("-Rpass-analysis=kernel-resource-usage")
         objs.append(o)

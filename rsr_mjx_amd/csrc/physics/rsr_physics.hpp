@@ -1,0 +1,39 @@
+// rsr_physics.hpp -- the physics layer's side-buffer layout and launch arguments (host and device).
+#pragma once
+#include "../../../include/rsr_physics.h"
+#include "../rsr_solver.hpp"
+
+namespace rsr {
+
+// One entry per output element (host-expanded from the table): type, site, ref site or -1, component.  nsd = 0: no stage.
+// acc_site: the one site of the table's accelerometers (-1: none); only compiled in for Dims::XFRC.
+struct SensArgs {
+  const int4* el;
+  int nsd, acc_site;
+};
+
+// Side buffer (rsr_physics_view), per env, floats: qacc [nv] | actuator_force [nu] | xquat [nbody*4] | ncon | contacts [ncon_max][9]
+// (dist, pos[3], normal[3], geom1, geom2) | ncon_dropped, padded to 16 floats.  Filled by these kernels only (rsr_step leaves it).
+struct PhysLayout { int qacc, aforce, xquat, ncon, con, ncon_drop, stride; };
+__host__ __device__ inline PhysLayout phys_layout(int nv, int nu, int nbody, int ncon_max) {
+  PhysLayout p;
+  p.qacc = 0; p.aforce = nv; p.xquat = nv + nu; p.ncon = p.xquat + 4 * nbody; p.con = p.ncon + 1; p.ncon_drop = p.con + 9 * ncon_max;
+  p.stride = (p.ncon_drop + 1 + 15) & ~15;
+  return p;
+}
+struct PhysArgs {
+  const float* ctrl;    // [N][nu] or null (keep the record's ctrl)
+  float* out;           // side buffer [N][PhysLayout::stride] or null
+  const int* ids;       // [grid] the envs to run (rsr_physics_forward_envs), or null: env = workgroup index
+  int nsteps;           // substeps (the step kernel)
+  float* sd;            // sensordata [N][RSR_MAX_SENSORDATA], written when sens.nsd > 0
+  SensArgs sens;
+};
+// rsr_physics_rollout: ctrl [N][T][nu]; trajectory rows [N][T][w], each pointer null = not recorded
+struct RollArgs {
+  const float* ctrl;
+  int T;
+  float *qpos, *qvel, *time, *aforce, *ncon, *sd;
+};
+
+}  // namespace rsr

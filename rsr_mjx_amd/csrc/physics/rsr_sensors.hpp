@@ -1,17 +1,11 @@
 // rsr_sensors.hpp -- the sensor stage of the physics kernels (rsr_physics_set_sensors, include/rsr_physics.h): data.sensordata of
-// a table of site sensors, from what the last forward pass left in LDS.  Included by rsr_physics.hip after rsr_mjx.hip, whose Go2
-// sensor code (go2_sensors / go2_accelerometer) this reuses, expression for expression, so that the IMU sensors equal the
-// env's privileged_state bit for bit.
+// a table of site sensors, from what the last forward pass left in LDS.  It reuses the Go2 sensor code of rsr_go2_sensors.hpp
+// (go2_sensors / go2_accelerometer), expression for expression, so that the IMU sensors equal the env's privileged_state bit for bit.
 #pragma once
+#include "../rsr_go2_sensors.hpp"
+#include "rsr_physics.hpp"
 
 namespace rsr {
-
-// One entry per output element (host-expanded from the table): type, site, ref site or -1, component.  nsd = 0: no stage.
-// acc_site: the one site of the table's accelerometers (-1: none); only compiled in for Dims::XFRC.
-struct SensArgs {
-  const int4* el;
-  int nsd, acc_site;
-};
 
 __device__ __forceinline__ V3 site_rt(const float* R, V3 x) {      // R^T x, in go2_sensors' expression order
   return v3(R[0] * x.x + R[3] * x.y + R[6] * x.z, R[1] * x.x + R[4] * x.y + R[7] * x.z, R[2] * x.x + R[5] * x.y + R[8] * x.z);

@@ -1,0 +1,43 @@
+// rsr_launch.hpp -- the launch entry of each family unit.  The library is three units of kernels, one per model family, each with
+// its own flags (rsr_mjx_amd/build.py): rsr_cube.hip (Airbot cube / sf), rsr_tshape.hip (Airbot T-shape), rsr_go2.hip (Go2 joystick,
+// flat or on a height field, and handstand / footstand).  Each exports one function that launches its kernels; the host picks the
+// unit from the env kind in one place (family_of in rsr_host.hpp).
+#pragma once
+#include "rsr_env.hpp"
+#include "physics/rsr_physics.hpp"
+
+namespace rsr {
+
+enum Op {
+  OP_RESET,              // rsr_reset: grid = envs
+  OP_STEP,               // rsr_step: the Airbot units' persistent work-queue grid (sc), the Go2 unit's grid = envs
+  OP_STEP_OCCUPANCY,     // returns the resident workgroups per CU of the step kernel (0: unknown); launches nothing
+  OP_PHYS_FORWARD,       // rsr_physics_forward[_envs]: grid = envs or listed envs (p.ids)
+  OP_PHYS_STEP,          // rsr_physics_step
+  OP_PHYS_ROLLOUT,       // rsr_physics_rollout (r)
+};
+
+struct Launch {
+  int grid;
+  hipStream_t stream;
+  const DModel* dm;     // device model view
+  Layout L;
+  StepArgs a;
+  Sched sc;             // OP_STEP of the Airbot units
+  PhysArgs p;           // OP_PHYS_*
+  RollArgs r;           // OP_PHYS_ROLLOUT
+  int env_kind;         // the Go2 unit's pick: handstand / footstand, or the joystick with (hfield) or without the height field
+  bool hfield;
+};
+
+int launch_cube(int op, const Launch& x);
+int launch_tshape(int op, const Launch& x);
+int launch_go2(int op, const Launch& x);
+
+template <class K>
+int step_occupancy(K kernel, size_t lds) {
+  int per_cu = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, lds) == hipSuccess ? per_cu : 0;
+}
+
+}  // namespace rsr

@@ -1,0 +1,17 @@
+// rsr_tshape.hip -- unit of the Airbot T-shape kernels: env reset and step, physics forward, step and rollout.
+#include "rsr_airbot.hpp"
+#include "physics/rsr_physics_kernels.hpp"
+
+namespace rsr {
+
+int launch_tshape(int op, const Launch& x) {
+  using C = TShapeDims;
+  switch (op) {
+    case OP_RESET: hipLaunchKernelGGL((reset_kernel<C, ENV_TSHAPE>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a); return 0;
+    case OP_STEP: hipLaunchKernelGGL((step_kernel<C, ENV_TSHAPE>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.sc); return 0;
+    case OP_STEP_OCCUPANCY: return step_occupancy(step_kernel<C, ENV_TSHAPE>, sizeof(Smem<C>));
+    default: return launch_physics<C, RSR_WAVES_PER_EU>(op, x);
+  }
+}
+
+}  // namespace rsr

@@ -33,7 +33,7 @@ class Go2Data:
         self.site_xpos = v["site_xpos"].unflatten(1, (dims.nsite, 3))
 
 
-# slices of the 144-float info block (rsr_mjx.hip enum G2_*; joystick.py:175-196)
+# slices of the 144-float info block (csrc/rsr_env.hpp enum G2_*; joystick.py:175-196)
 _INFO = dict(command=(0, 3), steps_until_next_cmd=(3, 4), last_act=(4, 16), last_last_act=(16, 28), feet_air_time=(28, 32),
              feet_contact_time=(32, 36), last_contact=(36, 40), swing_peak=(40, 44), action_buffer=(44, 92),
              gyro_buffer=(92, 104), linvel_buffer=(104, 116), gravity_buffer=(116, 128), steps_until_next_pert=(128, 129),

@@ -1,5 +1,6 @@
 """VGPR liveness of a step kernel from its ISA: which registers are live where, and what stays live across the whole kernel.
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -gline-tables-only --cuda-device-only -S rsr_mjx_amd/csrc/physics/rsr_physics.hip -o dev.s [-DRSR_WAVES_PER_EU=3]
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -gline-tables-only --cuda-device-only -S rsr_mjx_amd/csrc/rsr_cube.hip -o dev.s [-DRSR_WAVES_PER_EU=3]
+    (T-shape: rsr_tshape.hip with -fno-slp-vectorize, as rsr_mjx_amd/build.py builds it)
     python tools/isa_liveness.py dev.s [Li22 = cube | Li15 = T-shape]
 Backward data flow over the kernel's basic blocks on the final instruction stream (defs / uses of v registers parsed from the text;
 read-modify-write forms: v_fmac, v_writelane, partial-row DPP).  Prints the maximum, the source lines at the maximum, the live
