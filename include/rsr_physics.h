@@ -7,11 +7,14 @@
  *   rsr_physics_step    <- mjx_env.step(model, data, ctrl, n_substeps): writes ctrl into the record, then nsteps x mjx.step.
  *   rsr_physics_rollout <- mujoco.rollout.rollout / lax.scan(mjx.step): T control steps in one launch, trajectories [N, T, w].
  *   rsr_physics_set_sensors: the site sensors of data.sensordata (RSR_P_SENSORDATA, and a rollout's sensordata rows).
+ *   rsr_physics_set_applied / rsr_physics_applied_view: data.xfrc_applied and data.qfrc_applied, per-env inputs of every forward
+ *                          pass of these calls (zero until set).
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
  * forward leaves qpos, qvel, ctrl and time as they are); obs, reward, done, metrics, info_*, first_* and stats are left alone, and
- * no PRNG key advances.  data.xfrc_applied is zero.  As in MJX's Data (and in the record after rsr_step), xpos / site_xpos and the
+ * no PRNG key advances.  rsr_step ignores the applied forces of a physics handle (the Go2 joystick's kick is env logic with a path
+ * of its own).  As in MJX's Data (and in the record after rsr_step), xpos / site_xpos and the
  * xquat / contacts of rsr_physics_view are those of the last forward pass, taken before the final integration.  One wavefront per
  * env, a plain launch: the scheduling knobs of rsr_step do not apply.  A following rsr_step continues from the state these leave.
  * Conventions as in rsr_mjx.h (0 on success, rsr_last_error; asynchronous on hip_stream, NULL = default stream).
@@ -105,6 +108,22 @@ typedef struct rsr_rollout_out {
  * with ctrl[:, t, :] would.  out may be NULL (nothing recorded).  RSR_ERR_ARG: null handle or ctrl, T < 1, nsteps < 1,
  * sensordata requested with no sensor table set. */
 int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int nsteps, const rsr_rollout_out* out, void* hip_stream);
+
+/* Applied forces (MuJoCo's data.xfrc_applied / data.qfrc_applied): per-env state of the handle, added in every forward pass of
+ * rsr_physics_step (each substep), _forward, _forward_envs and _rollout (each substep, held for all T control steps):
+ *   qfrc_smooth += qfrc_applied + sum over bodies b >= 1 of J_b(xipos_b)^T [f_b; tau_b]   (mj_xfrcAccumulate)
+ * so they reach qacc, the constraint solve, the integration and the sensors.  Row 0 (the world body) is ignored.
+ * on = 1: the calls above launch the applied-force kernels; on first use the buffers are allocated and zeroed, and turning them on
+ * again keeps their values.  on = 0: the buffers are zeroed and the calls run the plain kernels again.  Waits for the device
+ * (launches in flight read the buffers).  RSR_ERR_ARG: null handle, on outside {0, 1}.  rsr_physics_destroy frees the buffers. */
+int rsr_physics_set_applied(rsr_physics* p, int on);
+
+/* Writable zero-copy views (as rsr_physics_view) of the applied forces, device float32, row stride = width:
+ *   RSR_A_XFRC_APPLIED  [nbody*6]  per body: force[3], torque[3], world frame, acting at the body's centre of mass
+ *   RSR_A_QFRC_APPLIED  [nv]       generalised force
+ * RSR_ERR_ARG while applied forces are off, or for an unknown id. */
+enum rsr_applied_field { RSR_A_XFRC_APPLIED = 0, RSR_A_QFRC_APPLIED, RSR_A_COUNT };
+int rsr_physics_applied_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
 
 #ifdef __cplusplus
 }

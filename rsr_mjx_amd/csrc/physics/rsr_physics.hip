@@ -1,11 +1,12 @@
 // rsr_physics.hip -- the C ABI of the physics layer (include/rsr_physics.h): rsr_physics_step / rsr_physics_forward /
-// rsr_physics_rollout / rsr_physics_view and the sensor table of rsr_sensors.hpp.  The kernels are in the family units
+// rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp and the applied forces (rsr_physics_set_applied).  The kernels are in the family units
 // (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../rsr_host.hpp"
+#include "rsr_applied.hpp"
 
 // The side buffer belongs to a handle of its own, on a batch it borrows.
 struct rsr_physics {
@@ -15,6 +16,9 @@ struct rsr_physics {
   float* sd;            // sensordata [n][RSR_MAX_SENSORDATA]
   int4* sens_el;        // [RSR_MAX_SENSORDATA] the sensor table, one entry per output element (rsr::SensArgs)
   int nsd = 0, acc_site = -1;
+  float* xfrc = nullptr;  // data.xfrc_applied [n][nbody*6], allocated on the first rsr_physics_set_applied(p, 1)
+  float* qfrc = nullptr;  // data.qfrc_applied [n][nv]
+  bool applied = false;   // launches take the applied kernels
 };
 
 extern "C" int rsr_physics_create(rsr_batch* b, rsr_physics** out) {
@@ -47,6 +51,8 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
   if (p->out) (void)hipFree(p->out);
   if (p->sd) (void)hipFree(p->sd);
   if (p->sens_el) (void)hipFree(p->sens_el);
+  if (p->xfrc) (void)hipFree(p->xfrc);
+  if (p->qfrc) (void)hipFree(p->qfrc);
   delete p;
 }
 
@@ -54,12 +60,14 @@ static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, in
                           const rsr::RollArgs& r = rsr::RollArgs{}) {
   rsr_batch* b = ph->b;
   HIPCHK(hipSetDevice(b->device));
-  rsr::Launch x = launch_args(b, hip_stream);
+  rsr::AppliedLaunch x;                          // (read as one only when op carries OP_APPLIED)
+  static_cast<rsr::Launch&>(x) = launch_args(b, hip_stream);
   x.grid = grid;
   x.a.debug = nullptr;
   x.p = rsr::PhysArgs{ctrl, ph->out, ids, nsteps, ph->sd, rsr::SensArgs{ph->sens_el, ph->nsd, ph->acc_site}};
   x.r = r;
-  launch(b, op, x);
+  x.ap = rsr::Applied{ph->xfrc, ph->qfrc};
+  launch(b, ph->applied ? op | rsr::OP_APPLIED : op, x);
   { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
   return RSR_OK;
 }
@@ -156,4 +164,40 @@ extern "C" int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int
   const int rc = physics_launch(p, nullptr, nullptr, p->b->n, nsteps, rsr::OP_PHYS_ROLLOUT, hip_stream, "rsr_physics_rollout", r);
   if (rc == RSR_OK && p->b->timing) p->b->launches++;
   return rc;
+}
+
+extern "C" int rsr_physics_set_applied(rsr_physics* p, int on) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_set_applied: null handle");
+  if (on != 0 && on != 1) return fail(RSR_ERR_ARG, "rsr_physics_set_applied: on must be 0 or 1");
+  if (on == (int)p->applied) return RSR_OK;                 // (on again: the values stay)
+  const rsr_dims& d = p->b->model->dims;
+  const size_t xb = (size_t)p->b->n * d.nbody * 6 * sizeof(float), qb = (size_t)p->b->n * d.nv * sizeof(float);
+  HIPCHK(hipSetDevice(p->b->device));
+  HIPCHK(hipDeviceSynchronize());               // launches in flight read the buffers (and were launched with the old choice)
+  if (on && !p->xfrc) {
+    if (hipMalloc(&p->xfrc, xb) != hipSuccess) { p->xfrc = nullptr; return fail(RSR_ERR_NOMEM, "rsr_physics_set_applied: hipMalloc(xfrc)"); }
+    if (hipMalloc(&p->qfrc, qb) != hipSuccess) {
+      (void)hipFree(p->xfrc); p->xfrc = p->qfrc = nullptr; return fail(RSR_ERR_NOMEM, "rsr_physics_set_applied: hipMalloc(qfrc)");
+    }
+  }
+  HIPCHK(hipMemset(p->xfrc, 0, xb));            // first use: zeroed; off: back to zero for the next time on
+  HIPCHK(hipMemset(p->qfrc, 0, qb));
+  HIPCHK(hipDeviceSynchronize());
+  p->applied = on != 0;
+  return RSR_OK;
+}
+
+extern "C" int rsr_physics_applied_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
+  if (!p || !dev_ptr || !shape || !stride) return fail(RSR_ERR_ARG, "rsr_physics_applied_view: null argument");
+  if (!p->applied) return fail(RSR_ERR_ARG, "rsr_physics_applied_view: applied forces are off (rsr_physics_set_applied)");
+  const rsr_dims& d = p->b->model->dims;
+  int w = 0;
+  switch (field) {
+    case RSR_A_XFRC_APPLIED: *dev_ptr = p->xfrc; w = 6 * d.nbody; break;
+    case RSR_A_QFRC_APPLIED: *dev_ptr = p->qfrc; w = d.nv; break;
+    default: return fail(RSR_ERR_ARG, "rsr_physics_applied_view: unknown field id");
+  }
+  shape[0] = p->b->n; shape[1] = w;
+  stride[0] = w; stride[1] = 1;
+  return RSR_OK;
 }

@@ -4,12 +4,15 @@
     mjx_env.step(model, data, ctrl, n_substeps) ->  Physics.step(ctrl, nsteps)           (nsteps x mjx.step)
     mujoco.rollout.rollout / lax.scan(mjx.step)  ->  Physics.rollout(ctrl [N, T, nu])     (one launch, trajectories [N, T, w])
     mjx_env.get_sensor_data(model, data, name)  ->  Physics.sensor(name)                 (site sensors, Physics.set_sensors)
+    data.replace(xfrc_applied=..., qfrc_applied=...) ->  Physics.set_applied(xfrc, qfrc)  (held by every later step / forward /
+                                                                                           rollout, like a Data field)
 
 `Physics(env)` shares the batch of a BatchedEnv (Airbot cube / sf / T-shape, Go2 joystick, handstand / footstand): the same model,
 the same per-env domain randomisation, the same record and the same stream.  The pipeline fields it exposes are the record's own
 views, so a following `env.step` continues from whatever state these calls leave (rsr_physics_step / rsr_physics_forward,
 include/rsr_physics.h).  As in MJX's Data, the position-dependent outputs (xpos, xquat, site_xpos, contacts) after a step are those
-of the last forward pass, before the final integration.
+of the last forward pass, before the final integration.  The applied forces are per-env state of the Physics handle: env.step
+ignores them (the Go2 joystick's kick keeps its own path inside the env kernel).
 """
 from __future__ import annotations
 
@@ -68,6 +71,9 @@ class Physics:
         self.xquat = side["xquat"].unflatten(1, (d.nbody, 4))
         self._sensor_adr: Dict[str, tuple] = {}
         self.sensordata = side["sensordata"]
+        # data.xfrc_applied [N, nbody, 6] / data.qfrc_applied [N, nv]: writable views while applied forces are on, else None
+        self.xfrc_applied = None
+        self.qfrc_applied = None
         if sensors is not None:
             self.set_sensors(sensors)
 
@@ -125,6 +131,58 @@ class Physics:
         adr, w = self._sensor_adr[name]
         data = self.sensordata if data is None else data
         return data[..., adr:adr + w]
+
+    def _ids(self, env_ids, who: str):
+        """env_ids as an int64 tensor on the device (None: every env), checked: in range, no repeats."""
+        import torch
+        if env_ids is None:
+            return torch.arange(self.num_envs, device=self.device, dtype=torch.int64)
+        ids = torch.as_tensor(env_ids, device=self.device).to(torch.int64).reshape(-1)
+        if ids.numel() and bool(((ids < 0) | (ids >= self.num_envs)).any()):
+            raise ValueError(f"{who}: env_ids must lie in [0, {self.num_envs})")
+        if torch.unique(ids).numel() != ids.numel():
+            raise ValueError(f"{who}: env_ids must not repeat")
+        return ids
+
+    def set_applied(self, xfrc=None, qfrc=None, env_ids=None) -> None:
+        """data.replace(xfrc_applied=..., qfrc_applied=...): turns applied forces on (zero everywhere the first time) and writes
+        the given rows of the envs `env_ids` (default: all; rows in env_ids order).  xfrc: [k, nbody, 6], per body force[3] and
+        torque[3] in the world frame, acting at the body's centre of mass (row 0, the world, is ignored); qfrc: [k, nv].  None
+        leaves a field as it is.  The values persist: every later step (each substep), forward, set_state of other envs and
+        rollout (all T control steps) applies them."""
+        import torch
+        ids = self._ids(env_ids, "set_applied")
+        k, d = ids.numel(), self.dims
+        vals = {}
+        for name, x, shape in (("xfrc", xfrc, (k, d.nbody, 6)), ("qfrc", qfrc, (k, d.nv))):
+            if x is None:
+                continue
+            t = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"set_applied expects {name} of shape {shape}, got {tuple(t.shape)}")
+            vals[name] = t
+        if self.xfrc_applied is None:
+            _lib.check(_lib.lib().rsr_physics_set_applied(self._h, 1))
+            views = []
+            for fid in range(len(_lib.APPLIED_FIELDS)):
+                ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
+                _lib.check(_lib.lib().rsr_physics_applied_view(self._h, fid, C.byref(ptr), shape, stride))
+                views.append(_view(ptr, shape, stride, self.device))
+            self.xfrc_applied = views[0].unflatten(1, (d.nbody, 6))
+            self.qfrc_applied = views[1]
+        if k == 0:
+            return
+        if "xfrc" in vals:
+            self.xfrc_applied[ids] = vals["xfrc"]
+        if "qfrc" in vals:
+            self.qfrc_applied[ids] = vals["qfrc"]
+
+    def clear_applied(self) -> None:
+        """Turns applied forces off: every later call runs without them (xfrc_applied / qfrc_applied become None)."""
+        if self.xfrc_applied is None:
+            return
+        self.xfrc_applied = self.qfrc_applied = None
+        _lib.check(_lib.lib().rsr_physics_set_applied(self._h, 0))
 
     def rollout(self, ctrl, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), qpos0=None, qvel0=None,
                 ctrl0=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
@@ -190,19 +248,12 @@ class Physics:
 
     def set_state(self, qpos=None, qvel=None, ctrl=None, env_ids=None) -> None:
         """mjx_env.init: writes the given fields of the envs `env_ids` (default: all; rows in env_ids order), zeroes their
-        qacc_warmstart and runs mjx.forward on those envs only.  The other envs' record and physics outputs are not touched."""
+        qacc_warmstart (and their applied forces, when on) and runs mjx.forward on those envs only.  The other envs' record and physics outputs are not touched."""
         import torch
-        if env_ids is None:
-            ids = torch.arange(self.num_envs, device=self.device, dtype=torch.int64)
-        else:
-            ids = torch.as_tensor(env_ids, device=self.device).to(torch.int64).reshape(-1)
-            if ids.numel() == 0:
-                return
-            if bool(((ids < 0) | (ids >= self.num_envs)).any()):
-                raise ValueError(f"set_state: env_ids must lie in [0, {self.num_envs})")
-            if torch.unique(ids).numel() != ids.numel():
-                raise ValueError("set_state: env_ids must not repeat")
+        ids = self._ids(env_ids, "set_state")
         k = ids.numel()
+        if k == 0:
+            return
         vals = {}
         for name, x, width in (("qpos", qpos, self.dims.nq), ("qvel", qvel, self.dims.nv), ("ctrl", ctrl, self.dims.nu)):
             if x is None:
@@ -215,6 +266,9 @@ class Physics:
         for name, t in vals.items():
             rec[name][ids] = t
         self.qacc_warmstart[ids] = 0.0
+        if self.xfrc_applied is not None:           # a fresh Data (mjx_env.init) has no applied forces
+            self.xfrc_applied[ids] = 0.0
+            self.qfrc_applied[ids] = 0.0
         if env_ids is None:
             self.forward()
         else:

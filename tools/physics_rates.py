@@ -1,6 +1,8 @@
 """Physics-only env-steps/s per model family (rsr_physics_step with nsteps = n_frames) beside the fused env step (rsr_step), both
 timed with HIP events on the launch stream (rsr_timing_begin / rsr_timing_end).  One JSON line per family; --out also writes them
-to a file.  Usage: python tools/physics_rates.py [--envs 8192] [--steps 50] [--warmup 10] [--out FILE]"""
+to a file.  --applied adds the rates with applied forces on (Physics.set_applied: a non-zero xfrc on every body and a qfrc on every
+dof), for the step and for a rollout of --rollout-T control steps, beside the plain ones.
+Usage: python tools/physics_rates.py [--envs 8192] [--steps 50] [--warmup 10] [--applied] [--rollout-T 16] [--out FILE]"""
 from __future__ import annotations
 
 import argparse
@@ -19,6 +21,8 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--families", default="cube,tshape,go2flat,go2rough,footstand")
+    ap.add_argument("--applied", action="store_true")
+    ap.add_argument("--rollout-T", type=int, default=16)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -59,10 +63,33 @@ def main() -> None:
             phys.step(ctrl)
         ms_phys, launches = env.timing_end()
         ms_phys /= launches
-        finite = bool(torch.isfinite(env.view("qpos")).all())
         row = dict(family=kind, num_envs=n, n_frames=int(env.dims.n_frames), env_step_ms=ms_env, physics_step_ms=ms_phys,
                    env_steps_per_s=n / (ms_env * 1e-3), physics_env_steps_per_s=n / (ms_phys * 1e-3),
-                   physics_over_env=ms_phys / ms_env, finite=finite)
+                   physics_over_env=ms_phys / ms_env)
+        if args.applied:
+            def timed(fn, per):
+                for _ in range(args.warmup):
+                    fn()
+                env.timing_begin()
+                for _ in range(args.steps):
+                    fn()
+                ms, launches = env.timing_end()
+                return ms / launches / per
+            T = args.rollout_T
+            cr = ctrl[:, None, :].expand(n, T, env.dims.nu).contiguous()
+            row["rollout_step_ms"] = timed(lambda: phys.rollout(cr, fields=("qpos", "qvel")), T)
+            # small forces (2 % of each body's weight, a matching torque, 0.05 on every dof): the state stays near the plain one
+            mass = torch.as_tensor(envdef.sys.arrays["body_mass"], dtype=torch.float32, device=env.device)
+            g = torch.Generator(device="cpu").manual_seed(0)
+            x = torch.randn((n, env.dims.nbody, 6), generator=g).to(env.device) * 0.02 * 9.81 * mass[None, :, None].clamp(min=0.05)
+            q = torch.randn((n, env.dims.nv), generator=g).to(env.device) * 0.05
+            phys.set_applied(x, q)
+            row["applied_step_ms"] = timed(lambda: phys.step(ctrl), 1)
+            row["applied_rollout_step_ms"] = timed(lambda: phys.rollout(cr, fields=("qpos", "qvel")), T)
+            row["applied_over_plain_step"] = row["applied_step_ms"] / ms_phys
+            row["applied_over_plain_rollout"] = row["applied_rollout_step_ms"] / row["rollout_step_ms"]
+            row["rollout_T"] = T
+        row["finite"] = bool(torch.isfinite(env.view("qpos")).all())
         print(json.dumps(row), flush=True)
         rows.append(row)
         del phys, env
