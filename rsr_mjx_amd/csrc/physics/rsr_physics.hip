@@ -6,15 +6,14 @@
 #include <cstdint>
 
 #include "../rsr_host.hpp"
-#include "rsr_applied.hpp"
 
 // The side buffer belongs to a handle of its own, on a batch it borrows.
 struct rsr_physics {
   rsr_batch* b;         // borrowed
-  float* out;           // [n][PhysLayout::stride]
+  float* out = nullptr;  // [n][PhysLayout::stride]
   rsr::PhysLayout PL;
-  float* sd;            // sensordata [n][RSR_MAX_SENSORDATA]
-  int4* sens_el;        // [RSR_MAX_SENSORDATA] the sensor table, one entry per output element (rsr::SensArgs)
+  float* sd = nullptr;   // sensordata [n][RSR_MAX_SENSORDATA]
+  int4* sens_el = nullptr;  // [RSR_MAX_SENSORDATA] the sensor table, one entry per output element (rsr::SensArgs)
   int nsd = 0, acc_site = -1;
   float* xfrc = nullptr;  // data.xfrc_applied [n][nbody*6], allocated on the first rsr_physics_set_applied(p, 1)
   float* qfrc = nullptr;  // data.qfrc_applied [n][nv]
@@ -31,16 +30,14 @@ extern "C" int rsr_physics_create(rsr_batch* b, rsr_physics** out) {
   p->b = b;
   p->PL = rsr::phys_layout(d.nv, d.nu, d.nbody, d.ncon_max);
   const size_t bytes = (size_t)b->n * p->PL.stride * sizeof(float);
-  if (hipMalloc(&p->out, bytes) != hipSuccess) { delete p; return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(side buffer)"); }
-  if (hipMemset(p->out, 0, bytes) != hipSuccess) { (void)hipFree(p->out); delete p; return fail(RSR_ERR_HIP, "rsr_physics_create: hipMemset"); }
+  if (hipMalloc(&p->out, bytes) != hipSuccess) { p->out = nullptr; rsr_physics_destroy(p); return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(side buffer)"); }
+  if (hipMemset(p->out, 0, bytes) != hipSuccess) { rsr_physics_destroy(p); return fail(RSR_ERR_HIP, "rsr_physics_create: hipMemset"); }
   const size_t sd_bytes = (size_t)b->n * RSR_MAX_SENSORDATA * sizeof(float);
-  if (hipMalloc(&p->sd, sd_bytes) != hipSuccess) { (void)hipFree(p->out); delete p; return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(sensordata)"); }
+  if (hipMalloc(&p->sd, sd_bytes) != hipSuccess) { p->sd = nullptr; rsr_physics_destroy(p); return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(sensordata)"); }
   if (hipMalloc(&p->sens_el, RSR_MAX_SENSORDATA * sizeof(int4)) != hipSuccess) {
-    (void)hipFree(p->sd); (void)hipFree(p->out); delete p; return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(sensor table)");
+    p->sens_el = nullptr; rsr_physics_destroy(p); return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(sensor table)");
   }
-  if (hipMemset(p->sd, 0, sd_bytes) != hipSuccess) {
-    (void)hipFree(p->sens_el); (void)hipFree(p->sd); (void)hipFree(p->out); delete p; return fail(RSR_ERR_HIP, "rsr_physics_create: hipMemset");
-  }
+  if (hipMemset(p->sd, 0, sd_bytes) != hipSuccess) { rsr_physics_destroy(p); return fail(RSR_ERR_HIP, "rsr_physics_create: hipMemset"); }
   *out = p;
   return RSR_OK;
 }
@@ -60,14 +57,13 @@ static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, in
                           const rsr::RollArgs& r = rsr::RollArgs{}) {
   rsr_batch* b = ph->b;
   HIPCHK(hipSetDevice(b->device));
-  rsr::AppliedLaunch x;                          // (read as one only when op carries OP_APPLIED)
-  static_cast<rsr::Launch&>(x) = launch_args(b, hip_stream);
+  rsr::Launch x = launch_args(b, hip_stream);
   x.grid = grid;
   x.a.debug = nullptr;
   x.p = rsr::PhysArgs{ctrl, ph->out, ids, nsteps, ph->sd, rsr::SensArgs{ph->sens_el, ph->nsd, ph->acc_site}};
   x.r = r;
-  x.ap = rsr::Applied{ph->xfrc, ph->qfrc};
-  launch(b, ph->applied ? op | rsr::OP_APPLIED : op, x);
+  if (ph->applied) x.ap = rsr::Applied{ph->xfrc, ph->qfrc};
+  launch(b, op, x);
   { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
   return RSR_OK;
 }

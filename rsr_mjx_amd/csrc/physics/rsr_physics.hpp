@@ -29,6 +29,12 @@ struct PhysArgs {
   float* sd;            // sensordata [N][RSR_MAX_SENSORDATA], written when sens.nsd > 0
   SensArgs sens;
 };
+// data.xfrc_applied [nbody*6] (force, torque: world frame, at the body's COM) and data.qfrc_applied [nv] (rsr_physics_set_applied):
+// the handle's buffers [N][...], xfrc null = off (Launch::ap), or one env's rows (AppliedStage, rsr_applied.hpp)
+struct Applied {
+  const float* xfrc;
+  const float* qfrc;
+};
 // rsr_physics_rollout: ctrl [N][T][nu]; trajectory rows [N][T][w], each pointer null = not recorded
 struct RollArgs {
   const float* ctrl;

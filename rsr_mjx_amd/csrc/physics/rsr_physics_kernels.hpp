@@ -1,5 +1,7 @@
 // rsr_physics_kernels.hpp -- the physics-level kernels (include/rsr_physics.h): each family unit instantiates them for its Dims,
-// with its flags and next to its env kernels, and launches them through launch_physics.
+// with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
+// forward) and rollout_kernel, instantiated plain and with applied forces: the applied kernels take the handle's Applied buffers as
+// one more argument and pass forward<C> their env's rows as its force stage (rsr_applied.hpp).
 #pragma once
 #include "../rsr_launch.hpp"
 #include "rsr_sensors.hpp"
@@ -36,11 +38,20 @@ __device__ __forceinline__ void store_side(const DModel& m, const Smem<C>& s, fl
   if (lane == 0) { o[PL.ncon] = (float)nc; o[PL.ncon_drop] = (float)s.ncon_drop; }
 }
 
+// forward<C>'s force stage of env e: none, or its rows of the applied forces (the handle's buffers xfrc / qfrc: rsr_applied.hpp)
+template <class C>
+__device__ __forceinline__ NoForceStage force_stage(int) { return {}; }
+template <class C>
+__device__ __forceinline__ AppliedStage<C> force_stage(int e, const float* xfrc, const float* qfrc) {
+  return {{xfrc + (size_t)e * (C::NB * 6), qfrc + (size_t)e * C::NV}};
+}
+
 // STEP: nsteps x (forward, integrate); otherwise one forward.  Position-dependent outputs (xpos, xquat, site_xpos, contacts) are
 // those of the last forward pass, i.e. before the final integration (MJX Data semantics, as in the record after rsr_step).
-template <class C, bool STEP, int WAVES>
+// Ap: none (the plain kernel), or Applied: the applied forces ([N][nbody*6] / [N][nv]) enter every forward pass.
+template <class C, bool STEP, int WAVES, class... Ap>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
-void physics_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs p) {
+void physics_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs p, Ap... ap) {
   const DModel& m = *mp;
   const Hot hot = make_hot(m);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -48,14 +59,18 @@ void physics_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
   const int e = p.ids ? p.ids[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
   if (e < 0 || e >= a.n) return;                                // (an id out of range runs nothing)
   float* rec = a.state + (size_t)e * L.rec;
+  const auto stage = force_stage<C>(e, ap.xfrc..., ap.qfrc...);
   PROF_DECL
+  // the record load is written out here and in rollout_kernel: through load_pipeline or a helper of its own it compiles to
+  // other code
   for (int t = lane; t < C::NQ; t += 64) s.qpos[t] = rec[L.qpos + t];
   float warm = 0.0f;
   if (lane < C::NV) { s.qvel[lane] = rec[L.qvel + lane]; warm = rec[L.warm + lane]; }
   float time = rec[L.time];
   load_overrides<C>(m, s, a, e, lane);
   if (lane < C::NU) s.ctrl[lane] = p.ctrl ? p.ctrl[(size_t)e * C::NU + lane] : rec[L.ctrl + lane];
-  if constexpr (C::XFRC) {        // data.xfrc_applied = 0 (the Go2 joystick's kick is env logic); the accelerometer's body as in the env kernels
+  if constexpr (C::XFRC) {        // the Go2 single-body kick path idle (the joystick's kick is env logic; applied forces are the
+                                  // force stage); the accelerometer's body as in the env kernels
     if (lane == 0) { s.acc_body = m.site_bodyid[m.env_ids[0]]; s.xfrc_body = 0; s.xfrc[0] = s.xfrc[1] = s.xfrc[2] = 0.0f; }
   }
   WSYNC();
@@ -64,7 +79,7 @@ void physics_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
   const int nsteps = STEP ? p.nsteps : 1;
   for (int fr = 0; fr < nsteps; ++fr) {
     const int lane_s = lrec_lane(lane);        // see step_kernel
-    forward<C>(m, hot, s, lane_s, Mrow, warm, f, nullptr PROF_PASS);
+    forward<C>(m, hot, s, lane_s, Mrow, warm, f, nullptr PROF_PASS, stage);
     if constexpr (STEP) {
       integrate<C>(m, hot, s, lane_s, Mrow, f PROF_PASS);
       time += hot.timestep;
@@ -88,10 +103,10 @@ void physics_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
 // register from one control step to the next (in physics_kernel both make a round trip through the record, which is exact), so
 // the trajectory is bit-identical to T step launches.  After control step t the wave writes its rows t of the requested
 // trajectories: per env the rows are contiguous in time ([N][T][w]).  The record, the side buffer and the sensordata row are
-// written once, at the end, as physics_kernel<C, true> writes them.
-template <class C, int WAVES>
+// written once, at the end, as physics_kernel<C, true> writes them.  Applied forces (Ap) are held for all T control steps.
+template <class C, int WAVES, class... Ap>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
-void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs p, RollArgs r) {
+void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs p, RollArgs r, Ap... ap) {
   const DModel& m = *mp;
   const Hot hot = make_hot(m);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -99,6 +114,7 @@ void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
   const int e = (int)blockIdx.x, lane = threadIdx.x;
   if (e >= a.n) return;
   float* rec = a.state + (size_t)e * L.rec;
+  const auto stage = force_stage<C>(e, ap.xfrc..., ap.qfrc...);
   PROF_DECL
   for (int t = lane; t < C::NQ; t += 64) s.qpos[t] = rec[L.qpos + t];
   float warm = 0.0f;
@@ -119,115 +135,7 @@ void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
   int t = 0, fr = 0;
   for (int k = 0; k < total; ++k) {
     const int lane_s = lrec_lane(lane);        // see step_kernel
-    forward<C>(m, hot, s, lane_s, Mrow, warm, f, nullptr PROF_PASS);
-    integrate<C>(m, hot, s, lane_s, Mrow, f PROF_PASS);
-    time += hot.timestep;
-    if (++fr < p.nsteps) continue;
-    fr = 0;
-    WSYNC();
-    const size_t row = (size_t)e * r.T + t;
-    float sv = 0.0f;
-    if (nsd > 0) {
-      sv = sensor_stage<C>(m, s, lane, f.qacc, p.sens);
-      if (t == r.T - 1 && lane < nsd) p.sd[(size_t)e * RSR_MAX_SENSORDATA + lane] = sv;      // the view: the last control step's
-    }
-    if (r.qpos) for (int q = lane; q < C::NQ; q += 64) r.qpos[row * C::NQ + q] = s.qpos[q];
-    if (r.qvel && lane < C::NV) r.qvel[row * C::NV + lane] = s.qvel[lane];
-    if (r.time && lane == 0) r.time[row] = time;
-    if (r.aforce && lane < C::NU) r.aforce[row * C::NU + lane] = s.aforce[lane];
-    if (r.ncon && lane == 0) r.ncon[row] = (float)s.ncon;
-    if (r.sd && lane < nsd) r.sd[row * nsd + lane] = sv;
-    if (++t < r.T) {
-      if (lane < C::NU) s.ctrl[lane] = r.ctrl[(row + 1) * C::NU + lane];
-      WSYNC();
-    }
-  }
-  store_pipeline<C>(s, rec, L, lane, warm, time);
-  if (p.out) store_side<C>(m, s, p.out, e, lane, f.qacc);
-}
-
-// ================================================================ applied forces (rsr_physics_set_applied)
-// physics_kernel / rollout_kernel with data.xfrc_applied / qfrc_applied ([N][nbody*6] / [N][nv], global memory) added in every
-// forward pass (forward_applied, rsr_applied.hpp); a rollout holds them for all T control steps.  Copies of the plain kernels, which
-// keep their text and their code.
-template <class C, bool STEP, int WAVES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
-void physics_applied_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs p, Applied ap) {
-  const DModel& m = *mp;
-  const Hot hot = make_hot(m);
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  Smem<C>& s = *reinterpret_cast<Smem<C>*>(smem_raw);
-  const int e = p.ids ? p.ids[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-  if (e < 0 || e >= a.n) return;                                // (an id out of range runs nothing)
-  float* rec = a.state + (size_t)e * L.rec;
-  const Applied ae{ap.xfrc + (size_t)e * (C::NB * 6), ap.qfrc + (size_t)e * C::NV};     // this env's rows
-  PROF_DECL
-  for (int t = lane; t < C::NQ; t += 64) s.qpos[t] = rec[L.qpos + t];
-  float warm = 0.0f;
-  if (lane < C::NV) { s.qvel[lane] = rec[L.qvel + lane]; warm = rec[L.warm + lane]; }
-  float time = rec[L.time];
-  load_overrides<C>(m, s, a, e, lane);
-  if (lane < C::NU) s.ctrl[lane] = p.ctrl ? p.ctrl[(size_t)e * C::NU + lane] : rec[L.ctrl + lane];
-  if constexpr (C::XFRC) {        // the Go2 single-body kick path stays idle (xfrc_body = 0): the applied rows carry every force
-    if (lane == 0) { s.acc_body = m.site_bodyid[m.env_ids[0]]; s.xfrc_body = 0; s.xfrc[0] = s.xfrc[1] = s.xfrc[2] = 0.0f; }
-  }
-  WSYNC();
-  float Mrow[C::NV];
-  FwdOut<C> f;
-  const int nsteps = STEP ? p.nsteps : 1;
-  for (int fr = 0; fr < nsteps; ++fr) {
-    const int lane_s = lrec_lane(lane);        // see step_kernel
-    forward_applied<C>(m, hot, s, lane_s, Mrow, warm, f, ae PROF_PASS);
-    if constexpr (STEP) {
-      integrate<C>(m, hot, s, lane_s, Mrow, f PROF_PASS);
-      time += hot.timestep;
-    }
-  }
-  WSYNC();
-  if (p.sens.nsd > 0) {                                          // (wave-uniform; no table: the stage is skipped)
-    const float v = sensor_stage<C>(m, s, lane, f.qacc, p.sens);
-    if (lane < p.sens.nsd) p.sd[(size_t)e * RSR_MAX_SENSORDATA + lane] = v;
-  }
-  if constexpr (STEP) store_pipeline<C>(s, rec, L, lane, warm, time);
-  else {                          // mjx.forward leaves qpos as it was (kinematics normalises the quaternions in LDS only)
-    if (lane < C::NV) rec[L.warm + lane] = warm;
-    for (int t = lane; t < C::NB * 3; t += 64) rec[L.xpos + t] = s.xpos[t];
-    for (int t = lane; t < C::NS * 3; t += 64) rec[L.site_xpos + t] = s.spos[t];
-  }
-  if (p.out) store_side<C>(m, s, p.out, e, lane, f.qacc);
-}
-
-template <class C, int WAVES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
-void rollout_applied_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs p, RollArgs r, Applied ap) {
-  const DModel& m = *mp;
-  const Hot hot = make_hot(m);
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  Smem<C>& s = *reinterpret_cast<Smem<C>*>(smem_raw);
-  const int e = (int)blockIdx.x, lane = threadIdx.x;
-  if (e >= a.n) return;
-  float* rec = a.state + (size_t)e * L.rec;
-  const Applied ae{ap.xfrc + (size_t)e * (C::NB * 6), ap.qfrc + (size_t)e * C::NV};     // this env's rows
-  PROF_DECL
-  for (int t = lane; t < C::NQ; t += 64) s.qpos[t] = rec[L.qpos + t];
-  float warm = 0.0f;
-  if (lane < C::NV) { s.qvel[lane] = rec[L.qvel + lane]; warm = rec[L.warm + lane]; }
-  float time = rec[L.time];
-  load_overrides<C>(m, s, a, e, lane);
-  if constexpr (C::XFRC) {
-    if (lane == 0) { s.acc_body = m.site_bodyid[m.env_ids[0]]; s.xfrc_body = 0; s.xfrc[0] = s.xfrc[1] = s.xfrc[2] = 0.0f; }
-  }
-  float Mrow[C::NV];
-  FwdOut<C> f;
-  const int nsd = p.sens.nsd;
-  // one loop over the T * nsteps substeps, as in rollout_kernel
-  if (lane < C::NU) s.ctrl[lane] = r.ctrl[(size_t)e * r.T * C::NU + lane];
-  WSYNC();
-  const int total = r.T * p.nsteps;
-  int t = 0, fr = 0;
-  for (int k = 0; k < total; ++k) {
-    const int lane_s = lrec_lane(lane);        // see step_kernel
-    forward_applied<C>(m, hot, s, lane_s, Mrow, warm, f, ae PROF_PASS);
+    forward<C>(m, hot, s, lane_s, Mrow, warm, f, nullptr PROF_PASS, stage);
     integrate<C>(m, hot, s, lane_s, Mrow, f PROF_PASS);
     time += hot.timestep;
     if (++fr < p.nsteps) continue;
@@ -257,12 +165,10 @@ void rollout_applied_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a,
 // the physics ops of a family's launch entry (rsr_launch.hpp)
 template <class C, int WAVES>
 int launch_physics(int op, const Launch& x) {
-  if (op & OP_APPLIED) {            // (x is an AppliedLaunch: rsr_applied.hpp)
-    const Applied ap = static_cast<const AppliedLaunch&>(x).ap;
-    op &= ~OP_APPLIED;
-    if (op == OP_PHYS_STEP) hipLaunchKernelGGL((physics_applied_kernel<C, true, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, ap);
-    else if (op == OP_PHYS_FORWARD) hipLaunchKernelGGL((physics_applied_kernel<C, false, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, ap);
-    else hipLaunchKernelGGL((rollout_applied_kernel<C, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.r, ap);
+  if (x.ap.xfrc) {                  // applied forces on
+    if (op == OP_PHYS_STEP) hipLaunchKernelGGL((physics_kernel<C, true, WAVES, Applied>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.ap);
+    else if (op == OP_PHYS_FORWARD) hipLaunchKernelGGL((physics_kernel<C, false, WAVES, Applied>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.ap);
+    else hipLaunchKernelGGL((rollout_kernel<C, WAVES, Applied>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.r, x.ap);
     return 0;
   }
   if (op == OP_PHYS_STEP) hipLaunchKernelGGL((physics_kernel<C, true, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p);

@@ -26,6 +26,7 @@ struct Launch {
   Sched sc;             // OP_STEP of the Airbot units
   PhysArgs p;           // OP_PHYS_*
   RollArgs r;           // OP_PHYS_ROLLOUT
+  Applied ap;           // OP_PHYS_*: the applied forces, or ap.xfrc null: none (the plain kernels)
   int env_kind;         // the Go2 unit's pick: handstand / footstand, or the joystick with (hfield) or without the height field
   bool hfield;
 };

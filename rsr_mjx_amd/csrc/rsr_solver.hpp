@@ -647,11 +647,18 @@ __device__ __forceinline__ void solve(const Hot& m, Smem<C>& s, int lane, int ne
 template <class C>
 struct FwdOut { float qacc, qfc, fsmooth; int nefc; SolveStats st; };
 
+// forward()'s default force stage: none.  A stage maps this lane's qfrc_smooth to a new value right after smooth_forces; the
+// physics layer's applied forces are one (physics/rsr_applied.hpp).
+struct NoForceStage {
+  template <class S>
+  __device__ __forceinline__ float operator()(const Hot&, S&, int, float fs) const { return fs; }
+};
+
 // MJX forward(): position -> collision -> constraint rows -> velocity/actuation -> solve.
 // warm_i is read and replaced by the solver's qacc (qacc_warmstart <- qacc).
-template <class C>
+template <class C, class Stage = NoForceStage>
 __device__ __forceinline__ void forward(const DModel& m, const Hot& h, Smem<C>& s, int lane, float (&Mrow)[C::NV], float& warm, FwdOut<C>& out,
-                        float* dbg PROF_ARG) {
+                        float* dbg PROF_ARG, const Stage& stage = Stage{}) {
   kinematics<C>(m, h, s, lane PROF_PASS);
   PROF(PS_KIN)
   com_crb_mass<C>(m, h, s, lane PROF_PASS);
@@ -660,6 +667,7 @@ __device__ __forceinline__ void forward(const DModel& m, const Hot& h, Smem<C>& 
   // velocity stage first: its scratch and the frames die before the Jacobian claims the shared LDS region
   float qvel_i = lane < C::NV ? s.qvel[lane] : 0.0f;
   float fs = smooth_forces<C>(m, h, s, lane, qvel_i, 0.0f PROF_PASS);
+  fs = stage(h, s, lane, fs);
   PROF(PS_SMOOTH)
   // qacc_smooth = M^-1 qfrc_smooth
   float a[C::NCH], lt[C::NCH];
