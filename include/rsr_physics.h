@@ -9,6 +9,8 @@
  *   rsr_physics_set_sensors: the site sensors of data.sensordata (RSR_P_SENSORDATA, and a rollout's sensordata rows).
  *   rsr_physics_set_applied / rsr_physics_applied_view: data.xfrc_applied and data.qfrc_applied, per-env inputs of every forward
  *                          pass of these calls (zero until set).
+ *   rsr_physics_dynamics <- mj_fullM, data.qfrc_bias / qfrc_passive / qfrc_actuator and mj_jacSite at the record's current state
+ *                          (after the last integration, unlike the views of rsr_physics_view), in a buffer of its own.
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
@@ -124,6 +126,36 @@ int rsr_physics_set_applied(rsr_physics* p, int on);
  * RSR_ERR_ARG while applied forces are off, or for an unknown id. */
 enum rsr_applied_field { RSR_A_XFRC_APPLIED = 0, RSR_A_QFRC_APPLIED, RSR_A_COUNT };
 int rsr_physics_applied_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
+
+/* The model at the current state, for model-based control: one launch that evaluates the record's qpos / qvel / ctrl with the
+ * batch's per-env leaves and writes the handle's dynamics buffer.  It describes the state the record holds now, i.e. after the
+ * integration of the last rsr_physics_step, whereas the side buffer of rsr_physics_view shows that step's last forward pass.
+ * Nothing else is written: the record (qpos is not normalised; xpos, site_xpos, qacc_warmstart stay), the side buffer and
+ * RSR_P_SENSORDATA are untouched, and no PRNG key advances.  Applied forces enter none of the outputs.
+ *   RSR_D_QM             [nv*nv]    joint-space inertia, dense, symmetric, armature included (mj_fullM)
+ *   RSR_D_QFRC_BIAS      [nv]       Coriolis, centrifugal and gravity forces
+ *   RSR_D_QFRC_PASSIVE   [nv]       -damping * qvel
+ *   RSR_D_QFRC_ACTUATOR  [nv]       gear * actuator_force, clamped to the joint's actfrcrange
+ *                                   (qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator, plus any applied forces)
+ *   RSR_D_JAC            [K*6*nv]   per Jacobian site k: jacp rows x, y, z then jacr rows x, y, z, each [nv], world frame
+ *                                   (mj_jacSite); columns of dofs that do not move the site's body are 0
+ *   RSR_D_JAC_SITE_XPOS  [K*3]      the sites' world positions, where the Jacobians were taken
+ * K is the number of sites of rsr_physics_set_jac_sites (0 until set: width 0).  The buffer is allocated and zeroed by the first
+ * of these three calls; the views' pointers and row stride do not move afterwards.  rsr_physics_destroy frees it. */
+#define RSR_MAX_JAC_SITES 8
+enum rsr_dynamics_field {
+  RSR_D_QM = 0, RSR_D_QFRC_BIAS, RSR_D_QFRC_PASSIVE, RSR_D_QFRC_ACTUATOR, RSR_D_JAC, RSR_D_JAC_SITE_XPOS,
+  RSR_D_COUNT
+};
+/* site_ids: nsite site ids (host memory), at most RSR_MAX_JAC_SITES; nsite = 0 clears the table.  Checked before any device work
+ * (null handle, nsite outside [0, RSR_MAX_JAC_SITES], a null table, an id outside [0, nsite of the model): RSR_ERR_ARG); on
+ * error the previous table stays.  Waits for the device (launches in flight read the table). */
+int rsr_physics_set_jac_sites(rsr_physics* p, const int32_t* site_ids, int nsite);
+/* env_ids: device int32 [count], or NULL for every env (count is ignored); ids outside [0, num_envs) are skipped.  Only the
+ * listed envs' rows of the buffer are written.  RSR_ERR_ARG: null handle, env_ids with count < 1. */
+int rsr_physics_dynamics(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream);
+/* Zero-copy view (as rsr_physics_view) of one field of the dynamics buffer.  RSR_ERR_ARG for an unknown id. */
+int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
 
 #ifdef __cplusplus
 }

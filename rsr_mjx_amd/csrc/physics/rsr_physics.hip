@@ -1,5 +1,6 @@
 // rsr_physics.hip -- the C ABI of the physics layer (include/rsr_physics.h): rsr_physics_step / rsr_physics_forward /
-// rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp and the applied forces (rsr_physics_set_applied).  The kernels are in the family units
+// rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
+// the dynamics terms (rsr_physics_dynamics).  The kernels are in the family units
 // (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,9 @@ struct rsr_physics {
   float* xfrc = nullptr;  // data.xfrc_applied [n][nbody*6], allocated on the first rsr_physics_set_applied(p, 1)
   float* qfrc = nullptr;  // data.qfrc_applied [n][nv]
   bool applied = false;   // launches take the applied kernels
+  float* dyn = nullptr;   // the dynamics buffer [n][DynLayout::stride], allocated on first use (dyn_alloc)
+  int* jac_sites = nullptr;  // [RSR_MAX_JAC_SITES] the Jacobian sites (device)
+  int njac = 0;
 };
 
 extern "C" int rsr_physics_create(rsr_batch* b, rsr_physics** out) {
@@ -50,6 +54,8 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
   if (p->sens_el) (void)hipFree(p->sens_el);
   if (p->xfrc) (void)hipFree(p->xfrc);
   if (p->qfrc) (void)hipFree(p->qfrc);
+  if (p->dyn) (void)hipFree(p->dyn);
+  if (p->jac_sites) (void)hipFree(p->jac_sites);
   delete p;
 }
 
@@ -195,5 +201,71 @@ extern "C" int rsr_physics_applied_view(rsr_physics* p, int field, void** dev_pt
   }
   shape[0] = p->b->n; shape[1] = w;
   stride[0] = w; stride[1] = 1;
+  return RSR_OK;
+}
+
+// the dynamics buffer and the site table, on first use (zeroed)
+static int dyn_alloc(rsr_physics* p, const char* who) {
+  if (p->dyn) return RSR_OK;
+  const size_t bytes = (size_t)p->b->n * rsr::dyn_layout(p->b->model->dims.nv).stride * sizeof(float);
+  HIPCHK(hipSetDevice(p->b->device));
+  float* dyn = nullptr; int* sites = nullptr;
+  if (hipMalloc(&dyn, bytes) != hipSuccess) return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(dynamics buffer)");
+  if (hipMalloc(&sites, RSR_MAX_JAC_SITES * sizeof(int)) != hipSuccess) { (void)hipFree(dyn); return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(site table)"); }
+  if (hipMemset(dyn, 0, bytes) != hipSuccess || hipMemset(sites, 0, RSR_MAX_JAC_SITES * sizeof(int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(dyn); (void)hipFree(sites); return fail(RSR_ERR_HIP, std::string(who) + ": hipMemset");
+  }
+  p->dyn = dyn; p->jac_sites = sites;
+  return RSR_OK;
+}
+
+extern "C" int rsr_physics_set_jac_sites(rsr_physics* p, const int32_t* site_ids, int nsite) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_set_jac_sites: null handle");
+  if (nsite < 0 || nsite > RSR_MAX_JAC_SITES || (nsite > 0 && !site_ids))
+    return fail(RSR_ERR_ARG, "rsr_physics_set_jac_sites: nsite must lie in [0, " + std::to_string(RSR_MAX_JAC_SITES) + "] and the table must not be null");
+  for (int k = 0; k < nsite; ++k)
+    if (site_ids[k] < 0 || site_ids[k] >= p->b->model->dims.nsite)
+      return fail(RSR_ERR_ARG, "rsr_physics_set_jac_sites: site " + std::to_string(k) + ": site id out of range");
+  if (const int rc = dyn_alloc(p, "rsr_physics_set_jac_sites")) return rc;
+  HIPCHK(hipSetDevice(p->b->device));
+  HIPCHK(hipDeviceSynchronize());               // launches in flight read the table
+  if (nsite > 0) HIPCHK(hipMemcpy(p->jac_sites, site_ids, nsite * sizeof(int32_t), hipMemcpyHostToDevice));
+  p->njac = nsite;
+  return RSR_OK;
+}
+
+extern "C" int rsr_physics_dynamics(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_dynamics: null handle");
+  if (env_ids && count < 1) return fail(RSR_ERR_ARG, "rsr_physics_dynamics: count < 1 with env_ids");
+  if (const int rc = dyn_alloc(p, "rsr_physics_dynamics")) return rc;
+  rsr_batch* b = p->b;
+  HIPCHK(hipSetDevice(b->device));
+  rsr::Launch x = launch_args(b, hip_stream);
+  x.grid = env_ids ? count : b->n;
+  x.a.debug = nullptr;
+  x.p = rsr::pack_dyn(rsr::DynArgs{p->dyn, env_ids, p->jac_sites, p->njac});
+  launch(b, rsr::OP_PHYS_DYNAMICS, x);
+  { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string("rsr_physics_dynamics: launch: ") + hipGetErrorString(le)); }
+  return RSR_OK;
+}
+
+extern "C" int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
+  if (!p || !dev_ptr || !shape || !stride) return fail(RSR_ERR_ARG, "rsr_physics_dynamics_view: null argument");
+  const int nv = p->b->model->dims.nv;
+  const rsr::DynLayout DL = rsr::dyn_layout(nv);
+  int off = -1, w = 0;
+  switch (field) {
+    case RSR_D_QM: off = DL.qM; w = nv * nv; break;
+    case RSR_D_QFRC_BIAS: off = DL.bias; w = nv; break;
+    case RSR_D_QFRC_PASSIVE: off = DL.passive; w = nv; break;
+    case RSR_D_QFRC_ACTUATOR: off = DL.actuator; w = nv; break;
+    case RSR_D_JAC: off = DL.jac; w = p->njac * 6 * nv; break;
+    case RSR_D_JAC_SITE_XPOS: off = DL.sxpos; w = p->njac * 3; break;
+    default: return fail(RSR_ERR_ARG, "rsr_physics_dynamics_view: unknown field id");
+  }
+  if (const int rc = dyn_alloc(p, "rsr_physics_dynamics_view")) return rc;
+  *dev_ptr = p->dyn + off;
+  shape[0] = p->b->n; shape[1] = w;
+  stride[0] = DL.stride; stride[1] = 1;
   return RSR_OK;
 }

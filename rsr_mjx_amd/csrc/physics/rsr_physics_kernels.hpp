@@ -1,11 +1,13 @@
 // rsr_physics_kernels.hpp -- the physics-level kernels (include/rsr_physics.h): each family unit instantiates them for its Dims,
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
-// forward) and rollout_kernel, instantiated plain and with applied forces: the applied kernels take the handle's Applied buffers as
-// one more argument and pass forward<C> their env's rows as its force stage (rsr_applied.hpp).
+// forward), rollout_kernel and dynamics_kernel (rsr_dynamics.hpp); the first two are instantiated plain and with applied forces:
+// the applied kernels take the handle's Applied buffers as one more argument and pass forward<C> their env's rows as its force
+// stage (rsr_applied.hpp).
 #pragma once
 #include "../rsr_launch.hpp"
 #include "rsr_sensors.hpp"
 #include "rsr_applied.hpp"
+#include "rsr_dynamics.hpp"
 
 namespace rsr {
 
@@ -165,6 +167,11 @@ void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
 // the physics ops of a family's launch entry (rsr_launch.hpp)
 template <class C, int WAVES>
 int launch_physics(int op, const Launch& x) {
+  static_assert(OP_PHYS_DYNAMICS > OP_PHYS_ROLLOUT, "the dynamics op lies past enum Op");
+  if (op == OP_PHYS_DYNAMICS) {     // (applied forces enter none of its outputs)
+    hipLaunchKernelGGL((dynamics_kernel<C, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, unpack_dyn(x.p));
+    return 0;
+  }
   if (x.ap.xfrc) {                  // applied forces on
     if (op == OP_PHYS_STEP) hipLaunchKernelGGL((physics_kernel<C, true, WAVES, Applied>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.ap);
     else if (op == OP_PHYS_FORWARD) hipLaunchKernelGGL((physics_kernel<C, false, WAVES, Applied>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.ap);

@@ -6,6 +6,9 @@
     mjx_env.get_sensor_data(model, data, name)  ->  Physics.sensor(name)                 (site sensors, Physics.set_sensors)
     data.replace(xfrc_applied=..., qfrc_applied=...) ->  Physics.set_applied(xfrc, qfrc)  (held by every later step / forward /
                                                                                            rollout, like a Data field)
+    mj_fullM / data.qfrc_bias / mj_jacSite       ->  Physics.dynamics()                   (qM, qfrc_bias, qfrc_passive,
+                                                                                           qfrc_actuator, jacp, jacr at the
+                                                                                           record's current state)
 
 `Physics(env)` shares the batch of a BatchedEnv (Airbot cube / sf / T-shape, Go2 joystick, handstand / footstand): the same model,
 the same per-env domain randomisation, the same record and the same stream.  The pipeline fields it exposes are the record's own
@@ -74,6 +77,8 @@ class Physics:
         # data.xfrc_applied [N, nbody, 6] / data.qfrc_applied [N, nv]: writable views while applied forces are on, else None
         self.xfrc_applied = None
         self.qfrc_applied = None
+        # the dynamics buffer's views (dynamics): fetched on first use, when the library allocates the buffer
+        self._dyn: Optional[Dict[str, Any]] = None
         if sensors is not None:
             self.set_sensors(sensors)
 
@@ -183,6 +188,70 @@ class Physics:
             return
         self.xfrc_applied = self.qfrc_applied = None
         _lib.check(_lib.lib().rsr_physics_set_applied(self._h, 0))
+
+    def _dyn_views(self) -> Dict[str, Any]:
+        if self._dyn is None:
+            import torch
+            d, dyn = self.dims, {}
+            for fid, name in enumerate(_lib.DYNAMICS_FIELDS):
+                ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
+                _lib.check(_lib.lib().rsr_physics_dynamics_view(self._h, fid, C.byref(ptr), shape, stride))
+                dyn[name] = _view(ptr, shape, stride, self.device)
+            k = dyn["jac_site_xpos"].shape[1] // 3
+            jac = dyn["jac"].unflatten(1, (k, 6, d.nv)) if k else torch.empty((self.num_envs, 0, 6, d.nv), dtype=torch.float32, device=self.device)
+            self._dyn = dict(qM=dyn["qM"].unflatten(1, (d.nv, d.nv)), qfrc_bias=dyn["qfrc_bias"], qfrc_passive=dyn["qfrc_passive"],
+                             qfrc_actuator=dyn["qfrc_actuator"], jacp=jac[:, :, 0:3], jacr=jac[:, :, 3:6],
+                             jac_site_xpos=dyn["jac_site_xpos"].unflatten(1, (k, 3)) if k else torch.empty((self.num_envs, 0, 3), dtype=torch.float32, device=self.device))
+        return self._dyn
+
+    # outputs of dynamics(): views of the handle's dynamics buffer, zeros until the first call
+    qM = property(lambda self: self._dyn_views()["qM"], doc="[N, nv, nv] joint-space inertia, dense, armature included (mj_fullM)")
+    qfrc_bias = property(lambda self: self._dyn_views()["qfrc_bias"], doc="[N, nv] Coriolis, centrifugal and gravity forces")
+    qfrc_passive = property(lambda self: self._dyn_views()["qfrc_passive"], doc="[N, nv] -damping * qvel")
+    qfrc_actuator = property(lambda self: self._dyn_views()["qfrc_actuator"], doc="[N, nv] gear * actuator_force, actfrcrange clamp included")
+    jacp = property(lambda self: self._dyn_views()["jacp"], doc="[N, K, 3, nv] translational Jacobians of the sites of set_jac_sites")
+    jacr = property(lambda self: self._dyn_views()["jacr"], doc="[N, K, 3, nv] rotational Jacobians of the sites of set_jac_sites")
+    jac_site_xpos = property(lambda self: self._dyn_views()["jac_site_xpos"], doc="[N, K, 3] where those Jacobians were taken")
+
+    def set_jac_sites(self, sites: Optional[Sequence]) -> None:
+        """The sites whose Jacobians dynamics() evaluates (mj_jacSite): names or ids, at most _lib.MAX_JAC_SITES; None or []
+        clears the table (jacp / jacr get K = 0).  Earlier jacp / jacr / jac_site_xpos views keep their old K: read them again."""
+        import numpy as np
+        ids = []
+        for s_ in list(sites or []):
+            if isinstance(s_, str):
+                try:
+                    sid = int(self.env.sys.id("site", s_))
+                except Exception:
+                    raise ValueError(f"set_jac_sites: no site {s_!r}") from None
+            else:
+                sid = int(s_)
+            if not 0 <= sid < self.dims.nsite:
+                raise ValueError(f"set_jac_sites: site ids must lie in [0, {self.dims.nsite}), got {sid}")
+            ids.append(sid)
+        if len(ids) > _lib.MAX_JAC_SITES:
+            raise ValueError(f"set_jac_sites expects at most {_lib.MAX_JAC_SITES} sites, got {len(ids)}")
+        table = np.asarray(ids, dtype=np.int32)
+        _lib.check(_lib.lib().rsr_physics_set_jac_sites(self._h, table.ctypes.data_as(C.c_void_p) if len(ids) else None, len(ids)))
+        self._dyn = None
+
+    def dynamics(self, env_ids=None) -> None:
+        """The model at the record's current qpos / qvel / ctrl (per-env leaves included), one launch: fills qM, qfrc_bias,
+        qfrc_passive, qfrc_actuator and, for the sites of set_jac_sites, jacp / jacr / jac_site_xpos, of the envs `env_ids`
+        (default: all).  Meant to be called after step / set_state, before choosing the next ctrl or qfrc_applied: it describes
+        the state after the integration, whereas qacc, xquat and the contacts show the step's last forward pass.  Writes nothing
+        else (not the record, the side buffer or sensordata).  Applied forces enter none of the outputs:
+        qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator (+ the applied forces the caller set)."""
+        import torch
+        if env_ids is None:
+            _lib.check(_lib.lib().rsr_physics_dynamics(self._h, None, 0, self._stream()))
+            return
+        ids = self._ids(env_ids, "dynamics")
+        if ids.numel() == 0:
+            return
+        ids32 = ids.to(torch.int32).contiguous()
+        self._dyn_ids_in = ids32                   # kept alive until the next call (the launch is asynchronous)
+        _lib.check(_lib.lib().rsr_physics_dynamics(self._h, C.c_void_p(ids32.data_ptr()), ids.numel(), self._stream()))
 
     def rollout(self, ctrl, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), qpos0=None, qvel0=None,
                 ctrl0=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:

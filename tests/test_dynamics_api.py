@@ -1,0 +1,104 @@
+"""Dynamics terms of the physics layer (rsr_physics_set_jac_sites / rsr_physics_dynamics / rsr_physics_dynamics_view,
+Physics.set_jac_sites / Physics.dynamics), host side only: the ABI and the Python surface.  The kernel is covered by
+tests/test_dynamics_gpu.py."""
+import ctypes as C
+import inspect
+import os
+import re
+
+from conftest import ROOT
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+
+
+def test_header_declares_the_dynamics_api():
+    h = _header()
+    for sig in ("int rsr_physics_set_jac_sites(rsr_physics* p, const int32_t* site_ids, int nsite);",
+                "int rsr_physics_dynamics(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream);",
+                "int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);"):
+        assert sig in h, sig
+    enum = re.search(r"enum rsr_dynamics_field \{([^}]*)\}", h).group(1)
+    names = [t.strip().split("=")[0].strip() for t in enum.split(",") if t.strip()]
+    from rsr_mjx_amd import _lib
+    assert names == ["RSR_D_" + f.upper() for f in _lib.DYNAMICS_FIELDS] + ["RSR_D_COUNT"]
+    assert "RSR_D_QM = 0" in enum
+    nmax = int(re.search(r"#define RSR_MAX_JAC_SITES (\d+)", h).group(1))
+    assert nmax >= 5 and nmax == _lib.MAX_JAC_SITES          # the Go2's IMU and four feet fit
+    # the call is documented as describing the state after the integration
+    assert "after the" in h[h.index("RSR_D_QM") - 1500:h.index("RSR_D_QM")]
+    # the other enums are unchanged
+    assert _lib.PHYS_FIELDS[-1] == "sensordata" and len(_lib.PHYS_FIELDS) == 7 and len(_lib.APPLIED_FIELDS) == 2
+
+
+def test_library_exports_and_argument_checks():
+    from rsr_mjx_amd import _lib
+    L = _lib.lib()
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    for sym in ("rsr_physics_set_jac_sites", "rsr_physics_dynamics", "rsr_physics_dynamics_view"):
+        assert sym in _lib.PHYS_SYMBOLS and getattr(L, sym) is not None
+        assert getattr(L, sym).argtypes is not None
+    # null handle, refused before any device work
+    ids = (C.c_int32 * 2)(0, 1)
+    for table, k in ((None, 0), (ids, 2), (ids, _lib.MAX_JAC_SITES + 1), (ids, -1)):
+        assert L.rsr_physics_set_jac_sites(None, table, k) == -1
+        assert b"null" in L.rsr_last_error()
+    assert L.rsr_physics_dynamics(None, None, 0, None) == -1
+    assert b"null" in L.rsr_last_error()
+    ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
+    for fid in (0, len(_lib.DYNAMICS_FIELDS) - 1, len(_lib.DYNAMICS_FIELDS), -1):
+        assert L.rsr_physics_dynamics_view(None, fid, C.byref(ptr), shape, stride) == -1
+    assert not ptr.value
+
+
+def test_argument_checks_come_before_device_work():
+    """Bad site ids, nsite > RSR_MAX_JAC_SITES, env_ids with count < 1 and unknown view ids: RSR_ERR_ARG on a real handle, with
+    the check ahead of every device call and of the table update (checked by source order, as the handle needs a device)."""
+    src = open(os.path.join(ROOT, "rsr_mjx_amd", "csrc", "physics", "rsr_physics.hip")).read()
+
+    def body(name):
+        b = src[src.index(name + "("):]
+        return b[:b.index("\n}\n")]
+    dev = ("hipSetDevice", "hipDeviceSynchronize", "hipMalloc", "hipMemset", "hipMemcpy", "dyn_alloc", "launch(")
+    first_dev = lambda b: min(b.index(k) for k in dev if k in b)
+    sites = body("int rsr_physics_set_jac_sites")
+    for check in ("!p)", "nsite > RSR_MAX_JAC_SITES", "site_ids[k] >= p->b->model->dims.nsite", "site_ids[k] < 0"):
+        assert sites.index(check) < first_dev(sites), check
+    assert sites.count("RSR_ERR_ARG") == 3 and first_dev(sites) < sites.index("p->njac = nsite")
+    dyn = body("int rsr_physics_dynamics")
+    assert dyn.index("!p)") < first_dev(dyn) and dyn.index("count < 1") < first_dev(dyn)
+    view = body("int rsr_physics_dynamics_view")
+    assert view.index("default: return fail(RSR_ERR_ARG") < first_dev(view)
+    # the buffer goes with the handle
+    destroy = body("void rsr_physics_destroy")
+    assert "hipFree(p->dyn)" in destroy and "hipFree(p->jac_sites)" in destroy
+
+
+def test_the_dynamics_op_stays_clear_of_the_env_sources():
+    """The op and its arguments live in the physics layer: enum Op and struct Launch (sources of the env kernels) do not know it."""
+    csrc = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".hpp")):
+            text = open(os.path.join(csrc, f)).read()
+            assert "OP_PHYS_DYNAMICS" not in text and "dynamics_kernel" not in text and "DynArgs" not in text, f
+    phys = open(os.path.join(csrc, "physics", "rsr_physics.hpp")).read()
+    assert "OP_PHYS_DYNAMICS" in phys and "struct DynLayout" in phys
+    kern = open(os.path.join(csrc, "physics", "rsr_dynamics.hpp")).read()
+    assert "void dynamics_kernel(" in kern
+    for stage in ("kinematics<C>(", "com_crb_mass<C>(", "smooth_forces<C>("):
+        assert stage in kern, stage
+    for absent in ("collision<C>(", "make_constraint<C>(", "solve<C>(", "forward<C>("):
+        assert absent not in kern, absent
+
+
+def test_physics_module_surface():
+    from rsr_mjx_amd.physics import Physics
+    for m in ("set_jac_sites", "dynamics"):
+        assert callable(getattr(Physics, m))
+    assert list(inspect.signature(Physics.dynamics).parameters) == ["self", "env_ids"]
+    assert list(inspect.signature(Physics.set_jac_sites).parameters) == ["self", "sites"]
+    for view in ("qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "jacp", "jacr", "jac_site_xpos"):
+        assert isinstance(getattr(Physics, view), property), view
+    src = inspect.getsource(Physics.set_jac_sites)
+    assert "ValueError" in src and "set_jac_sites expects at most" in src

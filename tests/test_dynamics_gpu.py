@@ -1,0 +1,392 @@
+"""Physics.dynamics (rsr_physics_dynamics, csrc/physics/rsr_dynamics.hpp) on every built family: qM, qfrc_bias, qfrc_passive,
+qfrc_actuator against the CPU oracle, qM under domain randomisation, the site Jacobians against fp64 kinematics, consistency with
+the site velocity sensors and with qacc of a forward pass, no side effects, and gravity compensation end to end.
+
+Errors are relative as in tests/test_physics_gpu.py: |hip - ref| / max(1, |ref|_inf of that env's field).  The bound on a dynamic
+field is that file's rule: p99 <= 1e-5, or <= 3 x the fp32 oracle's own p99 distance from the fp64 oracle where that is larger,
+and every env within max(1e-4, 20 x the largest f32-to-f64 distance).  None of the fields here depends on contacts, so no env is
+excluded."""
+import numpy as np
+import pytest
+
+from rsr_mjx_amd import prng
+from test_physics_gpu import FAMILIES, PIPE, _make, _random_states, _rel
+
+N = 256
+JAC_SITES = {"cube": ["endpoint"], "tshape": ["endpoint", "T_tail", "T_target_tail"],
+             "go2flat": ["imu", "FR", "FL", "RR", "RL"], "go2rough": ["imu", "FR", "FL", "RR", "RL"],
+             "footstand": ["imu", "FR", "FL", "RR", "RL"]}
+DYN = ("qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator")
+ORACLE_NAME = dict(qM="M", qfrc_bias="qfrc_bias", qfrc_passive="qfrc_passive", qfrc_actuator="qfrc_actuator")
+
+
+def _rule(kind, what, err, spread, fails):
+    """The project's bound on a dynamic field (see the module docstring); prints p99 / max, appends to `fails`."""
+    p99, mx = float(np.quantile(err, 0.99)), float(err.max())
+    sp99, smx = float(np.quantile(spread, 0.99)), float(spread.max())
+    print(kind, what, "p99 %.2e max %.2e f32-f64 p99 %.2e max %.2e" % (p99, mx, sp99, smx))
+    if not (p99 <= 1e-5 or p99 <= 3.0 * sp99):
+        fails.append(f"{kind} {what}: p99 {p99:.2e}")
+    cap = max(1e-4, 20.0 * smx)
+    if not (err <= cap).all():
+        fails.append(f"{kind} {what}: {(err > cap).sum()} envs beyond the cap {cap:.2e}, max {mx:.2e}")
+
+
+def _free_states(envdef, kind, n, seed, zero_vel=False):
+    """_random_states moved clear of every contact and joint limit: free bodies (the Airbot's cube / target / T block) parked
+    apart in the air or the Go2 trunk lifted to 1 m, limited joints kept 0.02 inside their range (the middle of a range narrower
+    than 0.1: the Airbot's link4 and fingers).  The Airbot's shoulder (its second joint) is raised by 0.3 rad: the reset pose
+    holds the fingers a centimetre above the table, and the perturbation of _random_states puts them into it in 12 of 256
+    T-shape envs (CPU oracle)."""
+    qpos, qvel, ctrl = _random_states(envdef, kind, n, seed)
+    A = envdef.sys.arrays
+    if kind in ("cube", "tshape"):
+        qpos[:, int(A["jnt_qposadr"][1])] += 0.3
+    for j in range(len(A["jnt_type"])):
+        jt, qa = int(A["jnt_type"][j]), int(A["jnt_qposadr"][j])
+        if jt == 0:
+            qpos[:, qa:qa + 3] = [0.0, 0.0, 1.0] if kind not in ("cube", "tshape") else [3.0 + j, 3.0, 2.0]
+        elif A["jnt_limited"][j]:
+            lo, hi = float(A["jnt_range"][j, 0]), float(A["jnt_range"][j, 1])
+            qpos[:, qa] = 0.5 * (lo + hi) if hi - lo < 0.1 else np.clip(qpos[:, qa], lo + 0.02, hi - 0.02)
+    if zero_vel:
+        qvel[:] = 0.0
+    return qpos, qvel, ctrl
+
+
+_REF = {}
+
+
+def _oracle_ref(oracle_mod, E, key, qpos, qvel, ctrl, names, blob=None):
+    """{precision: {name: [n, w]}} of Oracle.forward(qpos, qvel, ctrl, zeros) per env, plus counts; cached per `key`."""
+    if key in _REF:
+        return _REF[key]
+    n = len(qpos)
+    ref = {}
+    for p in ("f32", "f64"):
+        o = oracle_mod.Oracle(blob or E.blob, p)
+        o.set_ncon_cap(E.dims.ncon_max)
+        rows = {k: [] for k in names + ("counts",)}
+        for e in range(n):
+            o.forward(qpos[e].astype(np.float64), qvel[e].astype(np.float64), ctrl[e], np.zeros(E.dims.nv), step=False)
+            for k in rows:
+                rows[k].append(o.get(k))
+        ref[p] = {k: np.asarray(v) for k, v in rows.items()}
+    _REF[key] = ref
+    return ref
+
+
+def _dyn_fields(phys):
+    return {f: getattr(phys, f).cpu().numpy().astype(np.float64).reshape(phys.num_envs, -1) for f in DYN}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", FAMILIES)
+def test_dynamics_terms_match_the_oracle(oracle_mod, kind):
+    """qM, qfrc_bias, qfrc_passive, qfrc_actuator against Oracle.forward in f64, DR off, 256 perturbed reset states with
+    non-zero qvel; the bound is the module's rule with the f32 oracle's own distance, no env excluded."""
+    import torch
+    from rsr_mjx_amd.physics import Physics
+    envdef, E, _, _ = _make(kind, N, False)
+    E.reset(prng.split(prng.PRNGKey(1), N))
+    qpos, qvel, ctrl = _random_states(envdef, kind, N, 21)
+    assert np.abs(qvel).max() > 0.1
+    phys = Physics(E)
+    assert float(phys.qM.abs().max()) == 0.0 and phys.jacp.shape == (N, 0, 3, E.dims.nv)      # zeros until the first call
+    phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
+    phys.dynamics()
+    torch.cuda.synchronize()
+    hip = _dyn_fields(phys)
+    assert phys.qM.shape == (N, E.dims.nv, E.dims.nv)
+    np.testing.assert_array_equal(phys.qM.cpu().numpy(), phys.qM.cpu().numpy().transpose(0, 2, 1))      # symmetric, bitwise
+    ref = _oracle_ref(oracle_mod, E, (kind, 21), qpos, qvel, ctrl, tuple(ORACLE_NAME.values()))
+    fails = []
+    for f in DYN:
+        r64, r32 = ref["f64"][ORACLE_NAME[f]], ref["f32"][ORACLE_NAME[f]]
+        _rule(kind, f, _rel(hip[f], r64), _rel(r32, r64), fails)
+    assert not fails, fails
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["cube", "go2flat", "go2rough", "footstand"])
+def test_qM_honours_the_per_env_leaves(oracle_mod, kind):
+    """DR on.  Cube (body masses): fp64 mjcf.mass_matrix with the env's masses.  Go2 families (masses, inertial positions,
+    armature, qpos0): the fp64 oracle on a model blob that carries the env's leaves (its debug forward reads the model's own
+    values, so each env gets its own oracle model).  The f32 oracle on the same blob gives the rule's f32-to-f64 distance.
+    The nominal model's qM must miss the bound by far, or the test would not see the leaves."""
+    import torch
+    from rsr_mjx_amd import mjcf
+    from rsr_mjx_amd.model import pack_blob, unpack_blob
+    from rsr_mjx_amd.physics import Physics
+    envdef, E, dr, _ = _make(kind, N, True)
+    E.reset(prng.split(prng.PRNGKey(1), N))
+    qpos, qvel, ctrl = _random_states(envdef, kind, N, 22)
+    phys = Physics(E)
+    phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
+    phys.dynamics()
+    torch.cuda.synchronize()
+    hip = phys.qM.cpu().numpy().astype(np.float64).reshape(N, -1)
+    fields = unpack_blob(E.blob)
+    leaves = [k for k in ("body_mass", "body_ipos", "dof_armature", "qpos0") if dr.get(k) is not None]
+    assert "body_mass" in leaves and (kind == "cube" or len(leaves) == 4)
+    nv = E.dims.nv
+    r64, r32, nominal = np.zeros((N, nv * nv)), np.zeros((N, nv * nv)), np.zeros((N, nv * nv))
+    o_nom = oracle_mod.Oracle(E.blob, "f64")
+    for e in range(N):
+        g = dict(fields)
+        for k in leaves:
+            g[k] = np.asarray(dr[k][e], dtype=fields[k].dtype).reshape(fields[k].shape)
+        blob = pack_blob(g)
+        for p, out in (("f64", r64), ("f32", r32)):
+            o = oracle_mod.Oracle(blob, p)
+            o.forward(qpos[e].astype(np.float64), qvel[e].astype(np.float64), ctrl[e], np.zeros(nv))
+            out[e] = o.get("M")
+        if kind == "cube":
+            r64[e] = mjcf.mass_matrix(envdef.sys, qpos[e].astype(np.float64), body_mass=np.asarray(dr["body_mass"][e], np.float64)).ravel()
+        o_nom.forward(qpos[e].astype(np.float64), qvel[e].astype(np.float64), ctrl[e], np.zeros(nv))
+        nominal[e] = o_nom.get("M")
+    fails = []
+    _rule(kind, "qM (DR)", _rel(hip, r64), _rel(r32, r64), fails)
+    assert not fails, fails
+    assert np.quantile(_rel(nominal, r64), 0.5) > 1e-3, "the randomisation does not move qM: the test shows nothing"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", FAMILIES)
+def test_site_jacobians_match_fp64_kinematics(kind):
+    """jacp / jacr / jac_site_xpos of sites on distinct bodies (a leaf of the longest chain among them) against
+    mjcf.forward_kinematics + body_jacobian at the site's fp64 position: every entry within 1e-5 absolute (the bound on the
+    kinematic fields of a forward pass; lever arms are under a metre), non-ancestor columns exactly 0.0."""
+    import torch
+    from rsr_mjx_amd import mjcf
+    from rsr_mjx_amd.physics import Physics
+    envdef, E, _, _ = _make(kind, N, False)
+    E.reset(prng.split(prng.PRNGKey(1), N))
+    qpos, qvel, ctrl = _random_states(envdef, kind, N, 21)
+    sys_, A = envdef.sys, envdef.sys.arrays
+    names = JAC_SITES[kind]
+    sids = [sys_.id("site", s) for s in names]
+    bodies = [int(A["site_bodyid"][s]) for s in sids]
+    assert len(set(bodies)) == len(bodies)
+    phys = Physics(E)
+    phys.set_jac_sites(names)
+    phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
+    phys.dynamics()
+    torch.cuda.synchronize()
+    jp, jr, sx = phys.jacp.cpu().numpy(), phys.jacr.cpu().numpy(), phys.jac_site_xpos.cpu().numpy()
+    K, nv = len(names), E.dims.nv
+    assert jp.shape == (N, K, 3, nv) and jr.shape == (N, K, 3, nv) and sx.shape == (N, K, 3)
+    worst = dict(jacp=0.0, jacr=0.0, jac_site_xpos=0.0)
+    for e in range(N):
+        kin = mjcf.forward_kinematics(sys_, qpos[e].astype(np.float64))
+        for k, (s, b) in enumerate(zip(sids, bodies)):
+            p = kin["xpos"][b] + kin["xmat"][b] @ A["site_pos"][s]
+            rp, rr = mjcf.body_jacobian(sys_, kin, p, b)
+            worst["jacp"] = max(worst["jacp"], np.abs(jp[e, k] - rp).max())
+            worst["jacr"] = max(worst["jacr"], np.abs(jr[e, k] - rr).max())
+            worst["jac_site_xpos"] = max(worst["jac_site_xpos"], np.abs(sx[e, k] - p).max())
+            off = (rp == 0).all(0) & (rr == 0).all(0)                 # dofs that do not move the body
+            assert (jp[e, k][:, off] == 0.0).all() and (jr[e, k][:, off] == 0.0).all(), (kind, e, names[k])
+    for f, w in worst.items():
+        print(kind, f, "max abs %.2e" % w)
+    assert all(w <= 1e-5 for w in worst.values()), worst
+    # ids work like names; [] clears; more than the maximum or a bad id raises and the table stays
+    from rsr_mjx_amd import _lib
+    with pytest.raises(ValueError):
+        phys.set_jac_sites([0] * (_lib.MAX_JAC_SITES + 1))
+    with pytest.raises(ValueError):
+        phys.set_jac_sites([E.dims.nsite])
+    with pytest.raises(ValueError):
+        phys.set_jac_sites(["no_such_site"])
+    bad = (np.ones(2, np.int32) * E.dims.nsite)
+    assert _lib.lib().rsr_physics_set_jac_sites(phys._h, bad.ctypes.data, 2) == -1
+    many = np.zeros(_lib.MAX_JAC_SITES + 1, np.int32)
+    assert _lib.lib().rsr_physics_set_jac_sites(phys._h, many.ctypes.data, len(many)) == -1
+    assert _lib.lib().rsr_physics_set_jac_sites(phys._h, None, 1) == -1
+    assert _lib.lib().rsr_physics_dynamics(phys._h, bad.ctypes.data, 0, None) == -1          # env_ids with count < 1
+    assert phys.jacp.shape[1] == K
+    phys.set_jac_sites(sids[:1])
+    phys.dynamics()
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(phys.jacp.cpu().numpy()[:, 0], jp[:, 0])
+    phys.set_jac_sites([])
+    phys.dynamics()
+    assert phys.jacp.shape == (N, 0, 3, nv) and phys.jac_site_xpos.shape == (N, 0, 3)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", FAMILIES)
+def test_jacobians_times_qvel_are_the_site_velocity_sensors(kind):
+    """framelinvel / frameangvel sensors on the same sites after forward(), against jacp @ qvel and jacr @ qvel from dynamics()
+    on the same state (product in fp64 on the host): within 1e-5 relative."""
+    import torch
+    from rsr_mjx_amd.physics import Physics
+    envdef, E, _, _ = _make(kind, N, False)
+    E.reset(prng.split(prng.PRNGKey(1), N))
+    qpos, qvel, ctrl = _random_states(envdef, kind, N, 21)
+    names = JAC_SITES[kind]
+    spec = [(f"lin_{s}", "framelinvel", s) for s in names] + [(f"ang_{s}", "frameangvel", s) for s in names]
+    phys = Physics(E, sensors=spec)
+    phys.set_jac_sites(names)
+    phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)          # (runs forward)
+    phys.dynamics()
+    torch.cuda.synchronize()
+    v = phys.qvel.cpu().numpy().astype(np.float64)
+    jp, jr = phys.jacp.cpu().numpy().astype(np.float64), phys.jacr.cpu().numpy().astype(np.float64)
+    worst = 0.0
+    for k, s in enumerate(names):
+        for name, J in ((f"lin_{s}", jp), (f"ang_{s}", jr)):
+            sens = phys.sensor(name).cpu().numpy()
+            err = _rel(np.einsum("nij,nj->ni", J[:, k], v), sens)
+            print(kind, name, "p99 %.2e max %.2e" % (np.quantile(err, 0.99), err.max()))
+            worst = max(worst, float(err.max()))
+    assert worst <= 1e-5, worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", FAMILIES)
+def test_qacc_of_a_forward_pass_follows_from_the_dynamics_terms(oracle_mod, kind):
+    """On states with no contact and no active joint limit (asserted on the fp64 oracle for every env: the Go2 lifted to 1 m, the
+    Airbot arm in free space with its free bodies parked in the air), the fp64 host solve of qM a = qfrc_passive - qfrc_bias +
+    qfrc_actuator must match phys.qacc of forward().  Two rows of these models outlive such a state, and the test removes what
+    it can of them rather than widening the bound.  Dof friction loss (every actuated joint of both robots) is set to zero
+    through the batch's per-env dof_frictionloss leaf, and in the oracle's blob: on the Go2 no constraint row carries force then.
+    The Airbot's finger equality cannot be switched off: its force is taken from the fp64 oracle on the same state
+    (qfrc_constraint) and added to the right-hand side.  (On the Go2 that would not do: its single Newton iteration does not
+    reach M qacc = qfrc_smooth + qfrc_constraint.)  The bound is the rule of test_physics_oracle_parity on qacc, with the f32
+    oracle's own qacc distance."""
+    import torch
+    from rsr_mjx_amd.model import pack_blob, unpack_blob
+    from rsr_mjx_amd.physics import Physics
+    envdef, E, _, _ = _make(kind, N, False)
+    nv = E.dims.nv
+    E.set_randomization({"dof_frictionloss": np.zeros((N, nv), np.float32)})
+    E.reset(prng.split(prng.PRNGKey(1), N))
+    qpos, qvel, ctrl = _free_states(envdef, kind, N, 23)
+    phys = Physics(E)
+    phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
+    phys.dynamics()
+    torch.cuda.synchronize()
+    fields = dict(unpack_blob(E.blob))
+    fields["dof_frictionloss"] = np.zeros_like(fields["dof_frictionloss"])
+    ref = _oracle_ref(oracle_mod, E, (kind, "free", 23), qpos, qvel, ctrl, ("qacc", "qfrc_constraint"), blob=pack_blob(fields))
+    counts = ref["f64"]["counts"]                              # nefc, ne, nf, ncon, ...
+    assert (counts[:, 3] == 0).all(), f"{kind}: contacts in {(counts[:, 3] != 0).sum()} envs"
+    assert (counts[:, 0] == counts[:, 1] + counts[:, 2]).all(), f"{kind}: active limits in {(counts[:, 0] != counts[:, 1] + counts[:, 2]).sum()} envs"
+    assert (phys.contacts()["ncon"] == 0).all()
+    d = _dyn_fields(phys)
+    rhs = d["qfrc_passive"] - d["qfrc_bias"] + d["qfrc_actuator"]
+    if kind in ("cube", "tshape"):                             # both Airbot models carry the finger equality
+        assert (counts[:, 1] == 1).all()
+        rhs = rhs + ref["f64"]["qfrc_constraint"]
+    else:
+        assert (counts[:, 1] == 0).all() and np.abs(ref["f64"]["qfrc_constraint"]).max() == 0.0
+    a = np.stack([np.linalg.solve(d["qM"][e].reshape(nv, nv), rhs[e]) for e in range(N)])
+    fails = []
+    _rule(kind, "qacc from qM and the forces", _rel(a, phys.qacc.cpu().numpy()), _rel(ref["f32"]["qacc"], ref["f64"]["qacc"]), fails)
+    assert not fails, fails
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", FAMILIES)
+def test_dynamics_has_no_side_effects(kind):
+    import torch
+    from rsr_mjx_amd.physics import Physics
+    envdef, E, _, scale = _make(kind, N, kind != "tshape")
+    _, F, _, _ = _make(kind, N, kind != "tshape")
+    E.reset(prng.split(prng.PRNGKey(4), N))
+    F.reset(prng.split(prng.PRNGKey(4), N))
+    rng = np.random.default_rng(0)
+    act = lambda: np.clip(rng.normal(size=(N, E.dims.nu)) * scale, -1, 1).astype(np.float32)
+    a0 = act()
+    E.step(None, a0)
+    F.step(None, a0)
+    names = JAC_SITES[kind]
+    phys = Physics(E, sensors=[("lin", "framelinvel", names[0])])
+    phys.set_jac_sites(names)
+    phys.step(None, 1)
+    torch.cuda.synchronize()
+    bits = lambda t: t.contiguous().view(torch.int32)          # (bitwise: Go2 records hold PRNG key words, some of them NaN patterns)
+    rec0, side0 = E.record.clone(), {k: v.clone() for k, v in phys._side.items()}
+    phys.dynamics()
+    torch.cuda.synchronize()
+    # the record, the side buffer and sensordata are bitwise as before
+    assert torch.equal(bits(E.record), bits(rec0))
+    for k in side0:
+        assert torch.equal(bits(phys._side[k]), bits(side0[k])), k
+    outs = ("qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "jacp", "jacr", "jac_site_xpos")
+    first = {f: getattr(phys, f).clone() for f in outs}
+    assert all(float(first[f].abs().max()) > 0 for f in outs)
+    # two calls on the same state: bitwise equal outputs
+    phys.dynamics()
+    torch.cuda.synchronize()
+    for f in outs:
+        assert torch.equal(bits(getattr(phys, f)), bits(first[f])), f
+    # env_ids: the other envs' rows of every output keep a sentinel, the listed rows get the full call's values
+    for f in outs:
+        getattr(phys, f).fill_(7.25)
+    ids = np.array([3, 17, 64, 100, N - 1])
+    phys.dynamics(env_ids=ids)
+    torch.cuda.synchronize()
+    others = np.setdiff1d(np.arange(N), ids)
+    for f in outs:
+        got = getattr(phys, f)
+        assert bool((got[others] == 7.25).all()), f
+        assert torch.equal(bits(got[ids]), bits(first[f][ids])), f
+    with pytest.raises(ValueError):
+        phys.dynamics(env_ids=[N])
+    with pytest.raises(ValueError):
+        phys.dynamics(env_ids=[1, 1])
+    assert torch.equal(bits(E.record), bits(rec0))
+    # an env.step after dynamics() equals the same step without it (F: the same history, no physics handle)
+    F.record.copy_(rec0)
+    a1 = act()
+    E.step(None, a1)
+    F.step(None, a1)
+    torch.cuda.synchronize()
+    for k in PIPE + ("obs", "reward", "done"):
+        assert torch.equal(bits(E.view(k)), bits(F.view(k))), k
+
+
+@pytest.mark.gpu
+def test_gravity_compensation_holds_the_airbot_arm(oracle_mod):
+    """Airbot cube, arm in free space, qvel = 0: set_applied(qfrc = qfrc_bias - qfrc_passive - qfrc_actuator) from dynamics(),
+    then forward().  In fp64 the same construction from the oracle's M and forces gives exactly zero acceleration, so the
+    reference for |qacc| on the arm dofs (the six arm joints) is 0.  The bound is the fp32 oracle's own residual for the same
+    construction, M32^-1 (qfrc_smooth32 + fp32(qfrc_bias32 - qfrc_passive32 - qfrc_actuator32)): 3 x its p99 on the p99 and 20 x
+    its max on every env.  Measured (256 envs): that residual is exactly 0, p99 and max.  At qvel = 0 qfrc_passive is 0, so
+    qfrc_smooth = act - bias and the applied force bias - act are exact negatives in fp32, and the rows left on these states
+    (friction loss, the finger equality at zero residual) are satisfied by qacc = 0.  So the bound is 0 and the HIP qacc must be
+    exactly 0 as well (measured: it is).  That needs dynamics_kernel's qfrc_bias and qfrc_actuator to be bitwise the terms inside
+    smooth_forces' qfrc_smooth, i.e. the compiler to contract the six-term cdof . cfrcsum product the same way in both places.  If
+    a later toolchain contracts them differently, this test fails with a force residual of an ulp and nothing wrong in the
+    kernel: that is what a failure with |qacc| of the order of ulp(force) / inertia would mean.  The uncompensated |qacc| must be at least 100 x the bound and, the bound being 0, at
+    least 100 in its own right (measured: min 3.1e3, median 9.8e3, the position servos pulling towards ctrl)."""
+    import torch
+    from rsr_mjx_amd.physics import Physics
+    kind, arm = "cube", slice(0, 6)
+    envdef, E, _, _ = _make(kind, N, False)
+    E.reset(prng.split(prng.PRNGKey(1), N))
+    qpos, qvel, ctrl = _free_states(envdef, kind, N, 24, zero_vel=True)
+    phys = Physics(E)
+    phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
+    torch.cuda.synchronize()
+    free = np.abs(phys.qacc.cpu().numpy()[:, arm]).max(1)                 # uncompensated
+    phys.dynamics()
+    phys.set_applied(qfrc=phys.qfrc_bias - phys.qfrc_passive - phys.qfrc_actuator)
+    phys.forward()
+    torch.cuda.synchronize()
+    held = np.abs(phys.qacc.cpu().numpy()[:, arm]).max(1)
+    ref = _oracle_ref(oracle_mod, E, (kind, "free0", 24), qpos, qvel, ctrl, ("M", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "qfrc_smooth"))
+    r = ref["f32"]
+    nv = E.dims.nv
+    f32 = np.float32
+    qfrc = (r["qfrc_bias"].astype(f32) - r["qfrc_passive"].astype(f32) - r["qfrc_actuator"].astype(f32)).astype(f32)
+    total = (r["qfrc_smooth"].astype(f32) + qfrc).astype(np.float64)
+    res = np.stack([np.abs(np.linalg.solve(r["M"][e].reshape(nv, nv), total[e]))[arm].max() for e in range(N)])
+    bound_p99, bound_max = 3.0 * float(np.quantile(res, 0.99)), 20.0 * float(res.max())
+    print("gravity compensation: f32 oracle residual p99 %.3e max %.3e -> bounds p99 %.3e max %.3e; hip |qacc| p99 %.3e max %.3e; "
+          "uncompensated min %.3e median %.3e" % (np.quantile(res, 0.99), res.max(), bound_p99, bound_max, np.quantile(held, 0.99),
+                                                held.max(), free.min(), np.median(free)))
+    assert free.min() >= 100.0 * bound_max and free.min() >= 100.0, "the uncompensated arm barely accelerates: the test would pass vacuously"
+    assert np.quantile(held, 0.99) <= bound_p99 and held.max() <= bound_max

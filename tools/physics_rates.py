@@ -1,8 +1,10 @@
 """Physics-only env-steps/s per model family (rsr_physics_step with nsteps = n_frames) beside the fused env step (rsr_step), both
 timed with HIP events on the launch stream (rsr_timing_begin / rsr_timing_end).  One JSON line per family; --out also writes them
 to a file.  --applied adds the rates with applied forces on (Physics.set_applied: a non-zero xfrc on every body and a qfrc on every
-dof), for the step and for a rollout of --rollout-T control steps, beside the plain ones.
-Usage: python tools/physics_rates.py [--envs 8192] [--steps 50] [--warmup 10] [--applied] [--rollout-T 16] [--out FILE]"""
+dof), for the step and for a rollout of --rollout-T control steps, beside the plain ones.  --dynamics adds ms per
+rsr_physics_dynamics launch without Jacobian sites and with the family's example sites, beside ms per rsr_physics_forward launch
+on the same batch.
+Usage: python tools/physics_rates.py [--envs 8192] [--steps 50] [--warmup 10] [--applied] [--dynamics] [--rollout-T 16] [--out FILE]"""
 from __future__ import annotations
 
 import argparse
@@ -22,6 +24,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--families", default="cube,tshape,go2flat,go2rough,footstand")
     ap.add_argument("--applied", action="store_true")
+    ap.add_argument("--dynamics", action="store_true")
     ap.add_argument("--rollout-T", type=int, default=16)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -89,6 +92,24 @@ def main() -> None:
             row["applied_over_plain_step"] = row["applied_step_ms"] / ms_phys
             row["applied_over_plain_rollout"] = row["applied_rollout_step_ms"] / row["rollout_step_ms"]
             row["rollout_T"] = T
+        if args.dynamics:
+            def per_launch(fn):                     # (forward and dynamics do not count as env launches: divide by the calls)
+                for _ in range(args.warmup):
+                    fn()
+                env.timing_begin()
+                for _ in range(args.steps):
+                    fn()
+                return env.timing_end()[0] / args.steps
+            sites = ["endpoint"] if kind in ("cube", "tshape") else ["imu", "FR", "FL", "RR", "RL"]
+            row["forward_ms"] = per_launch(phys.forward)
+            phys.set_jac_sites([])
+            row["dynamics_ms"] = per_launch(phys.dynamics)
+            phys.set_jac_sites(sites)
+            row["dynamics_sites_ms"] = per_launch(phys.dynamics)
+            row["jac_sites"] = len(sites)
+            row["dynamics_over_forward"] = row["dynamics_sites_ms"] / row["forward_ms"]
+            from bench import csrc_sha16
+            row["csrc_sha16"] = csrc_sha16()
         row["finite"] = bool(torch.isfinite(env.view("qpos")).all())
         print(json.dumps(row), flush=True)
         rows.append(row)
