@@ -26,8 +26,6 @@ struct rsr_physics {
 
 extern "C" int rsr_physics_create(rsr_batch* b, rsr_physics** out) {
   if (!b || !out) return fail(RSR_ERR_ARG, "rsr_physics_create: null argument");
-  if (rsr::family_of(b->model->dims.env_kind) == rsr::FAMILY_NONE)
-    return fail(RSR_ERR_UNSUPPORTED, "rsr_physics_create: no physics kernel for this env kind");
   HIPCHK(hipSetDevice(b->device));
   const rsr_dims& d = b->model->dims;
   rsr_physics* p = new rsr_physics();
@@ -59,6 +57,7 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
   delete p;
 }
 
+// One physics op on `grid` envs (ids: which, or null: the first `grid`), the handle's buffers as every op's arguments; reports the launch error as `who`.
 static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, int grid, int nsteps, int op, void* hip_stream, const char* who,
                           const rsr::RollArgs& r = rsr::RollArgs{}) {
   rsr_batch* b = ph->b;
@@ -68,8 +67,9 @@ static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, in
   x.a.debug = nullptr;
   x.p = rsr::PhysArgs{ctrl, ph->out, ids, nsteps, ph->sd, rsr::SensArgs{ph->sens_el, ph->nsd, ph->acc_site}};
   x.r = r;
+  x.d = rsr::DynArgs{ph->dyn, ids, ph->jac_sites, ph->njac};
   if (ph->applied) x.ap = rsr::Applied{ph->xfrc, ph->qfrc};
-  launch(b, op, x);
+  if (launch(b, op, x) < 0) return fail(RSR_ERR_UNSUPPORTED, std::string(who) + ": the model's kernels have no such op");
   { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
   return RSR_OK;
 }
@@ -123,7 +123,7 @@ extern "C" int rsr_physics_set_sensors(rsr_physics* p, const int32_t* table, int
     return fail(RSR_ERR_ARG, "rsr_physics_set_sensors: nsensor must lie in [0, 64] and the table must not be null");
   static const int width[RSR_S_COUNT] = {3, 3, 3, 3, 3, 3, 4, 3, 3};
   const rsr_model* md = p->b->model;
-  const int nsite = md->dims.nsite, kind = md->dims.env_kind;
+  const int nsite = md->dims.nsite;
   const int32_t* site_body = static_cast<const int32_t*>(md->find("site_bodyid"));
   const int32_t* env_ids = static_cast<const int32_t*>(md->find("env_ids"));
   std::vector<int4> el;
@@ -138,7 +138,7 @@ extern "C" int rsr_physics_set_sensors(rsr_physics* p, const int32_t* table, int
     if ((int)el.size() + width[type] > RSR_MAX_SENSORDATA) return fail(RSR_ERR_ARG, at + "more than 64 sensordata floats");
     if (type == RSR_S_ACCELEROMETER) {
       // the kernels track the acceleration bias of one body: the Go2 IMU site's (env_ids[0])
-      if (rsr::family_of(kind) != rsr::FAMILY_GO2 || !site_body || !env_ids || site_body[site] != site_body[env_ids[0]])
+      if (md->spec->family != rsr::FAMILY_GO2 || !site_body || !env_ids || site_body[site] != site_body[env_ids[0]])
         return fail(RSR_ERR_UNSUPPORTED, at + "accelerometer only on a site of the Go2 IMU's body");
       if (acc_site >= 0 && acc_site != site) return fail(RSR_ERR_UNSUPPORTED, at + "accelerometers on more than one site");
       acc_site = site;
@@ -238,15 +238,7 @@ extern "C" int rsr_physics_dynamics(rsr_physics* p, const int32_t* env_ids, int 
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_dynamics: null handle");
   if (env_ids && count < 1) return fail(RSR_ERR_ARG, "rsr_physics_dynamics: count < 1 with env_ids");
   if (const int rc = dyn_alloc(p, "rsr_physics_dynamics")) return rc;
-  rsr_batch* b = p->b;
-  HIPCHK(hipSetDevice(b->device));
-  rsr::Launch x = launch_args(b, hip_stream);
-  x.grid = env_ids ? count : b->n;
-  x.a.debug = nullptr;
-  x.p = rsr::pack_dyn(rsr::DynArgs{p->dyn, env_ids, p->jac_sites, p->njac});
-  launch(b, rsr::OP_PHYS_DYNAMICS, x);
-  { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string("rsr_physics_dynamics: launch: ") + hipGetErrorString(le)); }
-  return RSR_OK;
+  return physics_launch(p, nullptr, env_ids, env_ids ? count : p->b->n, 1, rsr::OP_PHYS_DYNAMICS, hip_stream, "rsr_physics_dynamics");
 }
 
 extern "C" int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {

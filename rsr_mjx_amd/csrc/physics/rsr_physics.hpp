@@ -21,8 +21,6 @@ __host__ __device__ inline PhysLayout phys_layout(int nv, int nu, int nbody, int
   p.stride = (p.ncon_drop + 1 + 15) & ~15;
   return p;
 }
-// (For OP_PHYS_DYNAMICS the same struct carries a DynArgs instead, see pack_dyn / unpack_dyn below: out, ids, sens.el and sens.nsd
-// then mean the dynamics buffer, the env list, the site ids and their count, and launch_physics must not read x.p any other way.)
 struct PhysArgs {
   const float* ctrl;    // [N][nu] or null (keep the record's ctrl)
   float* out;           // side buffer [N][PhysLayout::stride] or null
@@ -44,11 +42,9 @@ struct RollArgs {
   float *qpos, *qvel, *time, *aforce, *ncon, *sd;
 };
 
-// rsr_physics_dynamics (rsr_dynamics.hpp): a physics op of its own, past enum Op of rsr_launch.hpp (the family units pass every
-// op they do not know on to launch_physics).  Its buffer, per env, floats: qM [nv*nv] | qfrc_bias [nv] | qfrc_passive [nv] |
+// rsr_physics_dynamics (rsr_dynamics.hpp).  Its buffer, per env, floats: qM [nv*nv] | qfrc_bias [nv] | qfrc_passive [nv] |
 // qfrc_actuator [nv] | jac_site_xpos [RSR_MAX_JAC_SITES*3] | jac [RSR_MAX_JAC_SITES][6][nv] (rows jacp x y z, jacr x y z),
 // padded to 16 floats.
-constexpr int OP_PHYS_DYNAMICS = 64;
 struct DynLayout { int qM, bias, passive, actuator, sxpos, jac, stride; };
 __host__ __device__ inline DynLayout dyn_layout(int nv) {
   DynLayout d;
@@ -57,20 +53,12 @@ __host__ __device__ inline DynLayout dyn_layout(int nv) {
   d.stride = (d.jac + RSR_MAX_JAC_SITES * 6 * nv + 15) & ~15;
   return d;
 }
-// The launch arguments of OP_PHYS_DYNAMICS.  struct Launch is part of the env kernels' sources and stays as it is, and PhysArgs
-// is a by-value argument of the existing kernels, so the op travels in the PhysArgs fields it has no other use for:
-//   out = the dynamics buffer [N][DynLayout::stride], ids = the env list or null, sens.el = the site ids, sens.nsd = their count.
+// The launch arguments of OP_PHYS_DYNAMICS (Launch::d)
 struct DynArgs {
-  float* out;
-  const int* ids;
+  float* out;           // the dynamics buffer [N][DynLayout::stride]
+  const int* ids;       // [grid] the envs to run, or null: env = workgroup index
   const int* sites;     // [nsite] site ids of the Jacobians (device)
   int nsite;
 };
-inline PhysArgs pack_dyn(const DynArgs& d) {
-  return PhysArgs{nullptr, d.out, d.ids, 1, nullptr, SensArgs{reinterpret_cast<const int4*>(d.sites), d.nsite, -1}};
-}
-__host__ __device__ inline DynArgs unpack_dyn(const PhysArgs& p) {
-  return DynArgs{p.out, p.ids, reinterpret_cast<const int*>(p.sens.el), p.sens.nsd};
-}
 
 }  // namespace rsr

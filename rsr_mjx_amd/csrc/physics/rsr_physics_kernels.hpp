@@ -167,21 +167,15 @@ void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
 // the physics ops of a family's launch entry (rsr_launch.hpp)
 template <class C, int WAVES>
 int launch_physics(int op, const Launch& x) {
-  static_assert(OP_PHYS_DYNAMICS > OP_PHYS_ROLLOUT, "the dynamics op lies past enum Op");
-  if (op == OP_PHYS_DYNAMICS) {     // (applied forces enter none of its outputs)
-    hipLaunchKernelGGL((dynamics_kernel<C, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, unpack_dyn(x.p));
-    return 0;
+  auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, args...); return 0; };
+  const bool ap = x.ap.xfrc != nullptr;      // applied forces on
+  switch (op) {
+    case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, true, WAVES>, x.p);
+    case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, false, WAVES>, x.p);
+    case OP_PHYS_ROLLOUT: return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
+    case OP_PHYS_DYNAMICS: return go(dynamics_kernel<C, WAVES>, x.d);      // (applied forces enter none of its outputs)
+    default: return -1;
   }
-  if (x.ap.xfrc) {                  // applied forces on
-    if (op == OP_PHYS_STEP) hipLaunchKernelGGL((physics_kernel<C, true, WAVES, Applied>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.ap);
-    else if (op == OP_PHYS_FORWARD) hipLaunchKernelGGL((physics_kernel<C, false, WAVES, Applied>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.ap);
-    else hipLaunchKernelGGL((rollout_kernel<C, WAVES, Applied>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.r, x.ap);
-    return 0;
-  }
-  if (op == OP_PHYS_STEP) hipLaunchKernelGGL((physics_kernel<C, true, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p);
-  else if (op == OP_PHYS_FORWARD) hipLaunchKernelGGL((physics_kernel<C, false, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p);
-  else hipLaunchKernelGGL((rollout_kernel<C, WAVES>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.p, x.r);
-  return 0;
 }
 
 }  // namespace rsr

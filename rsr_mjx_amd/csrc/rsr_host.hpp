@@ -1,8 +1,10 @@
 // rsr_host.hpp -- what the two host units share (rsr_mjx.hip: the C ABI of include/rsr_mjx.h; physics/rsr_physics.hip: that of
-// include/rsr_physics.h): the model and batch structs, error reporting, and the dispatch of launches to the family units.
+// include/rsr_physics.h): the model and batch structs, error reporting, what the host knows of each kernel family (KernelSpec), and
+// the dispatch of launches to the family units.
 #pragma once
 #include <cstring>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "rsr_launch.hpp"
@@ -13,12 +15,44 @@ using rsr::Layout;
 int fail(int code, const std::string& msg);        // sets rsr_last_error, returns code
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(RSR_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
+namespace rsr {
+// the unit holding an env kind's kernels
+enum Family { FAMILY_CUBE, FAMILY_TSHAPE, FAMILY_GO2 };
+
+// What the host needs to know of the kernels an env kind runs, read off their Dims once (spec_of): the dimensions a model must
+// have, the structure rsr_model_create checks it for, and the sizes the record layout and rsr_model_dims report.
+struct KernelSpec {
+  Family family;
+  int nq, nv, nu, nb, nj, ng, ns, np, neq, nf, nl, obs, nmet;     // a model fits when it has exactly these
+  int nga, condim;                       // geom slots of the LDS image; the condim of every contact pair
+  int tree1, tree2;                      // tree1 > 0: separate kinematic trees over dofs [0, tree1), [tree1, tree2), [tree2, nv)
+  int iso0, iso1;                        // iso1 > iso0: dofs [iso0, iso1) decoupled from the rest
+  bool arrow; int ant, alegn, alegs;     // block-arrow factorisation: ant trunk dofs carrying alegs legs of alegn dofs
+  bool hfield;                           // sphere / height-field pairs are compiled in
+  int ncon, nefc, lds_bytes;
+  int ninfo, priv;                       // floats of the record's Go2 info block and of each privileged-obs block
+  constexpr auto tie() const {           // every field, for comparing two specs
+    return std::tie(family, nq, nv, nu, nb, nj, ng, ns, np, neq, nf, nl, obs, nmet, nga, condim, tree1, tree2, iso0, iso1, arrow, ant, alegn,
+                    alegs, hfield, ncon, nefc, lds_bytes, ninfo, priv);
+  }
+};
+template <class C>
+constexpr KernelSpec spec_of(Family family) {
+  return {family, C::NQ, C::NV, C::NU, C::NB, C::NJ, C::NG, C::NS, C::NP, C::NEQ, C::NF, C::NL, C::OBS, C::NMET,
+          C::NGA, C::CONDIM, C::TREE1, C::TREE2, C::ISO0, C::ISO1, C::ARROW, C::ANT, C::ALEGN, C::ALEGS, C::HFIELD,
+          C::NCON, C::NEFC, (int)sizeof(Smem<C>), C::NINFO, C::NINFO > 0 ? GO2_PRIV : 0};
+}
+// the spec of an env kind, or null: no kernel is built for it.  The only host code that names the Dims types (rsr_mjx.hip).
+const KernelSpec* kernel_spec(int env_kind);
+}  // namespace rsr
+
 struct blob_entry { char name[40]; int32_t dtype, count, offset, reserved; };
 
 struct rsr_model {
   std::vector<char> blob;
   rsr_dims dims;
   Layout layout;
+  const rsr::KernelSpec* spec = nullptr;      // of dims.env_kind; set once rsr_model_create has accepted the model
   bool has_hfield = false;      // any PAIR_HFIELD_SPHERE pair: the Go2 kernels with the height-field narrow phase
   const void* find(const char* name, int* count = nullptr) const {
     const int32_t* h = reinterpret_cast<const int32_t*>(blob.data());
@@ -57,14 +91,9 @@ struct rsr_batch {
   float* racc;                  // [n] reward sums of the repeats, or null
 };
 
-namespace rsr {
-// the unit holding an env kind's kernels: the only place that maps env kinds to kernels
-enum Family { FAMILY_NONE = -1, FAMILY_CUBE, FAMILY_TSHAPE, FAMILY_GO2 };
-Family family_of(int env_kind);
-}  // namespace rsr
 
 rsr::StepArgs make_args(rsr_batch* b);
 // the batch's launch arguments: grid = envs, its model view, record layout and StepArgs, on the caller's stream
 rsr::Launch launch_args(rsr_batch* b, void* hip_stream);
-// op (rsr::Op) by the family unit of the batch's env kind; returns what the unit's launch entry returns
+// op (rsr::Op) by the family unit of the batch's model (KernelSpec::family); returns what the unit's launch entry returns
 int launch(const rsr_batch* b, int op, const rsr::Launch& x);

@@ -1,7 +1,7 @@
 // rsr_launch.hpp -- the launch entry of each family unit.  The library is three units of kernels, one per model family, each with
 // its own flags (rsr_mjx_amd/build.py): rsr_cube.hip (Airbot cube / sf), rsr_tshape.hip (Airbot T-shape), rsr_go2.hip (Go2 joystick,
 // flat or on a height field, and handstand / footstand).  Each exports one function that launches its kernels; the host picks the
-// unit from the env kind in one place (family_of in rsr_host.hpp).
+// unit from the model's KernelSpec (rsr_host.hpp) in one place (launch in rsr_mjx.hip).
 #pragma once
 #include "rsr_env.hpp"
 #include "physics/rsr_physics.hpp"
@@ -15,6 +15,7 @@ enum Op {
   OP_PHYS_FORWARD,       // rsr_physics_forward[_envs]: grid = envs or listed envs (p.ids)
   OP_PHYS_STEP,          // rsr_physics_step
   OP_PHYS_ROLLOUT,       // rsr_physics_rollout (r)
+  OP_PHYS_DYNAMICS,      // rsr_physics_dynamics (d): grid = envs or listed envs (d.ids)
 };
 
 struct Launch {
@@ -24,13 +25,15 @@ struct Launch {
   Layout L;
   StepArgs a;
   Sched sc;             // OP_STEP of the Airbot units
-  PhysArgs p;           // OP_PHYS_*
+  PhysArgs p;           // OP_PHYS_FORWARD, OP_PHYS_STEP, OP_PHYS_ROLLOUT
   RollArgs r;           // OP_PHYS_ROLLOUT
-  Applied ap;           // OP_PHYS_*: the applied forces, or ap.xfrc null: none (the plain kernels)
+  DynArgs d;            // OP_PHYS_DYNAMICS
+  Applied ap;           // the ops that take p: the applied forces, or ap.xfrc null: none (the plain kernels)
   int env_kind;         // the Go2 unit's pick: handstand / footstand, or the joystick with (hfield) or without the height field
   bool hfield;
 };
 
+// each returns 0, or what its op says above; -1: an op the unit does not know (nothing is launched)
 int launch_cube(int op, const Launch& x);
 int launch_tshape(int op, const Launch& x);
 int launch_go2(int op, const Launch& x);

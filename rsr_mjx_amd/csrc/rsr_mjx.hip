@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include "rsr_host.hpp"
 
@@ -94,18 +95,25 @@ __global__ __launch_bounds__(64) void repeat_post_kernel(float* __restrict__ sta
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
-rsr::Family rsr::family_of(int env_kind) {
+const rsr::KernelSpec* rsr::kernel_spec(int env_kind) {
+  static constexpr KernelSpec cube = spec_of<CubeDims>(FAMILY_CUBE), tshape = spec_of<TShapeDims>(FAMILY_TSHAPE),
+                              go2 = spec_of<Go2Dims>(FAMILY_GO2), go2_flat = spec_of<Go2FlatDims>(FAMILY_GO2), hand = spec_of<HandDims>(FAMILY_GO2);
+  // a joystick model is accepted against Go2Dims and runs Go2FlatDims when it has no height-field pair (launch_go2): apart from
+  // that stage the host must see one kernel
+  constexpr auto but_hfield = [](KernelSpec k) { k.hfield = false; return k; };
+  static_assert(go2.hfield && but_hfield(go2).tie() == go2_flat.tie(), "Go2FlatDims is Go2Dims without the height-field stage");
   switch (env_kind) {
-    case ENV_CUBE: case ENV_AIRBOT_SF: return FAMILY_CUBE;
-    case ENV_TSHAPE: return FAMILY_TSHAPE;
-    case ENV_GO2: case ENV_GO2_HANDSTAND: return FAMILY_GO2;
-    default: return FAMILY_NONE;
+    case ENV_CUBE: case ENV_AIRBOT_SF: return &cube;
+    case ENV_TSHAPE: return &tshape;
+    case ENV_GO2: return &go2;
+    case ENV_GO2_HANDSTAND: return &hand;
+    default: return nullptr;
   }
 }
 
-static bool go2_family(int env_kind) { return rsr::family_of(env_kind) == rsr::FAMILY_GO2; }
+static bool go2_family(const rsr_model* m) { return m->spec->family == rsr::FAMILY_GO2; }
 
-static Layout make_layout(const rsr_dims& d) {
+static Layout make_layout(const rsr_dims& d, const rsr::KernelSpec& k) {
   Layout L{};
   int o = 0;
   auto take = [&](int n) { int r = o; o += n; return r; };
@@ -119,9 +127,8 @@ static Layout make_layout(const rsr_dims& d) {
   L.target_pos = take(3); L.new_cube_pos = take(2); L.site_pos = take(3); L.cube_pos = take(3); L.last_action = take(1);
   L.target_base_pos = take(3); L.target_vertical_pos = take(3); L.target_w = take(1); L.new_T_pos = take(2);
   L.T_pos = take(3); L.xita = take(1);
-  const bool go2 = go2_family(d.env_kind);
-  L.go2_info = take(go2 ? 144 : 0);
-  L.priv_obs = take(go2 ? 123 : 0); L.f_priv_obs = take(go2 ? 123 : 0);
+  L.go2_info = take(k.ninfo);
+  L.priv_obs = take(k.priv); L.f_priv_obs = take(k.priv);
   L.steps = take(1); L.truncation = take(1); L.episode_done = take(1); L.episode_metrics = take(2 + d.nmetrics);
   L.stats = take(4);
   L.rec = (o + 15) & ~15;
@@ -129,6 +136,136 @@ static Layout make_layout(const rsr_dims& d) {
 }
 
 extern "C" const char* rsr_last_error(void) { return g_err.c_str(); }
+
+// ---------------------------------------------------------------- rsr_model_create: what the kernels of a spec assume of a model
+// Each check returns null or why the model is refused (RSR_ERR_UNSUPPORTED); rsr_model_create runs them in the order of `checks`.
+namespace {
+template <class T>
+const T* field(const rsr_model& m, const char* name, int* count = nullptr) { return static_cast<const T*>(m.find(name, count)); }
+
+bool fits(const rsr_dims& d, const int* c2, const rsr::KernelSpec& k) {
+  return d.nq == k.nq && d.nv == k.nv && d.nu == k.nu && d.nbody == k.nb && d.njnt == k.nj && d.ngeom == k.ng && d.nsite == k.ns &&
+         d.npair == k.np && d.neq == k.neq && c2[0] == k.nf && c2[1] == k.nl && d.obs_dim == k.obs && d.nmetrics == k.nmet;
+}
+
+const char* check_joints(rsr_model& m, const rsr::KernelSpec&) {
+  return field<int>(m, "counts2")[3] > 1 ? "bodies with more than one joint are not built" : nullptr;
+}
+
+// geom slots: as many as the kernel's LDS image keeps, each a geom id, every pair geom among them (model.py: geom_slots)
+const char* check_geom_slots(rsr_model& m, const rsr::KernelSpec& k) {
+  int ns = 0, np1 = 0;
+  const int* gs = field<int>(m, "geom_slot_ids", &ns);
+  bool ok = gs && ns == k.nga;
+  for (int i = 0; ok && i < ns; ++i) ok = gs[i] >= 0 && gs[i] < k.ng && (k.nga != k.ng || gs[i] == i);
+  const int *pg1 = field<int>(m, "pair_geom1", &np1), *pg2 = field<int>(m, "pair_geom2");
+  for (int q = 0; ok && q < np1; ++q) {
+    bool f1 = false, f2 = false;
+    for (int i = 0; i < ns; ++i) { f1 |= gs[i] == pg1[q]; f2 |= gs[i] == pg2[q]; }
+    ok = f1 && f2;
+  }
+  return ok ? nullptr : "geom_slot_ids do not match the kernel's geom slots (Dims::NGA) or miss a pair geom";
+}
+
+// the Airbot kernels factor one kinematic tree per DPP row (Dims::ROWTREE): dof ranges [0, TREE1), [TREE1, TREE2), [TREE2, nv)
+// must be separate trees -- no body chain and no equality constraint may straddle them
+const char* check_trees(rsr_model& m, const rsr::KernelSpec& k) {
+  if (k.tree1 <= 0) return nullptr;
+  auto trees_of = [&](unsigned mask) {
+    const unsigned m0 = (1u << k.tree1) - 1u, m01 = (1u << k.tree2) - 1u;
+    return ((mask & m0) != 0u) + ((mask & (m01 & ~m0)) != 0u) + ((mask & ~m01) != 0u);
+  };
+  int nbm = 0, neq = 0;
+  const unsigned* bm = field<unsigned>(m, "body_dofmask", &nbm);
+  bool ok = bm != nullptr;
+  for (int b = 0; ok && b < nbm; ++b) ok = trees_of(bm[b]) <= 1;
+  const int *e1 = field<int>(m, "eq_obj1id", &neq), *e2 = field<int>(m, "eq_obj2id"), *jd = field<int>(m, "jnt_dofadr");
+  for (int q = 0; ok && e1 && e2 && jd && q < neq; ++q) {
+    const bool j1 = e1[q] >= 0 && e1[q] < k.nj, j2 = e2[q] >= 0 && e2[q] < k.nj;
+    if (j1 && j2) ok = trees_of((1u << jd[e1[q]]) | (1u << jd[e2[q]])) <= 1;
+  }
+  return ok ? nullptr : "the Airbot kernels need the arm and the free bodies as separate kinematic trees over fixed dof ranges";
+}
+
+// the Go2 kernels factor M and H in block-arrow form (Dims::ARROW): dofs 0..5 are the trunk, every further group of three dofs
+// is a leg, and no body chain and no contact pair may touch two legs
+const char* check_arrow(rsr_model& m, const rsr::KernelSpec& k) {
+  if (!k.arrow) return nullptr;
+  auto legs_of = [&](unsigned mask) {
+    int n = 0;
+    for (int l = 0; l < k.alegs; ++l) n += ((mask >> (k.ant + k.alegn * l)) & ((1u << k.alegn) - 1u)) != 0u;
+    return n;
+  };
+  int nbm = 0, npm = 0;
+  const unsigned* bm = field<unsigned>(m, "body_dofmask", &nbm);
+  const unsigned *pm1 = field<unsigned>(m, "pair_mask1", &npm), *pm2 = field<unsigned>(m, "pair_mask2");
+  bool ok = bm && pm1 && pm2;
+  for (int b = 0; ok && b < nbm; ++b) ok = legs_of(bm[b]) <= 1;
+  for (int q = 0; ok && q < npm; ++q) ok = legs_of(pm1[q] | pm2[q]) <= 1;
+  return ok ? nullptr : "the Go2 kernels need a trunk of 6 dofs carrying legs of 3 dofs that only couple through the trunk";
+}
+
+const char* check_condim(rsr_model& m, const rsr::KernelSpec& k) {
+  int npc = 0; const int* pc = field<int>(m, "pair_condim", &npc);
+  for (int i = 0; i < npc; ++i) if (pc[i] != k.condim) return "contact pairs must all have the condim the kernel is built for (Airbot 4, Go2 3)";
+  return nullptr;
+}
+const char* check_equality(rsr_model& m, const rsr::KernelSpec&) {
+  int nea = 0; const int* ea = field<int>(m, "eq_active0", &nea);
+  for (int i = 0; i < nea; ++i) if (!ea[i]) return "inactive equality constraints are not built";
+  return nullptr;
+}
+const char* check_integrator(rsr_model& m, const rsr::KernelSpec&) {
+  const int integrator = field<int>(m, "opt_integrator")[0];
+  return integrator != rsr::INT_IMPLICITFAST && integrator != rsr::INT_EULER ? "integrator" : nullptr;
+}
+
+// the kernels treat dofs [ISO0, ISO1) as decoupled from the rest: no chain, pair or equality may straddle the range
+const char* check_iso(rsr_model& m, const rsr::KernelSpec& k) {
+  if (k.iso1 <= k.iso0) return nullptr;
+  const unsigned iso = ((1u << k.iso1) - 1u) & ~((1u << k.iso0) - 1u);
+  auto straddles = [&](unsigned mask) { return (mask & iso) && (mask & ~iso); };
+  int nb = 0, np1 = 0, np2 = 0, ne1 = 0, ne2 = 0, nj = 0;
+  const unsigned* bm = field<unsigned>(m, "body_dofmask", &nb);
+  const unsigned *m1 = field<unsigned>(m, "pair_mask1", &np1), *m2 = field<unsigned>(m, "pair_mask2", &np2);
+  const int *e1 = field<int>(m, "eq_obj1id", &ne1), *e2 = field<int>(m, "eq_obj2id", &ne2), *jd = field<int>(m, "jnt_dofadr", &nj);
+  bool bad = !bm || !m1 || !m2 || np1 != np2 || !jd;
+  const unsigned low = (1u << k.iso0) - 1u;      // the trees before / after the range must be separate too (mass matrix blocks)
+  for (int i = 0; !bad && i < nb; ++i) bad = straddles(bm[i]) || ((bm[i] & low) && (bm[i] & ~low));
+  for (int i = 0; !bad && i < np1; ++i) bad = straddles(m1[i] | m2[i]);
+  for (int i = 0; !bad && e1 && e2 && i < ne1 && i < ne2; ++i) {
+    unsigned mk = (e1[i] >= 0 && e1[i] < nj ? 1u << jd[e1[i]] : 0u) | (e2[i] >= 0 && e2[i] < nj ? 1u << jd[e2[i]] : 0u);
+    bad = straddles(mk);
+  }
+  return bad ? "the kernel assumes the target body's dofs share no chain, contact pair or equality with other dofs" : nullptr;
+}
+
+// height-field pairs: kernels with Dims::HFIELD only, one field, spheres no wider than a grid cell; notes whether the model has any
+const char* check_hfield(rsr_model& m, const rsr::KernelSpec& k) {
+  int npk = 0, nh = 0, nsz = 0, nd = 0, ng2 = 0, ngs = 0;
+  const int* pk = field<int>(m, "pair_kind", &npk);
+  bool any_hf = false;
+  for (int i = 0; pk && i < npk; ++i) any_hf |= (pk[i] == rsr::PAIR_HFIELD_SPHERE);
+  m.has_hfield = any_hf;
+  if (!any_hf) return nullptr;
+  const int *hr = field<int>(m, "hfield_nrow", &nh), *hc = field<int>(m, "hfield_ncol");
+  const float* hs = field<float>(m, "hfield_size", &nsz);
+  m.find("hfield_data", &nd);
+  bool ok = k.hfield && hr && hc && hs && nh == 1 && nsz == 4 && hr[0] >= 3 && hc[0] >= 3 && nd == hr[0] * hc[0];
+  if (ok) {
+    const float cell = std::fmin(2.0f * hs[0] / (float)(hc[0] - 1), 2.0f * hs[1] / (float)(hr[0] - 1));
+    const int* g2 = field<int>(m, "pair_geom2", &ng2);
+    const float* gs = field<float>(m, "geom_size", &ngs);
+    for (int i = 0; i < npk; ++i)
+      if (pk[i] == rsr::PAIR_HFIELD_SPHERE && (i >= ng2 || g2[i] < 0 || 3 * g2[i] + 2 >= ngs || 2.0f * gs[3 * g2[i]] > cell)) ok = false;
+  }
+  return ok ? nullptr : "height-field pairs need the Go2 kernels, exactly one height field of at least 3x3 samples, and spheres no wider than a grid cell";
+}
+
+using Check = const char* (*)(rsr_model&, const rsr::KernelSpec&);
+constexpr Check checks[] = {check_joints, check_geom_slots, check_trees, check_arrow, check_condim,
+                            check_equality, check_integrator, check_iso, check_hfield};
+}  // namespace
 
 extern "C" int rsr_model_create(const void* blob, size_t nbytes, rsr_model** out) {
   if (!blob || !out || nbytes < 32) return fail(RSR_ERR_ARG, "rsr_model_create: null or short blob");
@@ -145,149 +282,38 @@ extern "C" int rsr_model_create(const void* blob, size_t nbytes, rsr_model** out
         return fail(RSR_ERR_ARG, "rsr_model_create: blob entry " + std::to_string(i) + " has no name terminator or points outside the blob");
     }
   }
-  rsr_model* m = new rsr_model();
+  auto m = std::make_unique<rsr_model>();
   m->blob.assign(static_cast<const char*>(blob), static_cast<const char*>(blob) + nbytes);
   int ndims = 0, nei = 0;
-  const int* dims = static_cast<const int*>(m->find("dims", &ndims));
-  const int* ei = static_cast<const int*>(m->find("env_int", &nei));
-  if (!dims || !ei || ndims < 9 || nei < 6) { delete m; return fail(RSR_ERR_ARG, "rsr_model_create: blob lacks dims/env_int"); }
+  const int* dims = field<int>(*m, "dims", &ndims);
+  const int* ei = field<int>(*m, "env_int", &nei);
+  if (!dims || !ei || ndims < 9 || nei < 6) return fail(RSR_ERR_ARG, "rsr_model_create: blob lacks dims/env_int");
   {  // fields read below or by fill_dmodel without a further check
     static const char* const need[] = {"counts2", "opt_integrator", "opt_timestep", "opt_gravity", "opt_tolerance", "opt_ls_tolerance", "opt_impratio",
                                        "stat_meaninertia", "opt_iterations", "opt_ls_iterations", "opt_disable_eulerdamp", "opt_disable_refsafe",
                                        "pair_condim", "pair_kind", "pair_geom1", "pair_geom2", "geom_size", "eq_active0", "lane_rec", "geom_slot_ids"};
     for (const char* f : need) {
       int cnt = 0;
-      if (!m->find(f, &cnt) || (cnt < 1 && std::strcmp(f, "pair_condim") && std::strcmp(f, "pair_kind") && std::strcmp(f, "pair_geom1") && std::strcmp(f, "pair_geom2") && std::strcmp(f, "eq_active0"))) {
-        delete m; return fail(RSR_ERR_ARG, std::string("rsr_model_create: blob lacks field ") + f);
-      }
+      if (!m->find(f, &cnt) || (cnt < 1 && std::strcmp(f, "pair_condim") && std::strcmp(f, "pair_kind") && std::strcmp(f, "pair_geom1") && std::strcmp(f, "pair_geom2") && std::strcmp(f, "eq_active0")))
+        return fail(RSR_ERR_ARG, std::string("rsr_model_create: blob lacks field ") + f);
     }
     int nc2 = 0, ng = 0; m->find("counts2", &nc2); m->find("opt_gravity", &ng);
-    if (nc2 < 4 || ng < 3) { delete m; return fail(RSR_ERR_ARG, "rsr_model_create: counts2 / opt_gravity too short"); }
+    if (nc2 < 4 || ng < 3) return fail(RSR_ERR_ARG, "rsr_model_create: counts2 / opt_gravity too short");
   }
   rsr_dims& d = m->dims;
   d.nq = dims[0]; d.nv = dims[1]; d.nu = dims[2]; d.nbody = dims[3]; d.njnt = dims[4]; d.ngeom = dims[5];
   d.nsite = dims[6]; d.neq = dims[7]; d.npair = dims[8];
   d.env_kind = ei[0]; d.n_frames = ei[1]; d.episode_length = ei[2]; d.obs_dim = ei[4]; d.nmetrics = ei[5];
-  const int* c2 = static_cast<const int*>(m->find("counts2"));
-  auto fits = [&](auto dims_tag) {
-    using C = decltype(dims_tag);
-    return d.nq == C::NQ && d.nv == C::NV && d.nu == C::NU && d.nbody == C::NB && d.njnt == C::NJ && d.ngeom == C::NG &&
-           d.nsite == C::NS && d.npair == C::NP && d.neq == C::NEQ && c2 && c2[0] == C::NF && c2[1] == C::NL &&
-           d.obs_dim == C::OBS && d.nmetrics == C::NMET;
-  };
-  bool ok = ((d.env_kind == rsr::ENV_CUBE || d.env_kind == rsr::ENV_AIRBOT_SF) && fits(rsr::CubeDims{})) ||
-            (d.env_kind == rsr::ENV_TSHAPE && fits(rsr::TShapeDims{})) || (d.env_kind == rsr::ENV_GO2 && fits(rsr::Go2Dims{})) ||
-            (d.env_kind == rsr::ENV_GO2_HANDSTAND && fits(rsr::HandDims{}));
-  const bool go2 = go2_family(d.env_kind);
-  const int want_condim = go2 ? 3 : 4;
-  if (!ok) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: model dims / env kind have no compiled kernel (built: Airbot cube, Airbot sf, Airbot T-shape, Go2 joystick, Go2 handstand / footstand)"); }
-  if (c2[3] > 1) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: bodies with more than one joint are not built"); }
-  {  // geom slots: as many as the kernel's LDS image keeps, each a geom id, every pair geom among them (model.py: geom_slots)
-    int ns = 0, np1 = 0; const int* gs = static_cast<const int*>(m->find("geom_slot_ids", &ns));
-    const int want = d.env_kind == rsr::ENV_GO2 ? rsr::Go2Dims::NGA : (d.env_kind == rsr::ENV_GO2_HANDSTAND ? rsr::HandDims::NGA : (d.env_kind == rsr::ENV_TSHAPE ? rsr::TShapeDims::NGA : rsr::CubeDims::NGA));
-    bool okg = gs && ns == want;
-    for (int i = 0; okg && i < ns; ++i) okg = gs[i] >= 0 && gs[i] < d.ngeom && (want != d.ngeom || gs[i] == i);
-    const int* pg1 = static_cast<const int*>(m->find("pair_geom1", &np1)); const int* pg2 = static_cast<const int*>(m->find("pair_geom2"));
-    for (int q = 0; okg && q < np1; ++q) {
-      bool f1 = false, f2 = false;
-      for (int i = 0; i < ns; ++i) { f1 |= gs[i] == pg1[q]; f2 |= gs[i] == pg2[q]; }
-      okg = f1 && f2;
-    }
-    if (!okg) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: geom_slot_ids do not match the kernel's geom slots (Dims::NGA) or miss a pair geom"); }
-  }
-  if (!go2) {
-    // the Airbot kernels factor one kinematic tree per DPP row (Dims::ROWTREE): dof ranges [0, TREE1), [TREE1, TREE2), [TREE2, nv)
-    // must be separate trees -- no body chain and no equality constraint may straddle them
-    const int t1 = d.env_kind == rsr::ENV_TSHAPE ? rsr::TShapeDims::TREE1 : rsr::CubeDims::TREE1;
-    const int t2 = d.env_kind == rsr::ENV_TSHAPE ? rsr::TShapeDims::TREE2 : rsr::CubeDims::TREE2;
-    auto trees_of = [&](unsigned mask) {
-      const unsigned m0 = (1u << t1) - 1u, m01 = (1u << t2) - 1u;
-      return ((mask & m0) != 0u) + ((mask & (m01 & ~m0)) != 0u) + ((mask & ~m01) != 0u);
-    };
-    int nbm = 0, neq = 0;
-    const unsigned* bm = static_cast<const unsigned*>(m->find("body_dofmask", &nbm));
-    bool okt = bm != nullptr;
-    for (int b = 0; okt && b < nbm; ++b) okt = trees_of(bm[b]) <= 1;
-    const int* e1 = static_cast<const int*>(m->find("eq_obj1id", &neq)); const int* e2 = static_cast<const int*>(m->find("eq_obj2id"));
-    const int* jd = static_cast<const int*>(m->find("jnt_dofadr"));
-    for (int q = 0; okt && e1 && e2 && jd && q < neq; ++q) {
-      const bool j1 = e1[q] >= 0 && e1[q] < d.njnt, j2 = e2[q] >= 0 && e2[q] < d.njnt;
-      if (j1 && j2) okt = trees_of((1u << jd[e1[q]]) | (1u << jd[e2[q]])) <= 1;
-    }
-    if (!okt) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: the Airbot kernels need the arm and the free bodies as separate kinematic trees over fixed dof ranges"); }
-  }
-  if (go2 && rsr::Go2Dims::ARROW) {
-    // the Go2 kernels factor M and H in block-arrow form (Dims::ARROW): dofs 0..5 are the trunk, every further group of three dofs
-    // is a leg, and no body chain and no contact pair may touch two legs
-    using G = rsr::Go2Dims;
-    auto legs_of = [](unsigned mask) { int n = 0; for (int l = 0; l < G::ALEGS; ++l) n += ((mask >> (G::ANT + G::ALEGN * l)) & 7u) != 0u; return n; };
-    int nbm = 0, npm = 0;
-    const unsigned* bm = static_cast<const unsigned*>(m->find("body_dofmask", &nbm));
-    const unsigned* pm1 = static_cast<const unsigned*>(m->find("pair_mask1", &npm)); const unsigned* pm2 = static_cast<const unsigned*>(m->find("pair_mask2"));
-    bool oka = d.nv == G::NV && bm && pm1 && pm2;
-    for (int b = 0; oka && b < nbm; ++b) oka = legs_of(bm[b]) <= 1;
-    for (int q = 0; oka && q < npm; ++q) oka = legs_of(pm1[q] | pm2[q]) <= 1;
-    if (!oka) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: the Go2 kernels need a trunk of 6 dofs carrying legs of 3 dofs that only couple through the trunk"); }
-  }
-  int npc = 0; const int* pc = static_cast<const int*>(m->find("pair_condim", &npc));
-  for (int i = 0; i < npc; ++i) if (pc[i] != want_condim) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: contact pairs must all have the condim the kernel is built for (Airbot 4, Go2 3)"); }
-  int nea = 0; const int* ea = static_cast<const int*>(m->find("eq_active0", &nea));
-  for (int i = 0; i < nea; ++i) if (!ea[i]) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: inactive equality constraints are not built"); }
-  if (static_cast<const int*>(m->find("opt_integrator"))[0] != rsr::INT_IMPLICITFAST &&
-      static_cast<const int*>(m->find("opt_integrator"))[0] != rsr::INT_EULER) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: integrator"); }
-  {  // the kernels treat dofs [ISO0, ISO1) as decoupled from the rest: no chain, pair or equality may straddle the range
-    const int iso0 = (d.env_kind == rsr::ENV_CUBE || d.env_kind == rsr::ENV_AIRBOT_SF) ? rsr::CubeDims::ISO0 : 0;
-    const int iso1 = (d.env_kind == rsr::ENV_CUBE || d.env_kind == rsr::ENV_AIRBOT_SF) ? rsr::CubeDims::ISO1 : 0;
-    if (iso1 > iso0) {
-      const unsigned iso = ((1u << iso1) - 1u) & ~((1u << iso0) - 1u);
-      auto straddles = [&](unsigned mask) { return (mask & iso) && (mask & ~iso); };
-      int nb = 0, np1 = 0, np2 = 0, ne1 = 0, ne2 = 0, nj = 0;
-      const unsigned* bm = static_cast<const unsigned*>(m->find("body_dofmask", &nb));
-      const unsigned* m1 = static_cast<const unsigned*>(m->find("pair_mask1", &np1));
-      const unsigned* m2 = static_cast<const unsigned*>(m->find("pair_mask2", &np2));
-      const int* e1 = static_cast<const int*>(m->find("eq_obj1id", &ne1));
-      const int* e2 = static_cast<const int*>(m->find("eq_obj2id", &ne2));
-      const int* jd = static_cast<const int*>(m->find("jnt_dofadr", &nj));
-      bool bad = !bm || !m1 || !m2 || np1 != np2 || !jd;
-      const unsigned low = (1u << iso0) - 1u;      // the trees before / after the range must be separate too (mass matrix blocks)
-      for (int i = 0; !bad && i < nb; ++i) bad = straddles(bm[i]) || ((bm[i] & low) && (bm[i] & ~low));
-      for (int i = 0; !bad && i < np1; ++i) bad = straddles(m1[i] | m2[i]);
-      for (int i = 0; !bad && e1 && e2 && i < ne1 && i < ne2; ++i) {
-        unsigned mk = (e1[i] >= 0 && e1[i] < nj ? 1u << jd[e1[i]] : 0u) | (e2[i] >= 0 && e2[i] < nj ? 1u << jd[e2[i]] : 0u);
-        bad = straddles(mk);
-      }
-      if (bad) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: the kernel assumes the target body's dofs share no chain, contact pair or equality with other dofs"); }
-    }
-  }
-  {  // height-field pairs: Go2 kernels only, one field, spheres no wider than a grid cell
-    int npk = 0, nh = 0, nsz = 0; const int* pk = static_cast<const int*>(m->find("pair_kind", &npk));
-    bool any_hf = false;
-    for (int i = 0; pk && i < npk; ++i) any_hf |= (pk[i] == rsr::PAIR_HFIELD_SPHERE);
-    m->has_hfield = any_hf;
-    if (any_hf) {
-      const int* hr = static_cast<const int*>(m->find("hfield_nrow", &nh));
-      const int* hc = static_cast<const int*>(m->find("hfield_ncol"));
-      const float* hs = static_cast<const float*>(m->find("hfield_size", &nsz));
-      int nd = 0; m->find("hfield_data", &nd);
-      bool okh = d.env_kind == rsr::ENV_GO2 && rsr::Go2Dims::HFIELD && hr && hc && hs && nh == 1 && nsz == 4 && hr[0] >= 3 && hc[0] >= 3 && nd == hr[0] * hc[0];
-      if (okh) {
-        const float cell = std::fmin(2.0f * hs[0] / (float)(hc[0] - 1), 2.0f * hs[1] / (float)(hr[0] - 1));
-        const int* g2 = static_cast<const int*>(m->find("pair_geom2"));
-        const float* gs = static_cast<const float*>(m->find("geom_size"));
-        int ng2 = 0, ngs = 0; m->find("pair_geom2", &ng2); m->find("geom_size", &ngs);
-        for (int i = 0; i < npk; ++i)
-          if (pk[i] == rsr::PAIR_HFIELD_SPHERE && (i >= ng2 || g2[i] < 0 || 3 * g2[i] + 2 >= ngs || 2.0f * gs[3 * g2[i]] > cell)) okh = false;
-      }
-      if (!okh) { delete m; return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: height-field pairs need the Go2 kernels, exactly one height field of at least 3x3 samples, and spheres no wider than a grid cell"); }
-    }
-  }
-  if (d.env_kind == rsr::ENV_GO2) { using C = rsr::Go2Dims; d.ncon_max = C::NCON; d.nefc_max = C::NEFC; d.lds_bytes = (int32_t)sizeof(rsr::Smem<C>); }
-  else if (d.env_kind == rsr::ENV_GO2_HANDSTAND) { using C = rsr::HandDims; d.ncon_max = C::NCON; d.nefc_max = C::NEFC; d.lds_bytes = (int32_t)sizeof(rsr::Smem<C>); }
-  else if (d.env_kind == rsr::ENV_TSHAPE) { using C = rsr::TShapeDims; d.ncon_max = C::NCON; d.nefc_max = C::NEFC; d.lds_bytes = (int32_t)sizeof(rsr::Smem<C>); }
-  else { using C = rsr::CubeDims; d.ncon_max = C::NCON; d.nefc_max = C::NEFC; d.lds_bytes = (int32_t)sizeof(rsr::Smem<C>); }
-  m->layout = make_layout(d);
+  const rsr::KernelSpec* k = rsr::kernel_spec(d.env_kind);
+  if (!k || !fits(d, field<int>(*m, "counts2"), *k))
+    return fail(RSR_ERR_UNSUPPORTED, "rsr_model_create: model dims / env kind have no compiled kernel (built: Airbot cube, Airbot sf, Airbot T-shape, Go2 joystick, Go2 handstand / footstand)");
+  for (Check check : checks)
+    if (const char* why = check(*m, *k)) return fail(RSR_ERR_UNSUPPORTED, std::string("rsr_model_create: ") + why);
+  m->spec = k;
+  d.ncon_max = k->ncon; d.nefc_max = k->nefc; d.lds_bytes = k->lds_bytes;
+  m->layout = make_layout(d, *k);
   d.rec_floats = m->layout.rec;
-  *out = m;
+  *out = m.release();
   return RSR_OK;
 }
 
@@ -296,7 +322,7 @@ extern "C" int rsr_model_dims(const rsr_model* m, rsr_dims* out) {
   *out = m->dims;
   return RSR_OK;
 }
-extern "C" void rsr_model_destroy(rsr_model* m) { delete m; }
+extern "C" void rsr_model_destroy(rsr_model* model) { delete model; }
 
 static int fill_dmodel(const rsr_model* m, const char* dbase, DModel& dm) {
 #define P(T, name) { ptrdiff_t o = m->offset_of(#name); if (o < 0) return fail(RSR_ERR_ARG, "blob lacks field " #name); dm.name = (decltype(dm.name))(dbase + o); }
@@ -322,7 +348,7 @@ static int fill_dmodel(const rsr_model* m, const char* dbase, DModel& dm) {
   { int nrec = 0; m->find("lane_rec", &nrec); if (nrec != rsr::LQ_COUNT * 64 * 4) return fail(RSR_ERR_ARG, "blob field lane_rec has the wrong size (model.py lane_records vs enum LaneQuad)"); }
   P(float, hfield_size) P(float, hfield_data) P(int, hfield_nrow) P(int, hfield_ncol)
   P(int, env_ids) P(float, env_action_scale) P(float, env_ctrl_lo) P(float, env_ctrl_hi) P(float, env_reset) P(float, env_reward)
-  if (go2_family(m->dims.env_kind)) {
+  if (go2_family(m)) {
     P(float, env_go2f) P(float, env_go2_scales) P(float, env_go2_home) P(float, env_go2_soft) P(int, env_go2i)
   } else { dm.env_go2f = dm.env_go2_scales = dm.env_go2_home = dm.env_go2_soft = nullptr; dm.env_go2i = nullptr; }
 #undef P
@@ -379,7 +405,7 @@ extern "C" int rsr_batch_create(const rsr_model* m, int num_envs, int hip_device
   b->prio_policy = -1; b->prio_slots = 1;
   b->action_repeat = 1; b->dmodel_plain = nullptr; b->racc = nullptr;
   const int step_per_cu = launch(b, rsr::OP_STEP_OCCUPANCY, launch_args(b, nullptr));    // resident workgroups per CU of the step kernel
-  if (go2_family(m->dims.env_kind)) {
+  if (go2_family(m)) {
     int per_cu = step_per_cu;
     hipDeviceProp_t prop;
     if (per_cu <= 0 || hipGetDeviceProperties(&prop, hip_device) != hipSuccess) { per_cu = 16; prop.multiProcessorCount = 256; }
@@ -438,7 +464,7 @@ extern "C" int rsr_batch_set_dr_field(rsr_batch* b, int dr_field, const float* d
     case RSR_DR_DOF_DAMPING: b->dr_damp = dev_values; return RSR_OK;
     case RSR_DR_DOF_FRICTIONLOSS: b->dr_floss = dev_values; return RSR_OK;
     case RSR_DR_BODY_IPOS: case RSR_DR_QPOS0: case RSR_DR_DOF_ARMATURE: case RSR_DR_ACTUATOR_GAINPRM: case RSR_DR_ACTUATOR_BIASPRM:
-      if (!go2_family(b->model->dims.env_kind))
+      if (!go2_family(b->model))
         return fail(RSR_ERR_UNSUPPORTED, "rsr_batch_set_dr_field: this field is per-env only in the Go2 kernels (randomize.py); the Airbot kernels take the four fields of rsr_batch_set_dr");
       b->dr_ex[dr_field - RSR_DR_BODY_IPOS] = dev_values;
       return RSR_OK;
@@ -533,12 +559,12 @@ rsr::Launch launch_args(rsr_batch* b, void* hip_stream) {
 }
 
 int launch(const rsr_batch* b, int op, const rsr::Launch& x) {
-  switch (rsr::family_of(b->model->dims.env_kind)) {
+  switch (b->model->spec->family) {
     case rsr::FAMILY_CUBE: return rsr::launch_cube(op, x);
     case rsr::FAMILY_TSHAPE: return rsr::launch_tshape(op, x);
     case rsr::FAMILY_GO2: return rsr::launch_go2(op, x);
-    default: return 0;
   }
+  return 0;
 }
 
 extern "C" int rsr_reset(rsr_batch* b, const uint32_t* keys, void* hip_stream) {
@@ -560,7 +586,7 @@ extern "C" int rsr_step(rsr_batch* b, const float* action, void* hip_stream) {
   const int repeat = b->action_repeat;
   const Layout& LY = b->model->layout;
   const rsr_dims& dd = b->model->dims;
-  const bool go2 = go2_family(dd.env_kind);
+  const bool go2 = go2_family(b->model);
   if (repeat > 1) x.dm = b->dmodel_plain;         // plain env.step, the wrappers around the repeats
   if (repeat > 1)
     hipLaunchKernelGGL(rsr::repeat_pre_kernel, dim3(b->n), dim3(64), 0, st, b->state, LY, b->n, b->dm.wrap_flags, b->racc);
@@ -586,7 +612,7 @@ extern "C" int rsr_step(rsr_batch* b, const float* action, void* hip_stream) {
   }
   if (repeat > 1)
     hipLaunchKernelGGL(rsr::repeat_post_kernel, dim3(b->n), dim3(64), 0, st, b->state, LY, b->n, b->dm.wrap_flags, repeat, b->dm.episode_length,
-                       dd.nmetrics, dd.obs_dim, go2 ? rsr::GO2_PRIV : 0, dd.env_kind == rsr::ENV_GO2 ? (int)rsr::G2_XFRC : -1, b->racc);
+                       dd.nmetrics, dd.obs_dim, b->model->spec->priv, dd.env_kind == rsr::ENV_GO2 ? (int)rsr::G2_XFRC : -1, b->racc);
   HIPCHK(hipGetLastError());
   if (b->timing) b->launches++;
   return RSR_OK;
@@ -596,48 +622,20 @@ extern "C" int rsr_view(rsr_batch* b, int field_id, void** dev_ptr, int64_t shap
   if (!b || !dev_ptr || !shape || !stride) return fail(RSR_ERR_ARG, "rsr_view: null argument");
   const Layout& L = b->model->layout;
   const rsr_dims& d = b->model->dims;
-  int off = -1, w = 0;
-  switch (field_id) {
-    case RSR_F_QPOS: off = L.qpos; w = d.nq; break;
-    case RSR_F_QVEL: off = L.qvel; w = d.nv; break;
-    case RSR_F_CTRL: off = L.ctrl; w = d.nu; break;
-    case RSR_F_QACC_WARMSTART: off = L.warm; w = d.nv; break;
-    case RSR_F_TIME: off = L.time; w = 1; break;
-    case RSR_F_XPOS: off = L.xpos; w = d.nbody * 3; break;
-    case RSR_F_SITE_XPOS: off = L.site_xpos; w = d.nsite * 3; break;
-    case RSR_F_OBS: off = L.obs; w = d.obs_dim; break;
-    case RSR_F_REWARD: off = L.reward; w = 1; break;
-    case RSR_F_DONE: off = L.done; w = 1; break;
-    case RSR_F_METRICS: off = L.metrics; w = d.nmetrics; break;
-    case RSR_F_INFO_TARGET_POS: off = L.target_pos; w = 3; break;
-    case RSR_F_INFO_NEW_CUBE_POS: off = L.new_cube_pos; w = 2; break;
-    case RSR_F_INFO_SITE_POS: off = L.site_pos; w = 3; break;
-    case RSR_F_INFO_CUBE_POS: off = L.cube_pos; w = 3; break;
-    case RSR_F_INFO_LAST_ACTION: off = L.last_action; w = 1; break;
-    case RSR_F_INFO_TARGET_BASE_POS: off = L.target_base_pos; w = 3; break;
-    case RSR_F_INFO_TARGET_VERTICAL_POS: off = L.target_vertical_pos; w = 3; break;
-    case RSR_F_INFO_TARGET_W: off = L.target_w; w = 1; break;
-    case RSR_F_INFO_NEW_T_POS: off = L.new_T_pos; w = 2; break;
-    case RSR_F_INFO_T_POS: off = L.T_pos; w = 3; break;
-    case RSR_F_INFO_XITA: off = L.xita; w = 1; break;
-    case RSR_F_INFO_GO2: off = L.go2_info; w = go2_family(d.env_kind) ? 144 : 0; break;
-    case RSR_F_INFO_STEPS: off = L.steps; w = 1; break;
-    case RSR_F_INFO_TRUNCATION: off = L.truncation; w = 1; break;
-    case RSR_F_INFO_EPISODE_DONE: off = L.episode_done; w = 1; break;
-    case RSR_F_INFO_EPISODE_METRICS: off = L.episode_metrics; w = 2 + d.nmetrics; break;
-    case RSR_F_FIRST_QPOS: off = L.f_qpos; w = d.nq; break;
-    case RSR_F_FIRST_QVEL: off = L.f_qvel; w = d.nv; break;
-    case RSR_F_FIRST_CTRL: off = L.f_ctrl; w = d.nu; break;
-    case RSR_F_FIRST_WARMSTART: off = L.f_warm; w = d.nv; break;
-    case RSR_F_FIRST_TIME: off = L.f_time; w = 1; break;
-    case RSR_F_FIRST_XPOS: off = L.f_xpos; w = d.nbody * 3; break;
-    case RSR_F_FIRST_SITE_XPOS: off = L.f_site_xpos; w = d.nsite * 3; break;
-    case RSR_F_FIRST_OBS: off = L.f_obs; w = d.obs_dim; break;
-    case RSR_F_PRIVILEGED_OBS: off = L.priv_obs; w = go2_family(d.env_kind) ? 123 : 0; break;
-    case RSR_F_FIRST_PRIVILEGED_OBS: off = L.f_priv_obs; w = go2_family(d.env_kind) ? 123 : 0; break;
-    case RSR_F_STATS: off = L.stats; w = 4; break;
-    default: return fail(RSR_ERR_ARG, "rsr_view: unknown field id");
-  }
+  const rsr::KernelSpec& k = *b->model->spec;
+  const int view[][2] = {      // {offset, width} of every rsr_field, in the enum's order
+      {L.qpos, d.nq}, {L.qvel, d.nv}, {L.ctrl, d.nu}, {L.warm, d.nv}, {L.time, 1}, {L.xpos, d.nbody * 3}, {L.site_xpos, d.nsite * 3},
+      {L.obs, d.obs_dim}, {L.reward, 1}, {L.done, 1}, {L.metrics, d.nmetrics},
+      {L.target_pos, 3}, {L.new_cube_pos, 2}, {L.site_pos, 3}, {L.cube_pos, 3}, {L.last_action, 1},
+      {L.target_base_pos, 3}, {L.target_vertical_pos, 3}, {L.target_w, 1}, {L.new_T_pos, 2}, {L.T_pos, 3}, {L.xita, 1},
+      {L.go2_info, k.ninfo},
+      {L.steps, 1}, {L.truncation, 1}, {L.episode_done, 1}, {L.episode_metrics, 2 + d.nmetrics},
+      {L.f_qpos, d.nq}, {L.f_qvel, d.nv}, {L.f_ctrl, d.nu}, {L.f_warm, d.nv}, {L.f_time, 1},
+      {L.f_xpos, d.nbody * 3}, {L.f_site_xpos, d.nsite * 3}, {L.f_obs, d.obs_dim},
+      {L.priv_obs, k.priv}, {L.f_priv_obs, k.priv}, {L.stats, 4}};
+  static_assert(sizeof(view) / sizeof(view[0]) == RSR_F_COUNT, "one entry per rsr_field");
+  if (field_id < 0 || field_id >= RSR_F_COUNT) return fail(RSR_ERR_ARG, "rsr_view: unknown field id");
+  const int off = view[field_id][0], w = view[field_id][1];
   *dev_ptr = b->state + off;
   shape[0] = b->n; shape[1] = w;
   stride[0] = L.rec; stride[1] = 1;

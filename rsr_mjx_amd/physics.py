@@ -63,12 +63,7 @@ class Physics:
         # the physics handle owns the side buffer of the physics outputs
         self._h = C.c_void_p()
         _lib.check(_lib.lib().rsr_physics_create(env._batch, C.byref(self._h)))
-        side = {}
-        for fid, name in enumerate(_lib.PHYS_FIELDS):
-            ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
-            _lib.check(_lib.lib().rsr_physics_view(self._h, fid, C.byref(ptr), shape, stride))
-            side[name] = _view(ptr, shape, stride, self.device)
-        self._side = side
+        side = self._side = {name: self._fetch("rsr_physics_view", fid) for fid, name in enumerate(_lib.PHYS_FIELDS)}
         self.qacc = side["qacc"]
         self.actuator_force = side["actuator_force"]
         self.xquat = side["xquat"].unflatten(1, (d.nbody, 4))
@@ -81,6 +76,12 @@ class Physics:
         self._dyn: Optional[Dict[str, Any]] = None
         if sensors is not None:
             self.set_sensors(sensors)
+
+    def _fetch(self, view_fn: str, fid: int):
+        """field `fid` of one of the library's three *_view entry points, as a tensor on the handle's memory"""
+        ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
+        _lib.check(getattr(_lib.lib(), view_fn)(self._h, fid, C.byref(ptr), shape, stride))
+        return _view(ptr, shape, stride, self.device)
 
     def __del__(self):
         try:
@@ -119,10 +120,7 @@ class Physics:
         table, where = _sensors.sensor_table(self.env.sys, spec, self._accel_site())
         _lib.check(_lib.lib().rsr_physics_set_sensors(self._h, table.ctypes.data_as(C.c_void_p) if len(table) else None, len(table)))
         self._sensor_adr = where
-        ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
-        _lib.check(_lib.lib().rsr_physics_view(self._h, _lib.PHYS_FIELDS.index("sensordata"), C.byref(ptr), shape, stride))
-        self.sensordata = _view(ptr, shape, stride, self.device)
-        self._side["sensordata"] = self.sensordata
+        self.sensordata = self._side["sensordata"] = self._fetch("rsr_physics_view", _lib.PHYS_FIELDS.index("sensordata"))
 
     @property
     def nsensordata(self) -> int:
@@ -168,11 +166,7 @@ class Physics:
             vals[name] = t
         if self.xfrc_applied is None:
             _lib.check(_lib.lib().rsr_physics_set_applied(self._h, 1))
-            views = []
-            for fid in range(len(_lib.APPLIED_FIELDS)):
-                ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
-                _lib.check(_lib.lib().rsr_physics_applied_view(self._h, fid, C.byref(ptr), shape, stride))
-                views.append(_view(ptr, shape, stride, self.device))
+            views = [self._fetch("rsr_physics_applied_view", fid) for fid in range(len(_lib.APPLIED_FIELDS))]
             self.xfrc_applied = views[0].unflatten(1, (d.nbody, 6))
             self.qfrc_applied = views[1]
         if k == 0:
@@ -192,11 +186,8 @@ class Physics:
     def _dyn_views(self) -> Dict[str, Any]:
         if self._dyn is None:
             import torch
-            d, dyn = self.dims, {}
-            for fid, name in enumerate(_lib.DYNAMICS_FIELDS):
-                ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
-                _lib.check(_lib.lib().rsr_physics_dynamics_view(self._h, fid, C.byref(ptr), shape, stride))
-                dyn[name] = _view(ptr, shape, stride, self.device)
+            d = self.dims
+            dyn = {name: self._fetch("rsr_physics_dynamics_view", fid) for fid, name in enumerate(_lib.DYNAMICS_FIELDS)}
             k = dyn["jac_site_xpos"].shape[1] // 3
             jac = dyn["jac"].unflatten(1, (k, 6, d.nv)) if k else torch.empty((self.num_envs, 0, 6, d.nv), dtype=torch.float32, device=self.device)
             self._dyn = dict(qM=dyn["qM"].unflatten(1, (d.nv, d.nv)), qfrc_bias=dyn["qfrc_bias"], qfrc_passive=dyn["qfrc_passive"],

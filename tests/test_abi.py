@@ -151,3 +151,137 @@ def test_airbot_model_create_checks_the_tree_ranges(lib, cube_model):
     bm[-1] = int(bm[-1]) | 1                                      # the last body's chain also runs through the arm's first dof
     bad["body_dofmask"] = bm
     assert create(bad) == -2 and b"trees" in lib.rsr_last_error()
+
+
+# ---------------------------------------------------------------- rsr_model_create: every refusal, and what it accepts
+# rsr_dims of every shipped model (episode_length 1000), field for field: nq nv nu nbody njnt ngeom nsite neq npair obs_dim nmetrics
+# n_frames episode_length env_kind rec_floats ncon_max nefc_max lds_bytes
+SHIPPED_DIMS = {
+    "cube": (22, 20, 5, 14, 10, 23, 1, 1, 45, 23, 3, 4, 1000, 0, 320, 24, 161, 16384),
+    "sf": (22, 20, 5, 14, 10, 23, 1, 1, 45, 23, 3, 4, 1000, 2, 320, 24, 161, 16384),
+    "tshape": (15, 14, 5, 14, 9, 25, 3, 1, 60, 16, 5, 4, 1000, 1, 288, 32, 209, 18944),
+    "go2_flat": (19, 18, 12, 14, 13, 39, 6, 0, 4, 48, 22, 5, 1000, 3, 832, 4, 40, 10032),
+    "go2_rough": (19, 18, 12, 14, 13, 39, 6, 0, 4, 48, 22, 5, 1000, 3, 832, 4, 40, 10032),
+    "handstand": (19, 18, 12, 14, 13, 44, 6, 0, 30, 45, 11, 5, 1000, 4, 800, 12, 72, 13600),
+}
+PAIR_HFIELD_SPHERE = 3          # rsr_device.hpp
+
+
+@pytest.fixture(scope="module")
+def shipped(cube_model, sf_model, tshape_model):
+    """The blob fields of every shipped model, as the env definitions pack them (config.*_env_fields)."""
+    from rsr_mjx_amd.envs import config, go2
+    from rsr_mjx_amd.model import model_fields
+    out = {}
+    for name, m, fn in (("cube", cube_model, config.cube_env_fields), ("sf", sf_model, config.sf_env_fields),
+                        ("tshape", tshape_model, config.tshape_env_fields)):
+        out[name] = dict(model_fields(m)); out[name].update(fn(m, 1000, True))
+    for name, env_name in (("go2_flat", "Go2JoystickFlatTerrain"), ("go2_rough", "Go2JoystickRoughTerrain"), ("handstand", "Go2Handstand")):
+        env = go2.load(env_name)
+        out[name] = dict(model_fields(env.sys)); out[name].update(env._fields_fn(env.sys, 1000, True))
+    return out
+
+
+def _create(lib, fields):
+    """(return code, message) of rsr_model_create on the packed fields; a created model is destroyed."""
+    from rsr_mjx_amd.model import pack_blob
+    blob, h = pack_blob(fields), C.c_void_p()
+    rc = lib.rsr_model_create(C.create_string_buffer(blob, len(blob)), len(blob), C.byref(h))
+    if rc == 0:
+        lib.rsr_model_destroy(h)
+        return 0, b""
+    return rc, lib.rsr_last_error()
+
+
+def _with(fields, **changes):
+    """A copy of `fields` with the given entries replaced: name=array, or name=(index, value) for one element."""
+    import numpy as np
+    out = dict(fields)
+    for name, v in changes.items():
+        if isinstance(v, tuple):
+            a = np.array(fields[name]).copy(); a.reshape(-1)[v[0]] = v[1]; v = a
+        out[name] = v
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(SHIPPED_DIMS))
+def test_model_create_accepts_every_shipped_model_and_reports_its_dims(lib, shipped, name):
+    from rsr_mjx_amd import _lib
+    from rsr_mjx_amd.model import pack_blob
+    blob, h = pack_blob(shipped[name]), C.c_void_p()
+    _lib.check(lib.rsr_model_create(C.create_string_buffer(blob, len(blob)), len(blob), C.byref(h)))
+    d = _lib.Dims()
+    _lib.check(lib.rsr_model_dims(h, C.byref(d)))
+    lib.rsr_model_destroy(h)
+    got = tuple(getattr(d, n) for n, _ in _lib.Dims._fields_)
+    print(name, got)
+    assert got == SHIPPED_DIMS[name]
+
+
+def _refusals(shipped):
+    """(id, fields, return code, distinctive part of the message), one per refusal of rsr_model_create after the directory checks."""
+    import numpy as np
+    cube, tshape, flat, rough, hand = (shipped[k] for k in ("cube", "tshape", "go2_flat", "go2_rough", "handstand"))
+    legs = lambda f, name, i: (i, int(np.asarray(f[name]).reshape(-1)[i]) | (7 << 6) | (7 << 9))       # the dofs of two legs
+    rough_foot = int(np.asarray(rough["pair_geom2"])[0])
+    wide = np.array(rough["geom_size"], dtype=np.float64).copy(); wide.reshape(-1, 3)[rough_foot, 0] = 0.2   # cell: 20 m / 255
+    return [
+        ("dims_short", _with(cube, dims=np.asarray(cube["dims"])[:8]), -1, b"lacks dims/env_int"),
+        ("counts2_short", _with(cube, counts2=np.asarray(cube["counts2"])[:3]), -1, b"counts2 / opt_gravity too short"),
+        ("no_kernel_nv", _with(cube, dims=(1, 19)), -2, b"no compiled kernel"),
+        ("no_kernel_env_kind", _with(cube, env_int=(0, 9)), -2, b"no compiled kernel"),
+        ("no_kernel_cube_dims_as_tshape", _with(cube, env_int=(0, 1)), -2, b"no compiled kernel"),
+        ("no_kernel_nfric", _with(flat, counts2=(0, 11)), -2, b"no compiled kernel"),
+        ("no_kernel_obs_dim", _with(hand, env_int=(4, 48)), -2, b"no compiled kernel"),
+        ("two_joints_per_body", _with(cube, counts2=(3, 2)), -2, b"more than one joint"),
+        ("slots_short", _with(cube, geom_slot_ids=np.asarray(cube["geom_slot_ids"])[:-1]), -2, b"geom_slot_ids"),
+        ("slots_permuted", _with(cube, geom_slot_ids=np.asarray(cube["geom_slot_ids"])[::-1].copy()), -2, b"geom_slot_ids"),
+        ("slots_out_of_range", _with(tshape, geom_slot_ids=(3, 25)), -2, b"geom_slot_ids"),
+        ("slots_count_handstand", _with(hand, geom_slot_ids=np.asarray(hand["geom_slot_ids"])[:5]), -2, b"geom_slot_ids"),
+        ("slots_miss_pair_geom", _with(flat, geom_slot_ids=(1, 13)), -2, b"miss a pair geom"),
+        ("trees_body_cube", _with(cube, body_dofmask=(-1, int(np.asarray(cube["body_dofmask"])[-1]) | 1)), -2, b"separate kinematic trees"),
+        ("trees_body_tshape", _with(tshape, body_dofmask=(-1, int(np.asarray(tshape["body_dofmask"])[-1]) | 1)), -2, b"separate kinematic trees"),
+        ("arrow_pair_go2", _with(flat, pair_mask1=legs(flat, "pair_mask1", 0)), -2, b"legs of 3 dofs"),
+        ("arrow_body_go2", _with(rough, body_dofmask=legs(rough, "body_dofmask", -1)), -2, b"legs of 3 dofs"),
+        ("arrow_body_handstand", _with(hand, body_dofmask=legs(hand, "body_dofmask", -1)), -2, b"legs of 3 dofs"),
+        ("condim_3_on_cube", _with(cube, pair_condim=(7, 3)), -2, b"condim the kernel is built for"),
+        ("condim_3_on_tshape", _with(tshape, pair_condim=(0, 3)), -2, b"condim the kernel is built for"),
+        ("condim_4_on_go2", _with(flat, pair_condim=(2, 4)), -2, b"condim the kernel is built for"),
+        ("condim_4_on_handstand", _with(hand, pair_condim=(29, 4)), -2, b"condim the kernel is built for"),
+        ("equality_inactive", _with(cube, eq_active0=(0, 0)), -2, b"inactive equality"),
+        ("integrator", _with(cube, opt_integrator=(0, 7)), -2, b"rsr_model_create: integrator"),
+        ("integrator_go2", _with(flat, opt_integrator=(0, 7)), -2, b"rsr_model_create: integrator"),
+        ("iso_pair", _with(cube, pair_mask1=(0, 1 | (1 << 8))), -2, b"target body's dofs"),
+        ("hfield_pair_on_cube", _with(cube, pair_kind=(0, PAIR_HFIELD_SPHERE)), -2, b"height-field pairs need the Go2 kernels"),
+        ("hfield_pair_on_handstand", _with(hand, pair_kind=(8, PAIR_HFIELD_SPHERE)), -2, b"height-field pairs need the Go2 kernels"),
+        ("hfield_without_field", _with(flat, pair_kind=(0, PAIR_HFIELD_SPHERE)), -2, b"height-field pairs need the Go2 kernels"),
+        ("hfield_two_rows", _with(rough, hfield_nrow=(0, 2)), -2, b"height-field pairs need the Go2 kernels"),
+        ("hfield_wide_sphere", _with(rough, geom_size=wide), -2, b"height-field pairs need the Go2 kernels"),
+        # two defects at once: the checks run in a fixed order and the first one to fail speaks
+        ("order_trees_before_condim", _with(cube, pair_condim=(0, 3), body_dofmask=(-1, int(np.asarray(cube["body_dofmask"])[-1]) | 1)), -2, b"separate kinematic trees"),
+        ("order_slots_before_arrow", _with(flat, geom_slot_ids=(1, 13), pair_mask1=legs(flat, "pair_mask1", 0)), -2, b"miss a pair geom"),
+        ("order_condim_before_integrator", _with(flat, pair_condim=(2, 4), opt_integrator=(0, 7)), -2, b"condim the kernel is built for"),
+        ("order_equality_before_iso", _with(cube, eq_active0=(0, 0), pair_mask1=(0, 1 | (1 << 8))), -2, b"inactive equality"),
+        ("order_iso_before_hfield", _with(cube, pair_mask1=(0, 1 | (1 << 8)), pair_kind=(0, PAIR_HFIELD_SPHERE)), -2, b"target body's dofs"),
+    ]
+
+
+REFUSAL_IDS = ["dims_short", "counts2_short", "no_kernel_nv", "no_kernel_env_kind", "no_kernel_cube_dims_as_tshape", "no_kernel_nfric",
+               "no_kernel_obs_dim", "two_joints_per_body", "slots_short", "slots_permuted", "slots_out_of_range", "slots_count_handstand",
+               "slots_miss_pair_geom", "trees_body_cube", "trees_body_tshape", "arrow_pair_go2", "arrow_body_go2", "arrow_body_handstand",
+               "condim_3_on_cube", "condim_3_on_tshape", "condim_4_on_go2", "condim_4_on_handstand", "equality_inactive", "integrator",
+               "integrator_go2", "iso_pair", "hfield_pair_on_cube", "hfield_pair_on_handstand", "hfield_without_field", "hfield_two_rows",
+               "hfield_wide_sphere", "order_trees_before_condim", "order_slots_before_arrow", "order_condim_before_integrator",
+               "order_equality_before_iso", "order_iso_before_hfield"]
+
+
+@pytest.mark.parametrize("case", REFUSAL_IDS)
+def test_model_create_refusals(lib, shipped, case):
+    """Every refusal of rsr_model_create that a packed blob can reach on a host without a GPU: the return code and a distinctive
+    part of the message.  The `order_*` cases carry two defects and pin which check speaks first."""
+    table = {c[0]: c for c in _refusals(shipped)}
+    assert sorted(table) == sorted(REFUSAL_IDS)
+    _, fields, want_rc, want_msg = table[case]
+    rc, msg = _create(lib, fields)
+    print(case, rc, msg.decode())
+    assert rc == want_rc and want_msg in msg, (rc, msg)

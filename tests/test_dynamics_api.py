@@ -75,15 +75,29 @@ def test_argument_checks_come_before_device_work():
     assert "hipFree(p->dyn)" in destroy and "hipFree(p->jac_sites)" in destroy
 
 
-def test_the_dynamics_op_stays_clear_of_the_env_sources():
-    """The op and its arguments live in the physics layer: enum Op and struct Launch (sources of the env kernels) do not know it."""
+def test_the_dynamics_op_is_an_ordinary_op():
+    """The op is a member of enum Op and its arguments a field of struct Launch, like every other op's; nothing is carried through
+    another op's arguments.  The kernel, its arguments' type and its buffer layout stay in the physics layer."""
+    import re
     csrc = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
-    for f in os.listdir(csrc):
-        if f.endswith((".hip", ".hpp")):
-            text = open(os.path.join(csrc, f)).read()
-            assert "OP_PHYS_DYNAMICS" not in text and "dynamics_kernel" not in text and "DynArgs" not in text, f
+    for d in (csrc, os.path.join(csrc, "physics")):
+        for f in os.listdir(d):
+            if f.endswith((".hip", ".hpp")):
+                text = open(os.path.join(d, f)).read()
+                assert "pack_dyn" not in text and "reinterpret_cast<const int4" not in text, f
+                if d == csrc:
+                    assert "dynamics_kernel" not in text and "struct DynArgs" not in text, f
+    launch = open(os.path.join(csrc, "rsr_launch.hpp")).read()
+    assert "OP_PHYS_DYNAMICS" in re.search(r"enum Op \{(.*?)\};", launch, re.S).group(1)
+    assert re.search(r"\bDynArgs d;", re.search(r"struct Launch \{(.*?)\};", launch, re.S).group(1))
+    for unit in ("rsr_cube.hip", "rsr_tshape.hip", "rsr_go2.hip"):          # the units name the ops they forward; no catch-all
+        text = open(os.path.join(csrc, unit)).read()
+        assert "case OP_PHYS_DYNAMICS:" in text and "default: return -1;" in text, unit
     phys = open(os.path.join(csrc, "physics", "rsr_physics.hpp")).read()
-    assert "OP_PHYS_DYNAMICS" in phys and "struct DynLayout" in phys
+    assert "OP_PHYS_DYNAMICS = " not in phys and "struct DynArgs" in phys and "struct DynLayout" in phys
+    kernels = open(os.path.join(csrc, "physics", "rsr_physics_kernels.hpp")).read()
+    lp = kernels[kernels.index("int launch_physics("):]
+    assert "switch (op)" in lp and "case OP_PHYS_DYNAMICS:" in lp and "default: return -1;" in lp and "case OP_PHYS_ROLLOUT:" in lp
     kern = open(os.path.join(csrc, "physics", "rsr_dynamics.hpp")).read()
     assert "void dynamics_kernel(" in kern
     for stage in ("kinematics<C>(", "com_crb_mass<C>(", "smooth_forces<C>("):

@@ -26,6 +26,7 @@ for rnd in range(rounds):
             res[l].append(j["value"]); info[l] = (j["config"]["lds_bytes_per_env"], j["config"]["ncon_max"], j["roofline"]["avg_launch_ms"])
         except Exception:
             print(l, "FAILED", out.stderr[-400:])
+            sys.exit(1)                            # nothing more is started on a GPU that a run may have faulted
     print(f"round {rnd} done", flush=True)
 for l in args:
     print(f"{l}: " + " ".join(f"{x / 1e6:.3f}" for x in res[l]) + f"  M env-steps/s   lds/ncon/kernel ms {info.get(l)}")
