@@ -11,6 +11,8 @@
  *                          pass of these calls (zero until set).
  *   rsr_physics_dynamics <- mj_fullM, data.qfrc_bias / qfrc_passive / qfrc_actuator and mj_jacSite at the record's current state
  *                          (after the last integration, unlike the views of rsr_physics_view), in a buffer of its own.
+ *   rsr_physics_constraint <- data.efc_force, data.qfrc_constraint and mj_contactForce of one mjx.forward at the record's current
+ *                          state, in a buffer of its own.
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
@@ -156,6 +158,37 @@ int rsr_physics_set_jac_sites(rsr_physics* p, const int32_t* site_ids, int nsite
 int rsr_physics_dynamics(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream);
 /* Zero-copy view (as rsr_physics_view) of one field of the dynamics buffer.  RSR_ERR_ARG for an unknown id. */
 int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
+
+/* Constraint and contact forces: one launch that runs one mjx.forward pass at the record's current state -- its qpos / qvel / ctrl /
+ * qacc_warmstart, the batch's per-env leaves and, while they are on, the handle's applied forces -- and writes the handle's
+ * constraint buffer.  Like rsr_physics_dynamics it describes the state after the last integration.  Nothing else is written: the
+ * record (qacc_warmstart, xpos and site_xpos included), the side buffer, RSR_P_SENSORDATA and the dynamics buffer are untouched,
+ * and no PRNG key advances.  The pass is the one rsr_physics_forward would run on the same record: its qacc and contact list are
+ * those bit for bit.  The row forces are evaluated at the solver's final qacc (MJX's _update_constraint), so
+ * M qacc = qfrc_smooth + qfrc_constraint holds to the solver's convergence (one Newton iteration on the Go2 models).
+ * nefc_max and ncon_max: rsr_dims.  NPYR = 2 (condim - 1) pyramid edges per contact: 4 on the Go2 models, 6 on the Airbot ones;
+ * the edges of a contact come in pairs (+, -) per direction: tangent 1, tangent 2, then torsion (condim 4). */
+enum rsr_constraint_field {
+  RSR_C_QFRC_CONSTRAINT = 0,  /* [nv]           J^T efc_force at the solver's final qacc */
+  RSR_C_QACC,                 /* [nv]           qacc of this pass */
+  RSR_C_EFC_COUNTS,           /* [4]            nefc, ne, nf, nl (active limits), as float */
+  RSR_C_EFC_FORCE,            /* [nefc_max]     rows in the model's order: equality, dof friction, active limits,
+                                                contacts x NPYR pyramid edges; rows >= nefc are 0 */
+  RSR_C_NCON,                 /* [1] */
+  RSR_C_CONTACT,              /* [ncon_max*9]   as RSR_P_CONTACT, same slots */
+  RSR_C_CONTACT_WRENCH,       /* [ncon_max*7]   per slot: normal force (>= 0), force[3], torque[3] in the world frame,
+                                                acting on geom2's body at the contact point (geom1's body gets the
+                                                negative); torque is the torsional moment about the normal, 0 for condim 3;
+                                                slots >= ncon are 0 */
+  RSR_C_COUNT
+};
+/* env_ids: device int32 [count], or NULL for every env (count is ignored); ids outside [0, num_envs) are skipped.  Only the
+ * listed envs' rows of the buffer are written.  RSR_ERR_ARG: null handle, env_ids with count < 1; checked before any device
+ * work.  The buffer is allocated and zeroed by the first of these two calls; the views' pointers and row stride do not move
+ * afterwards.  rsr_physics_destroy frees it. */
+int rsr_physics_constraint(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream);
+/* Zero-copy view (as rsr_physics_view) of one field of the constraint buffer.  RSR_ERR_ARG for an unknown id. */
+int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
 
 #ifdef __cplusplus
 }

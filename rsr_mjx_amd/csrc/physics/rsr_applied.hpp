@@ -53,4 +53,12 @@ struct AppliedStage {
   __device__ __forceinline__ float operator()(const Hot& h, Smem<C>& s, int lane, float fs) const { return applied_forces<C>(h, s, lane, ap, fs); }
 };
 
+// forward<C>'s force stage of env e: none, or its rows of the applied forces (the handle's buffers xfrc / qfrc)
+template <class C>
+__device__ __forceinline__ NoForceStage force_stage(int) { return {}; }
+template <class C>
+__device__ __forceinline__ AppliedStage<C> force_stage(int e, const float* xfrc, const float* qfrc) {
+  return {{xfrc + (size_t)e * (C::NB * 6), qfrc + (size_t)e * C::NV}};
+}
+
 }  // namespace rsr

@@ -1,7 +1,7 @@
 // rsr_physics.hip -- the C ABI of the physics layer (include/rsr_physics.h): rsr_physics_step / rsr_physics_forward /
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
-// the dynamics terms (rsr_physics_dynamics).  The kernels are in the family units
-// (physics/rsr_physics_kernels.hpp).
+// the dynamics terms (rsr_physics_dynamics) and the constraint and contact forces (rsr_physics_constraint).  The kernels are in the
+// family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -22,6 +22,7 @@ struct rsr_physics {
   float* dyn = nullptr;   // the dynamics buffer [n][DynLayout::stride], allocated on first use (dyn_alloc)
   int* jac_sites = nullptr;  // [RSR_MAX_JAC_SITES] the Jacobian sites (device)
   int njac = 0;
+  float* con = nullptr;   // the constraint buffer [n][ConLayout::stride], allocated on first use (con_alloc)
 };
 
 extern "C" int rsr_physics_create(rsr_batch* b, rsr_physics** out) {
@@ -54,12 +55,14 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
   if (p->qfrc) (void)hipFree(p->qfrc);
   if (p->dyn) (void)hipFree(p->dyn);
   if (p->jac_sites) (void)hipFree(p->jac_sites);
+  if (p->con) (void)hipFree(p->con);
   delete p;
 }
 
 // One physics op on `grid` envs (ids: which, or null: the first `grid`), the handle's buffers as every op's arguments; reports the launch error as `who`.
+// con: OP_PHYS_DYNAMICS writes the constraint buffer (rsr_physics_constraint) instead of the dynamics buffer.
 static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, int grid, int nsteps, int op, void* hip_stream, const char* who,
-                          const rsr::RollArgs& r = rsr::RollArgs{}) {
+                          const rsr::RollArgs& r = rsr::RollArgs{}, float* con = nullptr) {
   rsr_batch* b = ph->b;
   HIPCHK(hipSetDevice(b->device));
   rsr::Launch x = launch_args(b, hip_stream);
@@ -67,7 +70,7 @@ static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, in
   x.a.debug = nullptr;
   x.p = rsr::PhysArgs{ctrl, ph->out, ids, nsteps, ph->sd, rsr::SensArgs{ph->sens_el, ph->nsd, ph->acc_site}};
   x.r = r;
-  x.d = rsr::DynArgs{ph->dyn, ids, ph->jac_sites, ph->njac};
+  x.d = con ? rsr::DynArgs{con, ids, nullptr, 0, 1} : rsr::DynArgs{ph->dyn, ids, ph->jac_sites, ph->njac, 0};
   if (ph->applied) x.ap = rsr::Applied{ph->xfrc, ph->qfrc};
   if (launch(b, op, x) < 0) return fail(RSR_ERR_UNSUPPORTED, std::string(who) + ": the model's kernels have no such op");
   { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
@@ -259,5 +262,50 @@ extern "C" int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_p
   *dev_ptr = p->dyn + off;
   shape[0] = p->b->n; shape[1] = w;
   stride[0] = DL.stride; stride[1] = 1;
+  return RSR_OK;
+}
+
+// the constraint buffer, on first use (zeroed)
+static int con_alloc(rsr_physics* p, const char* who) {
+  if (p->con) return RSR_OK;
+  const rsr_dims& d = p->b->model->dims;
+  const size_t bytes = (size_t)p->b->n * rsr::con_layout(d.nv, d.nefc_max, d.ncon_max).stride * sizeof(float);
+  HIPCHK(hipSetDevice(p->b->device));
+  float* con = nullptr;
+  if (hipMalloc(&con, bytes) != hipSuccess) return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(constraint buffer)");
+  if (hipMemset(con, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(con); return fail(RSR_ERR_HIP, std::string(who) + ": hipMemset");
+  }
+  p->con = con;
+  return RSR_OK;
+}
+
+extern "C" int rsr_physics_constraint(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_constraint: null handle");
+  if (env_ids && count < 1) return fail(RSR_ERR_ARG, "rsr_physics_constraint: count < 1 with env_ids");
+  if (const int rc = con_alloc(p, "rsr_physics_constraint")) return rc;
+  return physics_launch(p, nullptr, env_ids, env_ids ? count : p->b->n, 1, rsr::OP_PHYS_DYNAMICS, hip_stream, "rsr_physics_constraint",
+                        rsr::RollArgs{}, p->con);
+}
+
+extern "C" int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
+  if (!p || !dev_ptr || !shape || !stride) return fail(RSR_ERR_ARG, "rsr_physics_constraint_view: null argument");
+  const rsr_dims& d = p->b->model->dims;
+  const rsr::ConLayout CL = rsr::con_layout(d.nv, d.nefc_max, d.ncon_max);
+  int off = -1, w = 0;
+  switch (field) {
+    case RSR_C_QFRC_CONSTRAINT: off = CL.qfc; w = d.nv; break;
+    case RSR_C_QACC: off = CL.qacc; w = d.nv; break;
+    case RSR_C_EFC_COUNTS: off = CL.counts; w = 4; break;
+    case RSR_C_EFC_FORCE: off = CL.force; w = d.nefc_max; break;
+    case RSR_C_NCON: off = CL.ncon; w = 1; break;
+    case RSR_C_CONTACT: off = CL.con; w = 9 * d.ncon_max; break;
+    case RSR_C_CONTACT_WRENCH: off = CL.wrench; w = 7 * d.ncon_max; break;
+    default: return fail(RSR_ERR_ARG, "rsr_physics_constraint_view: unknown field id");
+  }
+  if (const int rc = con_alloc(p, "rsr_physics_constraint_view")) return rc;
+  *dev_ptr = p->con + off;
+  shape[0] = p->b->n; shape[1] = w;
+  stride[0] = CL.stride; stride[1] = 1;
   return RSR_OK;
 }

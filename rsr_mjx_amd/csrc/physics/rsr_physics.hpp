@@ -53,12 +53,27 @@ __host__ __device__ inline DynLayout dyn_layout(int nv) {
   d.stride = (d.jac + RSR_MAX_JAC_SITES * 6 * nv + 15) & ~15;
   return d;
 }
+// rsr_physics_constraint (rsr_constraint.hpp).  Its buffer, per env, floats: qfrc_constraint [nv] | qacc [nv] | efc counts [4]
+// (nefc, ne, nf, nl) | efc_force [nefc_max] | ncon | contacts [ncon_max][9] (as the side buffer's) | contact wrench [ncon_max][7]
+// (normal force, force[3], torque[3]), padded to 16 floats.
+struct ConLayout { int qfc, qacc, counts, force, ncon, con, wrench, stride; };
+__host__ __device__ inline ConLayout con_layout(int nv, int nefc_max, int ncon_max) {
+  ConLayout c;
+  c.qfc = 0; c.qacc = nv; c.counts = 2 * nv; c.force = c.counts + 4; c.ncon = c.force + nefc_max; c.con = c.ncon + 1;
+  c.wrench = c.con + 9 * ncon_max;
+  c.stride = (c.wrench + 7 * ncon_max + 15) & ~15;
+  return c;
+}
 // The launch arguments of OP_PHYS_DYNAMICS (Launch::d)
 struct DynArgs {
-  float* out;           // the dynamics buffer [N][DynLayout::stride]
+  float* out;           // the dynamics buffer [N][DynLayout::stride]; con: the constraint buffer [N][ConLayout::stride]
   const int* ids;       // [grid] the envs to run, or null: env = workgroup index
   const int* sites;     // [nsite] site ids of the Jacobians (device)
   int nsite;
+  int con;              // 0: the op runs dynamics_kernel; 1: constraint_kernel (rsr_physics_constraint), which reads out and ids.
+                        // (An int in the struct's tail padding, not a second pointer: the struct keeps its 32 bytes, so
+                        // dynamics_kernel's kernel arguments and with them its code object stay as they were.)
 };
+static_assert(sizeof(DynArgs) == 32, "dynamics_kernel's kernel-argument block");
 
 }  // namespace rsr

@@ -8,6 +8,7 @@
 #include "rsr_sensors.hpp"
 #include "rsr_applied.hpp"
 #include "rsr_dynamics.hpp"
+#include "rsr_constraint.hpp"
 
 namespace rsr {
 
@@ -38,14 +39,6 @@ __device__ __forceinline__ void store_side(const DModel& m, const Smem<C>& s, fl
     w[7] = on ? (float)m.pair_geom1[pr] : -1.0f; w[8] = on ? (float)m.pair_geom2[pr] : -1.0f;
   }
   if (lane == 0) { o[PL.ncon] = (float)nc; o[PL.ncon_drop] = (float)s.ncon_drop; }
-}
-
-// forward<C>'s force stage of env e: none, or its rows of the applied forces (the handle's buffers xfrc / qfrc: rsr_applied.hpp)
-template <class C>
-__device__ __forceinline__ NoForceStage force_stage(int) { return {}; }
-template <class C>
-__device__ __forceinline__ AppliedStage<C> force_stage(int e, const float* xfrc, const float* qfrc) {
-  return {{xfrc + (size_t)e * (C::NB * 6), qfrc + (size_t)e * C::NV}};
 }
 
 // STEP: nsteps x (forward, integrate); otherwise one forward.  Position-dependent outputs (xpos, xquat, site_xpos, contacts) are
@@ -173,7 +166,9 @@ int launch_physics(int op, const Launch& x) {
     case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, true, WAVES>, x.p);
     case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, false, WAVES>, x.p);
     case OP_PHYS_ROLLOUT: return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
-    case OP_PHYS_DYNAMICS: return go(dynamics_kernel<C, WAVES>, x.d);      // (applied forces enter none of its outputs)
+    case OP_PHYS_DYNAMICS:                 // x.d.con: rsr_physics_constraint on its buffer, or 0: rsr_physics_dynamics
+      if (!x.d.con) return go(dynamics_kernel<C, WAVES>, x.d);      // (applied forces enter none of its outputs)
+      return ap ? go(constraint_kernel<C, WAVES, Applied>, x.d, x.ap) : go(constraint_kernel<C, WAVES>, x.d);
     default: return -1;
   }
 }

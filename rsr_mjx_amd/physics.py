@@ -9,6 +9,8 @@
     mj_fullM / data.qfrc_bias / mj_jacSite       ->  Physics.dynamics()                   (qM, qfrc_bias, qfrc_passive,
                                                                                            qfrc_actuator, jacp, jacr at the
                                                                                            record's current state)
+    data.efc_force / qfrc_constraint / mj_contactForce ->  Physics.constraint_forces()    (one mjx.forward at the record's current
+                                                                                           state; Physics.contact_forces())
 
 `Physics(env)` shares the batch of a BatchedEnv (Airbot cube / sf / T-shape, Go2 joystick, handstand / footstand): the same model,
 the same per-env domain randomisation, the same record and the same stream.  The pipeline fields it exposes are the record's own
@@ -74,11 +76,13 @@ class Physics:
         self.qfrc_applied = None
         # the dynamics buffer's views (dynamics): fetched on first use, when the library allocates the buffer
         self._dyn: Optional[Dict[str, Any]] = None
+        # the constraint buffer's views (constraint_forces): likewise
+        self._con: Optional[Dict[str, Any]] = None
         if sensors is not None:
             self.set_sensors(sensors)
 
     def _fetch(self, view_fn: str, fid: int):
-        """field `fid` of one of the library's three *_view entry points, as a tensor on the handle's memory"""
+        """field `fid` of one of the library's *_view entry points, as a tensor on the handle's memory"""
         ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
         _lib.check(getattr(_lib.lib(), view_fn)(self._h, fid, C.byref(ptr), shape, stride))
         return _view(ptr, shape, stride, self.device)
@@ -243,6 +247,50 @@ class Physics:
         ids32 = ids.to(torch.int32).contiguous()
         self._dyn_ids_in = ids32                   # kept alive until the next call (the launch is asynchronous)
         _lib.check(_lib.lib().rsr_physics_dynamics(self._h, C.c_void_p(ids32.data_ptr()), ids.numel(), self._stream()))
+
+    def _con_views(self) -> Dict[str, Any]:
+        if self._con is None:
+            self._con = {name: self._fetch("rsr_physics_constraint_view", fid) for fid, name in enumerate(_lib.CONSTRAINT_FIELDS)}
+        return self._con
+
+    # outputs of constraint_forces(): views of the handle's constraint buffer, zeros until the first call
+    qfrc_constraint = property(lambda self: self._con_views()["qfrc_constraint"], doc="[N, nv] J^T efc_force at the solver's final qacc")
+    efc_force = property(lambda self: self._con_views()["efc_force"],
+                         doc="[N, nefc_max] row forces: equality, dof friction, active limits, contacts x pyramid edges; rows >= nefc are 0")
+    efc_counts = property(lambda self: self._con_views()["efc_counts"], doc="[N, 4] nefc, ne, nf, nl (active limits), as float")
+    constraint_qacc = property(lambda self: self._con_views()["qacc"], doc="[N, nv] qacc of the pass constraint_forces() ran")
+
+    def constraint_forces(self, env_ids=None) -> None:
+        """One mjx.forward pass at the record's current qpos / qvel / ctrl / qacc_warmstart (per-env leaves and, when on, the
+        applied forces included), one launch: fills qfrc_constraint, efc_force, efc_counts, constraint_qacc and the contacts of
+        contact_forces() of the envs `env_ids` (default: all).  Like dynamics() it describes the state after the last
+        integration and writes nothing else: not the record (qacc_warmstart stays), the side buffer, sensordata or the dynamics
+        buffer.  Its qacc and contacts are bit for bit those forward() would give on the same record, and
+        qM @ constraint_qacc = qfrc_passive - qfrc_bias + qfrc_actuator (+ applied forces) + qfrc_constraint to the solver's
+        convergence."""
+        import torch
+        if env_ids is None:
+            _lib.check(_lib.lib().rsr_physics_constraint(self._h, None, 0, self._stream()))
+            return
+        ids = self._ids(env_ids, "constraint_forces")
+        if ids.numel() == 0:
+            return
+        ids32 = ids.to(torch.int32).contiguous()
+        self._con_ids_in = ids32                   # kept alive until the next call (the launch is asynchronous)
+        _lib.check(_lib.lib().rsr_physics_constraint(self._h, C.c_void_p(ids32.data_ptr()), ids.numel(), self._stream()))
+
+    def contact_forces(self) -> Dict[str, Any]:
+        """The contacts of the last constraint_forces() with their forces (mj_contactForce, in the world frame), per env and
+        contact slot as contacts(): ncon [N] (int), dist [N, K], pos [N, K, 3], normal [N, K, 3] (views), geom1 / geom2 [N, K]
+        (int), and normal_force [N, K] (>= 0), force [N, K, 3], torque [N, K, 3] (views): the force and the torsional moment
+        about the normal that act on geom2's body at `pos`; geom1's body gets the negative.  Slots >= ncon are zeros."""
+        import torch
+        v = self._con_views()
+        c = v["contact"].unflatten(1, (self.ncon_max, 9))
+        w = v["contact_wrench"].unflatten(1, (self.ncon_max, 7))
+        return dict(ncon=v["ncon"][:, 0].to(torch.int32), dist=c[:, :, 0], pos=c[:, :, 1:4], normal=c[:, :, 4:7],
+                    geom1=c[:, :, 7].to(torch.int32), geom2=c[:, :, 8].to(torch.int32),
+                    normal_force=w[:, :, 0], force=w[:, :, 1:4], torque=w[:, :, 4:7])
 
     def rollout(self, ctrl, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), qpos0=None, qvel0=None,
                 ctrl0=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:

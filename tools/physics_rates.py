@@ -3,8 +3,10 @@ timed with HIP events on the launch stream (rsr_timing_begin / rsr_timing_end). 
 to a file.  --applied adds the rates with applied forces on (Physics.set_applied: a non-zero xfrc on every body and a qfrc on every
 dof), for the step and for a rollout of --rollout-T control steps, beside the plain ones.  --dynamics adds ms per
 rsr_physics_dynamics launch without Jacobian sites and with the family's example sites, beside ms per rsr_physics_forward launch
-on the same batch.
-Usage: python tools/physics_rates.py [--envs 8192] [--steps 50] [--warmup 10] [--applied] [--dynamics] [--rollout-T 16] [--out FILE]"""
+on the same batch.  --constraint adds ms per rsr_physics_constraint launch (Physics.constraint_forces) beside ms per
+rsr_physics_forward launch, interleaved in blocks on the same batch and state (of the state, forward moves qacc_warmstart only).
+Usage: python tools/physics_rates.py [--envs 8192] [--steps 50] [--warmup 10] [--applied] [--dynamics] [--constraint]
+                                     [--rollout-T 16] [--out FILE]"""
 from __future__ import annotations
 
 import argparse
@@ -25,6 +27,7 @@ def main() -> None:
     ap.add_argument("--families", default="cube,tshape,go2flat,go2rough,footstand")
     ap.add_argument("--applied", action="store_true")
     ap.add_argument("--dynamics", action="store_true")
+    ap.add_argument("--constraint", action="store_true")
     ap.add_argument("--rollout-T", type=int, default=16)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -108,6 +111,27 @@ def main() -> None:
             row["dynamics_sites_ms"] = per_launch(phys.dynamics)
             row["jac_sites"] = len(sites)
             row["dynamics_over_forward"] = row["dynamics_sites_ms"] / row["forward_ms"]
+            from bench import csrc_sha16
+            row["csrc_sha16"] = csrc_sha16()
+        if args.constraint:
+            # forward and constraint_forces in alternating blocks (A B A B A B), medians of the blocks: a drift of the clocks
+            # over the run falls on both
+            def block(fn):
+                env.timing_begin()
+                for _ in range(args.steps):
+                    fn()
+                return env.timing_end()[0] / args.steps
+            for _ in range(args.warmup):
+                phys.forward()
+                phys.constraint_forces()
+            fwd, con = [], []
+            for _ in range(3):
+                fwd.append(block(phys.forward))
+                con.append(block(phys.constraint_forces))
+            row["forward_ms"] = float(np.median(fwd))
+            row["constraint_ms"] = float(np.median(con))
+            row["forward_ms_blocks"], row["constraint_ms_blocks"] = fwd, con
+            row["constraint_over_forward"] = row["constraint_ms"] / row["forward_ms"]
             from bench import csrc_sha16
             row["csrc_sha16"] = csrc_sha16()
         row["finite"] = bool(torch.isfinite(env.view("qpos")).all())
