@@ -3,12 +3,11 @@
 // pass's qacc and contact list, and the wrench of every contact (mj_contactForce, rotated to the world frame).  Nothing but that
 // buffer is written: the record keeps its qacc_warmstart, xpos and site_xpos.
 //
-// forward<C> (rsr_solver.hpp) keeps the per-row registers of make_constraint to itself, so this kernel restates its sequence of
-// stages -- the same building blocks, in the same order, with the same arguments -- and goes on from the rows and the solver's
-// qacc: jaref = J qacc - aref, the row forces (rows_cost), J^T force (jt_force), as MJX's _update_constraint does after the last
-// iteration.  solve()'s own qfrc_constraint is not used: a single-iteration solve that nobody asks for the force (the Go2 models)
-// never forms it.  The stages compile to the arithmetic of physics_kernel<C, false>: qacc and the contact list are bit-identical
-// to what rsr_physics_forward gives on the same record (tests/test_constraint_gpu.py).
+// The pass is forward<C> (rsr_solver.hpp), called once with the force stage of the physics kernels and a rows tail (RowForces):
+// the tail sees the per-row registers of make_constraint and the solver's qacc and does what MJX's _update_constraint does after
+// the last iteration: jaref = J qacc - aref, the row forces (rows_cost), J^T force (jt_force).  solve()'s own qfrc_constraint is
+// not used: a single-iteration solve that nobody asks for the force (the Go2 models) never forms it.  qacc and the contact list
+// are bit-identical to what rsr_physics_forward gives on the same record (tests/test_constraint_gpu.py).
 #pragma once
 #include "../rsr_launch.hpp"
 #include "rsr_applied.hpp"
@@ -16,10 +15,10 @@
 namespace rsr {
 
 // One wave per env, a plain launch.  d.ids: the envs to run or null (env = workgroup index); an id out of range runs nothing.
-// d.out: the constraint buffer (d.con).  Ap: none, or Applied: the applied forces enter the pass as in the applied physics kernels.
+// d.out: the constraint buffer.  Ap: none, or Applied: the applied forces enter the pass as in the applied physics kernels.
 template <class C, int WAVES, class... Ap>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
-void constraint_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, DynArgs d, Ap... ap) {
+void constraint_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, ConArgs d, Ap... ap) {
   static_assert(C::NBC == 3 || C::NBC == 4, "contact wrench: frictional contacts with or without torsion");
   const DModel& m = *mp;
   const Hot hot = make_hot(m);
@@ -41,71 +40,31 @@ void constraint_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, DynA
   }
   WSYNC();
   const int lane_s = lrec_lane(lane);
-  // ---------------- forward<C>, stage for stage ----------------
-  float Mrow[C::NV];
-  kinematics<C>(m, hot, s, lane_s PROF_PASS);
-  com_crb_mass<C>(m, hot, s, lane_s PROF_PASS);
-  load_mrow<C>(s, lane_s, Mrow);
-  float qvel_i = lane_s < C::NV ? s.qvel[lane_s] : 0.0f;
-  float fs = smooth_forces<C>(m, hot, s, lane_s, qvel_i, 0.0f PROF_PASS);
-  fs = stage(hot, s, lane_s, fs);
-  float a0;
-  {                                 // qacc_smooth = M^-1 qfrc_smooth, by the family's factorisation
-    float fa[C::NCH], lt[C::NCH];
-    if constexpr (C::ROWTREE) {
-      const float dinv_m = rowtree_factor<C>(s.M, 0.0f, fa, lt, s.scratch_a(), lane_s);
-      a0 = rowtree_solve<C>(fa, lt, dinv_m, fs, lane_s);
-      a0 = lane_s < C::NV ? a0 : 0.0f;
-    } else if constexpr (C::ROWCHOL) {
-      const float dinv_m = rowchol_factor<C, true>(s.M, 0.0f, fa, lt, s.scratch_a(), lane_s);
-      a0 = rowchol_solve<C>(fa, lt, dinv_m, fs, lane_s);
-      a0 = lane_s < C::NV ? a0 : 0.0f;
-    } else if constexpr (C::ARROW) {
-      const float dinv_m = arrow_factor<C>(s.M, 0.0f, fa, lt, s.scratch_a(), lane_s);
-      a0 = arrow_solve<C>(fa, lt, dinv_m, fs, lane_s);
-      a0 = lane_s < C::NV ? a0 : 0.0f;
-    } else {
-#pragma unroll
-      for (int j = 0; j < C::NV; ++j) fa[j] = Mrow[j];
-      const float dinv_m = chol_factor<C, true>(fa, lt, s.scratch_a(), lane_s);
-      a0 = lane_s < C::NV ? chol_solve<C>(fa, lt, dinv_m, fs, lane_s) : 0.0f;
-    }
-  }
-  collision<C>(m, hot, s, lane_s PROF_PASS);
-  RowRegs rr[C::NCHUNK];
-  float bcoef[C::NCHUNK], jqv[C::NCHUNK];
-  int nbase;
-  const int nefc = make_constraint<C>(m, hot, s, lane_s, rr, bcoef, nbase PROF_PASS);
-  {
-    float qb[NVP<C>];
-    vec_bcast<C>(s, lane_s, qvel_i, qb);
-    jdot<C>(s, lane_s, nefc, nbase, rr, qb, jqv);                 // aref = -b (J.qvel) - k imp pos
-  }
-#pragma unroll
-  for (int ch = 0; ch < C::NCHUNK; ++ch) rr[ch].aref -= bcoef[ch] * jqv[ch];
-  const bool need_force = implicit_integration<C>(hot, s, lane_s);
-  float qacc, qfc_solver;
-  SolveStats st;
-  solve<C>(hot, s, lane_s, nefc, nbase, rr, Mrow, fs, a0, warm, need_force, qacc, qfc_solver, st, nullptr PROF_PASS);
-  if constexpr (!C::ARROW) __builtin_amdgcn_s_setprio(0);       // (raised at the top of solve())
-  // ---------------- the rows at the solver's qacc ----------------
+  float Mrow[C::NV], force[C::NCHUNK], qfc;
+  FwdOut<C> f;
+  // The rows tail: the rows at the solver's qacc, each row's force (force[ch]: row lane + 64 ch) and this lane's qfrc_constraint.
   // Live in LDS after the solve: the base rows J, bmu, sdof, the contact list with its normalised normals.  Dead: M under
-  // Dims::TALIAS (the Hessian's scratch), the tangents make_constraint staged in rw, and whatever the last factorisation left in
-  // jtp | bval | wc | rw; jdot and jt_force rewrite every word of bval and rw that they read, as inside the solver's loop.
-  float force[C::NCHUNK], hw[C::NCHUNK], jaref[C::NCHUNK];
-  {
-    float vb[NVP<C>];
-    vec_bcast<C>(s, lane_s, qacc, vb);
-    jdot<C>(s, lane_s, nefc, nbase, rr, vb, jaref);
-  }
+  // Dims::TALIAS (the Hessian's scratch), the tangents the rows' construction staged in rw, and whatever the last factorisation
+  // left in jtp | bval | wc | rw; jdot and jt_force rewrite every word of bval and rw that they read, as inside the solver's loop.
+  forward<C>(m, hot, s, lane_s, Mrow, warm, f, nullptr PROF_PASS, stage,      // (warm dies here: the record keeps its own)
+             [&](Smem<C>& s, int lane_s, int nefc, int nbase, const RowRegs (&rr)[C::NCHUNK], float qacc) {
+    if constexpr (!C::ARROW) __builtin_amdgcn_s_setprio(0);       // (raised at the top of the solver)
+    float hw[C::NCHUNK], jaref[C::NCHUNK];
+    {
+      float vb[NVP<C>];
+      vec_bcast<C>(s, lane_s, qacc, vb);
+      jdot<C>(s, lane_s, nefc, nbase, rr, vb, jaref);
+    }
 #pragma unroll
-  for (int ch = 0; ch < C::NCHUNK; ++ch) jaref[ch] -= rr[ch].aref;
-  (void)rows_cost<C, false>(lane_s, nefc, jaref, rr, force, hw);
-  const float qfc = jt_force<C>(s, lane_s, nefc, nbase, force);      // leaves the contact rows' forces in rw[rcon .. nefc)
+    for (int ch = 0; ch < C::NCHUNK; ++ch) jaref[ch] -= rr[ch].aref;
+    (void)rows_cost<C, false>(lane_s, nefc, jaref, rr, force, hw);
+    qfc = jt_force<C>(s, lane_s, nefc, nbase, force);      // leaves the contact rows' forces in rw[rcon .. nefc)
+  });
+  const int nefc = f.nefc;
   WSYNC();
   const ConLayout CL = con_layout(C::NV, C::NEFC, C::NCON);
   float* o = d.out + (size_t)e * CL.stride;
-  if (lane < C::NV) { o[CL.qfc + lane] = qfc; o[CL.qacc + lane] = qacc; }
+  if (lane < C::NV) { o[CL.qfc + lane] = qfc; o[CL.qacc + lane] = f.qacc; }
 #pragma unroll
   for (int ch = 0; ch < C::NCHUNK; ++ch) {
     const int r = lane + 64 * ch;

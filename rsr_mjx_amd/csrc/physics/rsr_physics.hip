@@ -60,9 +60,8 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
 }
 
 // One physics op on `grid` envs (ids: which, or null: the first `grid`), the handle's buffers as every op's arguments; reports the launch error as `who`.
-// con: OP_PHYS_DYNAMICS writes the constraint buffer (rsr_physics_constraint) instead of the dynamics buffer.
 static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, int grid, int nsteps, int op, void* hip_stream, const char* who,
-                          const rsr::RollArgs& r = rsr::RollArgs{}, float* con = nullptr) {
+                          const rsr::RollArgs& r = rsr::RollArgs{}) {
   rsr_batch* b = ph->b;
   HIPCHK(hipSetDevice(b->device));
   rsr::Launch x = launch_args(b, hip_stream);
@@ -70,7 +69,8 @@ static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, in
   x.a.debug = nullptr;
   x.p = rsr::PhysArgs{ctrl, ph->out, ids, nsteps, ph->sd, rsr::SensArgs{ph->sens_el, ph->nsd, ph->acc_site}};
   x.r = r;
-  x.d = con ? rsr::DynArgs{con, ids, nullptr, 0, 1} : rsr::DynArgs{ph->dyn, ids, ph->jac_sites, ph->njac, 0};
+  x.d = rsr::DynArgs{ph->dyn, ids, ph->jac_sites, ph->njac};
+  x.c = rsr::ConArgs{ph->con, ids};
   if (ph->applied) x.ap = rsr::Applied{ph->xfrc, ph->qfrc};
   if (launch(b, op, x) < 0) return fail(RSR_ERR_UNSUPPORTED, std::string(who) + ": the model's kernels have no such op");
   { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
@@ -95,6 +95,14 @@ extern "C" int rsr_physics_forward_envs(rsr_physics* p, const int32_t* env_ids, 
   return physics_launch(p, nullptr, env_ids, count, 1, rsr::OP_PHYS_FORWARD, hip_stream, "rsr_physics_forward_envs");
 }
 
+// a view's answer: `w` floats per env from `ptr`, the envs `row` floats apart
+static int view_out(const rsr_physics* p, float* ptr, int w, int row, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
+  *dev_ptr = ptr;
+  shape[0] = p->b->n; shape[1] = w;
+  stride[0] = row; stride[1] = 1;
+  return RSR_OK;
+}
+
 extern "C" int rsr_physics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
   if (!p || !dev_ptr || !shape || !stride) return fail(RSR_ERR_ARG, "rsr_physics_view: null argument");
   const rsr_dims& d = p->b->model->dims;
@@ -107,17 +115,10 @@ extern "C" int rsr_physics_view(rsr_physics* p, int field, void** dev_ptr, int64
     case RSR_P_NCON: off = PL.ncon; w = 1; break;
     case RSR_P_CONTACT: off = PL.con; w = 9 * d.ncon_max; break;
     case RSR_P_NCON_DROPPED: off = PL.ncon_drop; w = 1; break;
-    case RSR_P_SENSORDATA:
-      *dev_ptr = p->sd;
-      shape[0] = p->b->n; shape[1] = p->nsd;
-      stride[0] = RSR_MAX_SENSORDATA; stride[1] = 1;
-      return RSR_OK;
+    case RSR_P_SENSORDATA: return view_out(p, p->sd, p->nsd, RSR_MAX_SENSORDATA, dev_ptr, shape, stride);
     default: return fail(RSR_ERR_ARG, "rsr_physics_view: unknown field id");
   }
-  *dev_ptr = p->out + off;
-  shape[0] = p->b->n; shape[1] = w;
-  stride[0] = PL.stride; stride[1] = 1;
-  return RSR_OK;
+  return view_out(p, p->out + off, w, PL.stride, dev_ptr, shape, stride);
 }
 
 extern "C" int rsr_physics_set_sensors(rsr_physics* p, const int32_t* table, int nsensor) {
@@ -196,15 +197,11 @@ extern "C" int rsr_physics_applied_view(rsr_physics* p, int field, void** dev_pt
   if (!p || !dev_ptr || !shape || !stride) return fail(RSR_ERR_ARG, "rsr_physics_applied_view: null argument");
   if (!p->applied) return fail(RSR_ERR_ARG, "rsr_physics_applied_view: applied forces are off (rsr_physics_set_applied)");
   const rsr_dims& d = p->b->model->dims;
-  int w = 0;
   switch (field) {
-    case RSR_A_XFRC_APPLIED: *dev_ptr = p->xfrc; w = 6 * d.nbody; break;
-    case RSR_A_QFRC_APPLIED: *dev_ptr = p->qfrc; w = d.nv; break;
+    case RSR_A_XFRC_APPLIED: return view_out(p, p->xfrc, 6 * d.nbody, 6 * d.nbody, dev_ptr, shape, stride);
+    case RSR_A_QFRC_APPLIED: return view_out(p, p->qfrc, d.nv, d.nv, dev_ptr, shape, stride);
     default: return fail(RSR_ERR_ARG, "rsr_physics_applied_view: unknown field id");
   }
-  shape[0] = p->b->n; shape[1] = w;
-  stride[0] = w; stride[1] = 1;
-  return RSR_OK;
 }
 
 // the dynamics buffer and the site table, on first use (zeroed)
@@ -259,10 +256,7 @@ extern "C" int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_p
     default: return fail(RSR_ERR_ARG, "rsr_physics_dynamics_view: unknown field id");
   }
   if (const int rc = dyn_alloc(p, "rsr_physics_dynamics_view")) return rc;
-  *dev_ptr = p->dyn + off;
-  shape[0] = p->b->n; shape[1] = w;
-  stride[0] = DL.stride; stride[1] = 1;
-  return RSR_OK;
+  return view_out(p, p->dyn + off, w, DL.stride, dev_ptr, shape, stride);
 }
 
 // the constraint buffer, on first use (zeroed)
@@ -284,8 +278,7 @@ extern "C" int rsr_physics_constraint(rsr_physics* p, const int32_t* env_ids, in
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_constraint: null handle");
   if (env_ids && count < 1) return fail(RSR_ERR_ARG, "rsr_physics_constraint: count < 1 with env_ids");
   if (const int rc = con_alloc(p, "rsr_physics_constraint")) return rc;
-  return physics_launch(p, nullptr, env_ids, env_ids ? count : p->b->n, 1, rsr::OP_PHYS_DYNAMICS, hip_stream, "rsr_physics_constraint",
-                        rsr::RollArgs{}, p->con);
+  return physics_launch(p, nullptr, env_ids, env_ids ? count : p->b->n, 1, rsr::OP_PHYS_CONSTRAINT, hip_stream, "rsr_physics_constraint");
 }
 
 extern "C" int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
@@ -304,8 +297,5 @@ extern "C" int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev
     default: return fail(RSR_ERR_ARG, "rsr_physics_constraint_view: unknown field id");
   }
   if (const int rc = con_alloc(p, "rsr_physics_constraint_view")) return rc;
-  *dev_ptr = p->con + off;
-  shape[0] = p->b->n; shape[1] = w;
-  stride[0] = CL.stride; stride[1] = 1;
-  return RSR_OK;
+  return view_out(p, p->con + off, w, CL.stride, dev_ptr, shape, stride);
 }

@@ -1,4 +1,5 @@
-// rsr_physics.hpp -- the physics layer's side-buffer layout and launch arguments (host and device).
+// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics and constraint buffer) and the launch arguments of its ops,
+// one struct per op of rsr_launch.hpp that needs its own (host and device).
 #pragma once
 #include "../../../include/rsr_physics.h"
 #include "../rsr_solver.hpp"
@@ -66,14 +67,16 @@ __host__ __device__ inline ConLayout con_layout(int nv, int nefc_max, int ncon_m
 }
 // The launch arguments of OP_PHYS_DYNAMICS (Launch::d)
 struct DynArgs {
-  float* out;           // the dynamics buffer [N][DynLayout::stride]; con: the constraint buffer [N][ConLayout::stride]
+  float* out;           // the dynamics buffer [N][DynLayout::stride]
   const int* ids;       // [grid] the envs to run, or null: env = workgroup index
   const int* sites;     // [nsite] site ids of the Jacobians (device)
   int nsite;
-  int con;              // 0: the op runs dynamics_kernel; 1: constraint_kernel (rsr_physics_constraint), which reads out and ids.
-                        // (An int in the struct's tail padding, not a second pointer: the struct keeps its 32 bytes, so
-                        // dynamics_kernel's kernel arguments and with them its code object stay as they were.)
 };
 static_assert(sizeof(DynArgs) == 32, "dynamics_kernel's kernel-argument block");
+// The launch arguments of OP_PHYS_CONSTRAINT (Launch::c)
+struct ConArgs {
+  float* out;           // the constraint buffer [N][ConLayout::stride]
+  const int* ids;       // [grid] the envs to run, or null: env = workgroup index
+};
 
 }  // namespace rsr

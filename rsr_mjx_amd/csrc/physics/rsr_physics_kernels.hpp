@@ -1,8 +1,8 @@
 // rsr_physics_kernels.hpp -- the physics-level kernels (include/rsr_physics.h): each family unit instantiates them for its Dims,
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
-// forward), rollout_kernel and dynamics_kernel (rsr_dynamics.hpp); the first two are instantiated plain and with applied forces:
-// the applied kernels take the handle's Applied buffers as one more argument and pass forward<C> their env's rows as its force
-// stage (rsr_applied.hpp).
+// forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp) and constraint_kernel (rsr_constraint.hpp); all but dynamics_kernel
+// are instantiated plain and with applied forces: the applied kernels take the handle's Applied buffers as one more argument and
+// pass forward<C> their env's rows as its force stage (rsr_applied.hpp).
 #pragma once
 #include "../rsr_launch.hpp"
 #include "rsr_sensors.hpp"
@@ -166,9 +166,8 @@ int launch_physics(int op, const Launch& x) {
     case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, true, WAVES>, x.p);
     case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, false, WAVES>, x.p);
     case OP_PHYS_ROLLOUT: return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
-    case OP_PHYS_DYNAMICS:                 // x.d.con: rsr_physics_constraint on its buffer, or 0: rsr_physics_dynamics
-      if (!x.d.con) return go(dynamics_kernel<C, WAVES>, x.d);      // (applied forces enter none of its outputs)
-      return ap ? go(constraint_kernel<C, WAVES, Applied>, x.d, x.ap) : go(constraint_kernel<C, WAVES>, x.d);
+    case OP_PHYS_DYNAMICS: return go(dynamics_kernel<C, WAVES>, x.d);      // (applied forces enter none of its outputs)
+    case OP_PHYS_CONSTRAINT: return ap ? go(constraint_kernel<C, WAVES, Applied>, x.c, x.ap) : go(constraint_kernel<C, WAVES>, x.c);
     default: return -1;
   }
 }

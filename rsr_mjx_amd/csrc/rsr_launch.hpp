@@ -16,6 +16,7 @@ enum Op {
   OP_PHYS_STEP,          // rsr_physics_step
   OP_PHYS_ROLLOUT,       // rsr_physics_rollout (r)
   OP_PHYS_DYNAMICS,      // rsr_physics_dynamics (d): grid = envs or listed envs (d.ids)
+  OP_PHYS_CONSTRAINT,    // rsr_physics_constraint (c): grid = envs or listed envs (c.ids)
 };
 
 struct Launch {
@@ -28,7 +29,8 @@ struct Launch {
   PhysArgs p;           // OP_PHYS_FORWARD, OP_PHYS_STEP, OP_PHYS_ROLLOUT
   RollArgs r;           // OP_PHYS_ROLLOUT
   DynArgs d;            // OP_PHYS_DYNAMICS
-  Applied ap;           // the ops that take p: the applied forces, or ap.xfrc null: none (the plain kernels)
+  ConArgs c;            // OP_PHYS_CONSTRAINT
+  Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
   int env_kind;         // the Go2 unit's pick: handstand / footstand, or the joystick with (hfield) or without the height field
   bool hfield;
 };

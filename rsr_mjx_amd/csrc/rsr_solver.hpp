@@ -654,11 +654,19 @@ struct NoForceStage {
   __device__ __forceinline__ float operator()(const Hot&, S&, int, float fs) const { return fs; }
 };
 
+// forward()'s default rows tail: none.  A tail runs right after the solve and sees what forward() otherwise keeps to itself: the
+// row count, the count of base rows in LDS (nbase), the per-row registers of make_constraint with their final aref, and this
+// lane's qacc; the physics layer's constraint forces are one (rsr_physics_constraint, include/rsr_physics.h).
+struct NoRowsTail {
+  template <class S, class R>
+  __device__ __forceinline__ void operator()(S&, int, int, int, const R&, float) const {}
+};
+
 // MJX forward(): position -> collision -> constraint rows -> velocity/actuation -> solve.
 // warm_i is read and replaced by the solver's qacc (qacc_warmstart <- qacc).
-template <class C, class Stage = NoForceStage>
+template <class C, class Stage = NoForceStage, class Tail = NoRowsTail>
 __device__ __forceinline__ void forward(const DModel& m, const Hot& h, Smem<C>& s, int lane, float (&Mrow)[C::NV], float& warm, FwdOut<C>& out,
-                        float* dbg PROF_ARG, const Stage& stage = Stage{}) {
+                        float* dbg PROF_ARG, const Stage& stage = Stage{}, const Tail& tail = Tail{}) {
   kinematics<C>(m, h, s, lane PROF_PASS);
   PROF(PS_KIN)
   com_crb_mass<C>(m, h, s, lane PROF_PASS);
@@ -709,6 +717,7 @@ __device__ __forceinline__ void forward(const DModel& m, const Hot& h, Smem<C>& 
   const bool need_force = dbg != nullptr || implicit_integration<C>(h, s, lane);
   solve<C>(h, s, lane, nefc, nbase, rr, Mrow, fs, a0, warm, need_force, out.qacc, out.qfc, out.st, dbg PROF_PASS);
   warm = out.qacc;
+  tail(s, lane, nefc, nbase, rr, out.qacc);
   if (dbg) {   // parity dump (layout: rsr_mjx_amd/_debug_layout in the Python binding)
     if (lane == 0) {
       dbg[0] = (float)nefc; dbg[1] = (float)C::NEQ; dbg[2] = (float)C::NF; dbg[3] = (float)s.ncon;

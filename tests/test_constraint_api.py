@@ -63,7 +63,8 @@ def test_argument_checks_come_before_device_work():
     first_dev = lambda b: min(b.index(k) for k in dev if k in b)
     call = body("int rsr_physics_constraint")
     assert call.index("!p)") < first_dev(call) and call.index("count < 1") < first_dev(call)
-    assert call.count("RSR_ERR_ARG") == 2 and "con_alloc(" in call and "OP_PHYS_DYNAMICS" in call and "p->con" in call
+    assert call.count("RSR_ERR_ARG") == 2 and "con_alloc(" in call and "OP_PHYS_CONSTRAINT" in call
+    assert "rsr::ConArgs{ph->con, ids}" in body("static int physics_launch")      # the op runs on the handle's buffer
     view = body("int rsr_physics_constraint_view")
     assert view.index("default: return fail(RSR_ERR_ARG") < first_dev(view)
     for f in ("QFRC_CONSTRAINT", "QACC", "EFC_COUNTS", "EFC_FORCE", "NCON", "CONTACT", "CONTACT_WRENCH"):
@@ -76,19 +77,17 @@ def test_argument_checks_come_before_device_work():
 
 
 def test_the_kernel_lives_in_the_physics_layer():
-    """constraint_kernel is a file of its own under csrc/physics, restates forward<C>'s stages from the shared building blocks, and
-    is routed through launch_physics' OP_PHYS_DYNAMICS case, plain or applied; no kernel source outside csrc/physics knows of it,
-    and the hashed kernel sources are the parent's."""
+    """constraint_kernel is a file of its own under csrc/physics, calls forward<C> once with a rows tail instead of restating its
+    stages, and has an op of its own in launch_physics, plain or applied; no kernel source outside csrc/physics knows of it, and
+    the parity envelopes were measured on these kernel sources."""
     kern = open(os.path.join(CSRC, "physics", "rsr_constraint.hpp")).read()
     assert "void constraint_kernel(" in kern
-    for stage in ("kinematics<C>(", "com_crb_mass<C>(", "load_mrow<C>(", "smooth_forces<C>(", "stage(hot, s, lane_s, fs)", "collision<C>(",
-                  "make_constraint<C>(", "vec_bcast<C>(", "jdot<C>(", "solve<C>(", "rows_cost<C, false>(", "jt_force<C>(", "make_frame("):
-        assert stage in kern, stage
-    order = [kern.index(k) for k in ("kinematics<C>(", "com_crb_mass<C>(", "smooth_forces<C>(", "collision<C>(", "make_constraint<C>(",
-                                     " solve<C>(hot", "rows_cost<C, false>(", "jt_force<C>(")]
+    assert kern.count("forward<C>(") == 1
+    code = re.sub(r"//.*", "", kern)                                       # one statement of the forward pass: none of its stages here
+    named = re.findall(r"\b(kinematics|com_crb_mass|load_mrow|smooth_forces|\w+_factor|\w+_solve|collision|make_constraint|solve)\b", code)
+    assert not named, named
+    order = [kern.index(k) for k in ("forward<C>(", "rows_cost<C, false>(", "jt_force<C>(", "make_frame(")]
     assert order == sorted(order)
-    assert "forward<C>(" not in kern.replace("// forward<C> (", "").replace("forward<C>, stage for stage", "")
-    assert "qfc_solver" in kern and kern.count("qfc_solver") == 2          # solve()'s own force is taken and never used
     assert "asm" not in kern and "atomic" not in kern                      # plain stores only
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
@@ -96,14 +95,18 @@ def test_the_kernel_lives_in_the_physics_layer():
             assert "constraint_kernel" not in text and "ConLayout" not in text and "rsr_constraint" not in text, f
     kernels = open(os.path.join(CSRC, "physics", "rsr_physics_kernels.hpp")).read()
     lp = kernels[kernels.index("int launch_physics("):]
-    case = lp[lp.index("case OP_PHYS_DYNAMICS:"):lp.index("default: return -1;")]
-    assert "dynamics_kernel<C, WAVES>" in case and "constraint_kernel<C, WAVES, Applied>" in case and "constraint_kernel<C, WAVES>" in case
+    dyn_case = lp[lp.index("case OP_PHYS_DYNAMICS:"):lp.index("case OP_PHYS_CONSTRAINT:")]
+    assert "dynamics_kernel<C, WAVES>" in dyn_case and "constraint_kernel" not in dyn_case
+    con_case = lp[lp.index("case OP_PHYS_CONSTRAINT:"):lp.index("default: return -1;")]
+    assert "constraint_kernel<C, WAVES, Applied>" in con_case and "constraint_kernel<C, WAVES>" in con_case
+    assert re.findall(r"\b\w+_kernel\b", con_case) == ["constraint_kernel"] * 2
     dyn = open(os.path.join(CSRC, "physics", "rsr_dynamics.hpp")).read()
     assert "constraint_kernel" not in dyn
     phys = open(os.path.join(CSRC, "physics", "rsr_physics.hpp")).read()
-    assert "struct ConLayout" in phys and "sizeof(DynArgs) == 32" in phys
+    assert "struct ConLayout" in phys and "struct ConArgs" in phys and "sizeof(DynArgs) == 32" in phys
     import bench
-    assert bench.csrc_sha16() == "46239c6709fdff33"
+    import parity_envelopes as PE
+    assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
 
 
 def test_physics_module_surface():
