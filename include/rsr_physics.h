@@ -13,6 +13,8 @@
  *                          (after the last integration, unlike the views of rsr_physics_view), in a buffer of its own.
  *   rsr_physics_constraint <- data.efc_force, data.qfrc_constraint and mj_contactForce of one mjx.forward at the record's current
  *                          state, in a buffer of its own.
+ *   rsr_physics_transition_fd <- mjd_transitionFD / jax.jacobian(mjx.step): finite-difference Jacobians A, B, C, D of
+ *                          rsr_physics_step about the record's current state, in a buffer of its own.
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
@@ -189,6 +191,41 @@ enum rsr_constraint_field {
 int rsr_physics_constraint(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream);
 /* Zero-copy view (as rsr_physics_view) of one field of the constraint buffer.  RSR_ERR_ARG for an unknown id. */
 int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
+
+/* Transition Jacobians by finite differences (MuJoCo's mjd_transitionFD).  With x = (qpos, qvel) and u = ctrl as the record holds
+ * them and F = rsr_physics_step(u, nsteps), one launch evaluates, for every listed env and every column k of
+ * ncol = 2 nv + nu, the two perturbed runs and their difference:
+ *   k < nv            qpos moved by mj_integratePos(qpos, +-eps e_k): hinge / slide and free-joint translations add, a free joint's
+ *                     rotation multiplies its quaternion on the right by exp(+-eps e / 2)
+ *   nv <= k < 2 nv    qvel[k - nv] +- eps
+ *   2 nv <= k         ctrl[k - 2 nv] +- eps, with no ctrl-range handling (MuJoCo nudges ctrl back into its range; this does not)
+ * Every run starts from the record's qacc_warmstart and carries the warm start across its nsteps substeps as rsr_physics_step
+ * does, with the batch's per-env leaves and, while they are on, the handle's applied forces: each run is bit for bit the
+ * rsr_physics_step it stands for.  Rows 0 .. nv-1 of a column are mj_differentiatePos(y+.qpos, y-.qpos) / h, rows nv .. 2 nv-1
+ * (y+.qvel - y-.qvel) / h, and with a sensor table set the rows of C and D are (sensordata+ - sensordata-) / h, sensordata being
+ * that of the run's last forward pass (as RSR_P_SENSORDATA after rsr_physics_step).  RSR_FD_CENTERED: h = 2 eps; without it the
+ * second run is the unperturbed state and h = eps.  These are finite differences of the step at the given eps, not its
+ * derivative: friction loss, limits and contact activation make the step piecewise smooth at the scale of any usable eps.
+ * Nothing but the handle's transition buffer (and, with RSR_FD_STATES, its states buffer) is written: the record, the side
+ * buffer, RSR_P_SENSORDATA, the dynamics buffer and the constraint buffer are untouched, and no PRNG key advances.
+ * One wavefront per (env, column).
+ *   RSR_T_COLUMNS   [ncol * (2 nv + RSR_MAX_SENSORDATA)]  column-major: per column k a row of d qpos [nv], d qvel [nv],
+ *                                                         d sensordata [nsensordata]; the rest of the row is written as 0.  A = rows of
+ *                                                         columns k < 2 nv, entries < 2 nv, transposed; B: columns k >= 2 nv
+ *   RSR_T_STATES_X  [ncol * 2 * (nq + nv + nu)]           with RSR_FD_STATES: per column and run (+eps; then -eps or the
+ *                                                         unperturbed state) the perturbed qpos, qvel, ctrl
+ *   RSR_T_STATES_Y  [ncol * 2 * (nq + nv)]                and that run's end state qpos, qvel
+ * env_ids: device int32 [count], or NULL for every env (count is ignored); ids outside [0, num_envs) are skipped.  Only the
+ * listed envs' rows are written.  RSR_ERR_ARG, checked before any device work: null handle, nsteps outside [1, 2^30), eps not finite or <= 0,
+ * unknown flag bits, env_ids with count < 1.  The transition buffer is allocated and zeroed by the first call that needs it, the
+ * states buffer by the first call with RSR_FD_STATES or the first view of it; the views' pointers and row strides do not move
+ * afterwards.  rsr_physics_destroy frees them. */
+#define RSR_FD_CENTERED 1
+#define RSR_FD_STATES 2
+enum rsr_transition_field { RSR_T_COLUMNS = 0, RSR_T_STATES_X, RSR_T_STATES_Y, RSR_T_COUNT };
+int rsr_physics_transition_fd(rsr_physics* p, const int32_t* env_ids, int count, int nsteps, float eps, int flags, void* hip_stream);
+/* Zero-copy view (as rsr_physics_view) of the transition buffer or of one half of the states buffer.  RSR_ERR_ARG for an unknown id. */
+int rsr_physics_transition_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
 
 #ifdef __cplusplus
 }

@@ -1,9 +1,10 @@
 // rsr_physics.hip -- the C ABI of the physics layer (include/rsr_physics.h): rsr_physics_step / rsr_physics_forward /
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
-// the dynamics terms (rsr_physics_dynamics) and the constraint and contact forces (rsr_physics_constraint).  The kernels are in the
-// family units (physics/rsr_physics_kernels.hpp).
+// the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
+// (rsr_physics_transition_fd).  The kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 
 #include "../rsr_host.hpp"
@@ -23,6 +24,8 @@ struct rsr_physics {
   int* jac_sites = nullptr;  // [RSR_MAX_JAC_SITES] the Jacobian sites (device)
   int njac = 0;
   float* con = nullptr;   // the constraint buffer [n][ConLayout::stride], allocated on first use (con_alloc)
+  float* fd = nullptr;    // the transition buffer [n][FdLayout::env], allocated on first use (fd_alloc)
+  float* fd_states = nullptr;  // the states buffer of RSR_FD_STATES, allocated on first request (fd_alloc)
 };
 
 extern "C" int rsr_physics_create(rsr_batch* b, rsr_physics** out) {
@@ -56,6 +59,8 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
   if (p->dyn) (void)hipFree(p->dyn);
   if (p->jac_sites) (void)hipFree(p->jac_sites);
   if (p->con) (void)hipFree(p->con);
+  if (p->fd) (void)hipFree(p->fd);
+  if (p->fd_states) (void)hipFree(p->fd_states);
   delete p;
 }
 
@@ -298,4 +303,57 @@ extern "C" int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev
   }
   if (const int rc = con_alloc(p, "rsr_physics_constraint_view")) return rc;
   return view_out(p, p->con + off, w, CL.stride, dev_ptr, shape, stride);
+}
+
+// the transition buffer and, with `states`, the states buffer, each on first use (zeroed)
+static int fd_alloc(rsr_physics* p, bool states, const char* who) {
+  if (p->fd && (!states || p->fd_states)) return RSR_OK;
+  const rsr_dims& d = p->b->model->dims;
+  const rsr::FdLayout FL = rsr::fd_layout(d.nq, d.nv, d.nu);
+  HIPCHK(hipSetDevice(p->b->device));
+  auto zeroed = [&](size_t floats, float** out, const char* what) {
+    float* buf = nullptr;
+    if (hipMalloc(&buf, floats * sizeof(float)) != hipSuccess) return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(" + what + ")");
+    if (hipMemset(buf, 0, floats * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+      (void)hipFree(buf); return fail(RSR_ERR_HIP, std::string(who) + ": hipMemset");
+    }
+    *out = buf;
+    return (int)RSR_OK;
+  };
+  if (!p->fd) { if (const int rc = zeroed((size_t)p->b->n * FL.env, &p->fd, "transition buffer")) return rc; }
+  if (states && !p->fd_states) {
+    if (const int rc = zeroed((size_t)p->b->n * FL.ncol * 2 * (FL.xw + FL.yw), &p->fd_states, "states buffer")) return rc;
+  }
+  return RSR_OK;
+}
+
+extern "C" int rsr_physics_transition_fd(rsr_physics* p, const int32_t* env_ids, int count, int nsteps, float eps, int flags, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: null handle");
+  if (nsteps < 1 || nsteps > INT32_MAX / 2) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: nsteps must lie in [1, 2^30)");
+  if (!std::isfinite(eps) || !(eps > 0.0f)) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: eps must be finite and > 0");
+  if (flags & ~(RSR_FD_CENTERED | RSR_FD_STATES)) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: unknown flag bits");
+  if (env_ids && count < 1) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: count < 1 with env_ids");
+  const rsr_dims& d = p->b->model->dims;
+  const int64_t grid = (int64_t)(env_ids ? count : p->b->n) * rsr::fd_layout(d.nq, d.nv, d.nu).ncol;      // one wave per (env, column)
+  if (grid > INT32_MAX) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: envs x columns must stay below 2^31");
+  const bool states = (flags & RSR_FD_STATES) != 0;
+  if (const int rc = fd_alloc(p, states, "rsr_physics_transition_fd")) return rc;
+  rsr::RollArgs r{};
+  r.fd = rsr::FdArgs{p->fd, states ? p->fd_states : nullptr, env_ids, eps, flags};
+  return physics_launch(p, nullptr, nullptr, (int)grid, nsteps, rsr::OP_PHYS_ROLLOUT, hip_stream, "rsr_physics_transition_fd", r);
+}
+
+extern "C" int rsr_physics_transition_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
+  if (!p || !dev_ptr || !shape || !stride) return fail(RSR_ERR_ARG, "rsr_physics_transition_view: null argument");
+  const rsr_dims& d = p->b->model->dims;
+  const rsr::FdLayout FL = rsr::fd_layout(d.nq, d.nv, d.nu);
+  const int xrow = FL.ncol * 2 * FL.xw, yrow = FL.ncol * 2 * FL.yw;
+  switch (field) {
+    case RSR_T_COLUMNS: case RSR_T_STATES_X: case RSR_T_STATES_Y: break;
+    default: return fail(RSR_ERR_ARG, "rsr_physics_transition_view: unknown field id");
+  }
+  if (const int rc = fd_alloc(p, field != RSR_T_COLUMNS, "rsr_physics_transition_view")) return rc;
+  if (field == RSR_T_COLUMNS) return view_out(p, p->fd, FL.env, FL.env, dev_ptr, shape, stride);
+  if (field == RSR_T_STATES_X) return view_out(p, p->fd_states, xrow, xrow, dev_ptr, shape, stride);
+  return view_out(p, p->fd_states + (size_t)p->b->n * xrow, yrow, yrow, dev_ptr, shape, stride);
 }

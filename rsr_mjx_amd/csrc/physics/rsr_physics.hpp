@@ -36,11 +36,30 @@ struct Applied {
   const float* xfrc;
   const float* qfrc;
 };
-// rsr_physics_rollout: ctrl [N][T][nu]; trajectory rows [N][T][w], each pointer null = not recorded
+// rsr_physics_transition_fd (rsr_transition.hpp).  Its buffer, per env, floats: [ncol][2 nv + RSR_MAX_SENSORDATA], one row per
+// perturbed coordinate (ncol = 2 nv + nu: qpos tangent, qvel, ctrl): d qpos [nv] | d qvel [nv] | d sensordata [nsd], the rest of
+// the row zeros.  The states buffer (RSR_FD_STATES): the perturbed inputs [N][ncol][2][xw] (qpos | qvel | ctrl), then, y0
+// floats in, the end states [N][ncol][2][yw] (qpos | qvel); index 2: the run (+eps, then -eps or the unperturbed state).
+struct FdLayout { int ncol, w, env, xw, yw; };
+__host__ __device__ inline FdLayout fd_layout(int nq, int nv, int nu) {
+  FdLayout f;
+  f.ncol = 2 * nv + nu; f.w = 2 * nv + RSR_MAX_SENSORDATA; f.env = f.ncol * f.w; f.xw = nq + nv + nu; f.yw = nq + nv;
+  return f;
+}
+struct FdArgs {
+  float* out;           // the transition buffer [N][FdLayout::env]; null: the launch is a rollout
+  float* states;        // the states buffer, or null: not kept
+  const int* ids;       // [grid / ncol] the envs to run, or null: env = workgroup index / ncol
+  float eps;
+  int flags;            // RSR_FD_*
+};
+// rsr_physics_rollout: ctrl [N][T][nu]; trajectory rows [N][T][w], each pointer null = not recorded.  fd: the arguments of
+// rsr_physics_transition_fd, which rides on OP_PHYS_ROLLOUT until it gets an op of its own (launch_physics).
 struct RollArgs {
   const float* ctrl;
   int T;
   float *qpos, *qvel, *time, *aforce, *ncon, *sd;
+  FdArgs fd;
 };
 
 // rsr_physics_dynamics (rsr_dynamics.hpp).  Its buffer, per env, floats: qM [nv*nv] | qfrc_bias [nv] | qfrc_passive [nv] |

@@ -1,6 +1,7 @@
 // rsr_physics_kernels.hpp -- the physics-level kernels (include/rsr_physics.h): each family unit instantiates them for its Dims,
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
-// forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp) and constraint_kernel (rsr_constraint.hpp); all but dynamics_kernel
+// forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp), constraint_kernel (rsr_constraint.hpp) and transition_kernel
+// (rsr_transition.hpp); all but dynamics_kernel
 // are instantiated plain and with applied forces: the applied kernels take the handle's Applied buffers as one more argument and
 // pass forward<C> their env's rows as its force stage (rsr_applied.hpp).
 #pragma once
@@ -9,6 +10,7 @@
 #include "rsr_applied.hpp"
 #include "rsr_dynamics.hpp"
 #include "rsr_constraint.hpp"
+#include "rsr_transition.hpp"
 
 namespace rsr {
 
@@ -165,7 +167,14 @@ int launch_physics(int op, const Launch& x) {
   switch (op) {
     case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, true, WAVES>, x.p);
     case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, false, WAVES>, x.p);
-    case OP_PHYS_ROLLOUT: return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
+    case OP_PHYS_ROLLOUT:
+      // rsr_physics_transition_fd rides on this op (r.fd.out set; grid = envs x columns): enum Op and struct Launch are part of the
+      // sources the parity envelopes were measured on, so an op of its own comes with their next re-measurement
+      if (x.r.fd.out) {      // (its LDS: Smem<C> and the words the first run's end state waits in)
+        auto gofd = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(64), fd_lds_bytes<C>(), x.stream, x.dm, x.L, x.a, args...); return 0; };
+        return ap ? gofd(transition_kernel<C, WAVES, Applied>, x.p, x.r.fd, x.ap) : gofd(transition_kernel<C, WAVES>, x.p, x.r.fd);
+      }
+      return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
     case OP_PHYS_DYNAMICS: return go(dynamics_kernel<C, WAVES>, x.d);      // (applied forces enter none of its outputs)
     case OP_PHYS_CONSTRAINT: return ap ? go(constraint_kernel<C, WAVES, Applied>, x.c, x.ap) : go(constraint_kernel<C, WAVES>, x.c);
     default: return -1;

@@ -11,6 +11,8 @@
                                                                                            record's current state)
     data.efc_force / qfrc_constraint / mj_contactForce ->  Physics.constraint_forces()    (one mjx.forward at the record's current
                                                                                            state; Physics.contact_forces())
+    mjd_transitionFD / jax.jacobian(mjx.step)    ->  Physics.transition_fd()              (finite differences of step at a given
+                                                                                           eps: fd_A, fd_B, fd_C, fd_D)
 
 `Physics(env)` shares the batch of a BatchedEnv (Airbot cube / sf / T-shape, Go2 joystick, handstand / footstand): the same model,
 the same per-env domain randomisation, the same record and the same stream.  The pipeline fields it exposes are the record's own
@@ -78,6 +80,8 @@ class Physics:
         self._dyn: Optional[Dict[str, Any]] = None
         # the constraint buffer's views (constraint_forces): likewise
         self._con: Optional[Dict[str, Any]] = None
+        # the transition buffer's and the states buffer's views (transition_fd): likewise
+        self._fd: Dict[str, Any] = {}
         if sensors is not None:
             self.set_sensors(sensors)
 
@@ -291,6 +295,63 @@ class Physics:
         return dict(ncon=v["ncon"][:, 0].to(torch.int32), dist=c[:, :, 0], pos=c[:, :, 1:4], normal=c[:, :, 4:7],
                     geom1=c[:, :, 7].to(torch.int32), geom2=c[:, :, 8].to(torch.int32),
                     normal_force=w[:, :, 0], force=w[:, :, 1:4], torque=w[:, :, 4:7])
+
+    def _fd_view(self, name: str):
+        """[N, ncol, row] view of the transition buffer ("columns") or of one half of the states buffer, fetched on first use"""
+        if name not in self._fd:
+            d = self.dims
+            ncol = 2 * d.nv + d.nu
+            self._fd[name] = self._fetch("rsr_physics_transition_view", _lib.TRANSITION_FIELDS.index(name)).unflatten(1, (ncol, -1))
+        return self._fd[name]
+
+    def _fd_block(self, rows: str, cols: str):
+        """A block of [A B; C D]: the buffer holds one row per column of the matrix, so the block is a transposed view"""
+        d, nsd = self.dims, self.nsensordata
+        r = slice(0, 2 * d.nv) if rows == "x" else slice(2 * d.nv, 2 * d.nv + nsd)
+        c = slice(0, 2 * d.nv) if cols == "x" else slice(2 * d.nv, 2 * d.nv + d.nu)
+        return self._fd_view("columns")[:, c, r].transpose(1, 2)
+
+    # outputs of transition_fd(): views of the handle's transition buffer, zeros until the first call.  Rows and columns of x are
+    # the tangent space of (qpos, qvel): nv + nv.  fd_C / fd_D follow the sensor table of the moment they are read.
+    fd_A = property(lambda self: self._fd_block("x", "x"), doc="[N, 2nv, 2nv] d next (qpos, qvel) / d (qpos, qvel)")
+    fd_B = property(lambda self: self._fd_block("x", "u"), doc="[N, 2nv, nu] d next (qpos, qvel) / d ctrl")
+    fd_C = property(lambda self: self._fd_block("s", "x"), doc="[N, nsensordata, 2nv] d sensordata / d (qpos, qvel)")
+    fd_D = property(lambda self: self._fd_block("s", "u"), doc="[N, nsensordata, nu] d sensordata / d ctrl")
+    fd_x = property(lambda self: self._fd_view("states_x").unflatten(2, (2, -1)),
+                    doc="[N, ncol, 2, nq+nv+nu] keep_states: the perturbed qpos, qvel, ctrl of each column's two runs")
+    fd_y = property(lambda self: self._fd_view("states_y").unflatten(2, (2, -1)),
+                    doc="[N, ncol, 2, nq+nv] keep_states: the end state qpos, qvel of each column's two runs")
+
+    def transition_fd(self, env_ids=None, nsteps: Optional[int] = None, eps: float = 1e-3, centered: bool = True,
+                      keep_states: bool = False) -> None:
+        """mjd_transitionFD: finite differences of step(ctrl, nsteps) (default n_substeps) about the record's current qpos / qvel /
+        ctrl, one launch with one wave per (env, column): fills fd_A, fd_B and, with a sensor table, fd_C, fd_D of the envs
+        `env_ids` (default: all).  Column k < nv moves qpos in its tangent space (mj_integratePos: a free joint's rotation
+        multiplies its quaternion on the right), the next nv move qvel, the last nu move ctrl, each by +-eps (centered) or by +eps
+        against the unperturbed step; ctrl is moved wherever it stands, its range is not consulted (MuJoCo nudges it).  Each run
+        starts from the record's qacc_warmstart and is bit for bit the step it stands for, per-env leaves and applied forces
+        included.  Rows of qpos are mj_differentiatePos of the two end states.  These are differences at `eps`, not derivatives:
+        friction loss, limits and contacts make the step piecewise smooth, and the result depends on eps.  keep_states also
+        records the runs' inputs and end states (fd_x, fd_y).  Writes nothing else: not the record, the side buffer, sensordata,
+        the dynamics or the constraint buffer."""
+        import math
+        import torch
+        nsteps = self.n_substeps if nsteps is None else int(nsteps)
+        if nsteps < 1:
+            raise ValueError(f"transition_fd: nsteps must be >= 1, got {nsteps}")
+        eps = float(eps)
+        if not (math.isfinite(eps) and eps > 0.0):
+            raise ValueError(f"transition_fd: eps must be finite and > 0, got {eps}")
+        flags = (_lib.FD_CENTERED if centered else 0) | (_lib.FD_STATES if keep_states else 0)
+        if env_ids is None:
+            _lib.check(_lib.lib().rsr_physics_transition_fd(self._h, None, 0, nsteps, eps, flags, self._stream()))
+            return
+        ids = self._ids(env_ids, "transition_fd")
+        if ids.numel() == 0:
+            return
+        ids32 = ids.to(torch.int32).contiguous()
+        self._fd_ids_in = ids32                    # kept alive until the next call (the launch is asynchronous)
+        _lib.check(_lib.lib().rsr_physics_transition_fd(self._h, C.c_void_p(ids32.data_ptr()), ids.numel(), nsteps, eps, flags, self._stream()))
 
     def rollout(self, ctrl, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), qpos0=None, qvel0=None,
                 ctrl0=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:

@@ -5,8 +5,12 @@ dof), for the step and for a rollout of --rollout-T control steps, beside the pl
 rsr_physics_dynamics launch without Jacobian sites and with the family's example sites, beside ms per rsr_physics_forward launch
 on the same batch.  --constraint adds ms per rsr_physics_constraint launch (Physics.constraint_forces) beside ms per
 rsr_physics_forward launch, interleaved in blocks on the same batch and state (of the state, forward moves qacc_warmstart only).
+--transition is a mode of its own: per family and for N = 64, 1024 and 8192 envs it times Physics.transition_fd at its defaults
+beside the 2 ncol Physics.step launches that do the same work from Python, each after a restore of the record, in alternating
+blocks on the same batch and state, and writes one row per family to profiles/transition_rates_<N>.jsonl (--out-dir).
 Usage: python tools/physics_rates.py [--envs 8192] [--steps 50] [--warmup 10] [--applied] [--dynamics] [--constraint]
-                                     [--rollout-T 16] [--out FILE]"""
+                                     [--rollout-T 16] [--out FILE]
+       python tools/physics_rates.py --transition [--transition-envs 64,1024,8192] [--families ...] [--out-dir profiles]"""
 from __future__ import annotations
 
 import argparse
@@ -17,6 +21,76 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _make_env(kind, n):
+    """(envdef, env batch with the family's randomisation, action scale)"""
+    from rsr_mjx_amd import prng
+    from rsr_mjx_amd.envs import airbot, go2
+    if kind in ("cube", "tshape"):
+        envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
+        dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n)) if kind == "cube" else None
+        scale = 1.0
+    else:
+        envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind])
+        dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n))
+        scale = 0.5
+    return envdef, envdef.batched(n, episode_length=1000, auto_reset=True, randomization=dr), scale
+
+
+def transition_rates(args) -> None:
+    """ms per Physics.transition_fd() beside ms for the 2 ncol Physics.step launches it replaces (each after a record restore),
+    from the states 10 env steps reach; blocks alternate (A B A B A B) and the medians are reported."""
+    import torch
+    from bench import csrc_sha16
+    from rsr_mjx_amd import prng
+    from rsr_mjx_amd.physics import Physics
+    pipe = ("qpos", "qvel", "ctrl", "qacc_warmstart", "time", "xpos", "site_xpos")
+    for n in [int(v) for v in args.transition_envs.split(",")]:
+        rows = []
+        for kind in args.families.split(","):
+            envdef, env, scale = _make_env(kind, n)
+            env.reset(prng.split(prng.PRNGKey(0), n))
+            rng = np.random.default_rng(0)
+            for _ in range(10):
+                env.step(None, np.clip(rng.normal(size=(n, env.dims.nu)) * scale, -1, 1).astype(np.float32))
+            phys = Physics(env)
+            ncol = 2 * env.dims.nv + env.dims.nu
+            saved = {k: env.view(k).clone() for k in pipe}
+            ctrl = saved["ctrl"].clone()
+
+            def by_steps():
+                for _ in range(2 * ncol):
+                    for k in pipe:
+                        env.view(k).copy_(saved[k])
+                    phys.step(ctrl)
+
+            def block(fn, reps):
+                env.timing_begin()
+                for _ in range(reps):
+                    fn()
+                return env.timing_end()[0] / reps
+            phys.transition_fd()
+            by_steps()
+            fd, st = [], []
+            for _ in range(3):
+                fd.append(block(phys.transition_fd, args.transition_reps))
+                st.append(block(by_steps, 1))
+            for k in pipe:
+                env.view(k).copy_(saved[k])
+            torch.cuda.synchronize()
+            row = dict(family=kind, num_envs=n, n_frames=int(env.dims.n_frames), ncol=ncol, eps=1e-3, centered=True,
+                       transition_fd_ms=float(np.median(fd)), step_launches=2 * ncol, steps_ms=float(np.median(st)),
+                       transition_fd_ms_blocks=fd, steps_ms_blocks=st, steps_over_transition_fd=float(np.median(st) / np.median(fd)),
+                       finite=bool(torch.isfinite(phys.fd_A).all() and torch.isfinite(phys.fd_B).all()), csrc_sha16=csrc_sha16())
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            del phys, env, saved
+            torch.cuda.synchronize()
+        os.makedirs(args.out_dir, exist_ok=True)
+        with open(os.path.join(args.out_dir, f"transition_rates_{n}.jsonl"), "w") as fh:
+            for row in rows:
+                fh.write(json.dumps(row) + "\n")
 
 
 def main() -> None:
@@ -30,7 +104,14 @@ def main() -> None:
     ap.add_argument("--constraint", action="store_true")
     ap.add_argument("--rollout-T", type=int, default=16)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--transition", action="store_true")
+    ap.add_argument("--transition-envs", default="64,1024,8192")
+    ap.add_argument("--transition-reps", type=int, default=5)
+    ap.add_argument("--out-dir", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles"))
     args = ap.parse_args()
+    if args.transition:
+        transition_rates(args)
+        return
     import torch
     from rsr_mjx_amd import prng
     from rsr_mjx_amd.envs import airbot, go2
