@@ -20,13 +20,28 @@ struct rsr_physics {
   float* xfrc = nullptr;  // data.xfrc_applied [n][nbody*6], allocated on the first rsr_physics_set_applied(p, 1)
   float* qfrc = nullptr;  // data.qfrc_applied [n][nv]
   bool applied = false;   // launches take the applied kernels
-  float* dyn = nullptr;   // the dynamics buffer [n][DynLayout::stride], allocated on first use (dyn_alloc)
+  float* dyn = nullptr;   // the dynamics buffer [n][DynLayout::stride], allocated on first use (dyn_buffers)
   int* jac_sites = nullptr;  // [RSR_MAX_JAC_SITES] the Jacobian sites (device)
   int njac = 0;
-  float* con = nullptr;   // the constraint buffer [n][ConLayout::stride], allocated on first use (con_alloc)
-  float* fd = nullptr;    // the transition buffer [n][FdLayout::env], allocated on first use (fd_alloc)
-  float* fd_states = nullptr;  // the states buffer of RSR_FD_STATES, allocated on first request (fd_alloc)
+  float* con = nullptr;   // the constraint buffer [n][ConLayout::stride], allocated on first use (con_buffer)
+  float* fd = nullptr;    // the transition buffer [n][FdLayout::env], allocated on first use (fd_buffers)
+  float* fd_states = nullptr;  // the states buffer of RSR_FD_STATES, allocated on first request (fd_buffers)
 };
+
+// `*slot`, a buffer of the handle, on first use: `bytes` of device memory, zeroed; once there it never moves.  A failure is reported
+// as `who`'s, with the buffer's name `what`, and leaves the slot null.
+template <class T>
+static int zeroed_once(rsr_physics* p, T** slot, size_t bytes, const char* what, const char* who) {
+  if (*slot) return RSR_OK;
+  HIPCHK(hipSetDevice(p->b->device));
+  T* buf = nullptr;
+  if (hipMalloc(&buf, bytes) != hipSuccess) return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(" + what + ")");
+  if (hipMemset(buf, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(buf); return fail(RSR_ERR_HIP, std::string(who) + ": hipMemset");
+  }
+  *slot = buf;
+  return RSR_OK;
+}
 
 extern "C" int rsr_physics_create(rsr_batch* b, rsr_physics** out) {
   if (!b || !out) return fail(RSR_ERR_ARG, "rsr_physics_create: null argument");
@@ -35,15 +50,11 @@ extern "C" int rsr_physics_create(rsr_batch* b, rsr_physics** out) {
   rsr_physics* p = new rsr_physics();
   p->b = b;
   p->PL = rsr::phys_layout(d.nv, d.nu, d.nbody, d.ncon_max);
-  const size_t bytes = (size_t)b->n * p->PL.stride * sizeof(float);
-  if (hipMalloc(&p->out, bytes) != hipSuccess) { p->out = nullptr; rsr_physics_destroy(p); return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(side buffer)"); }
-  if (hipMemset(p->out, 0, bytes) != hipSuccess) { rsr_physics_destroy(p); return fail(RSR_ERR_HIP, "rsr_physics_create: hipMemset"); }
-  const size_t sd_bytes = (size_t)b->n * RSR_MAX_SENSORDATA * sizeof(float);
-  if (hipMalloc(&p->sd, sd_bytes) != hipSuccess) { p->sd = nullptr; rsr_physics_destroy(p); return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(sensordata)"); }
-  if (hipMalloc(&p->sens_el, RSR_MAX_SENSORDATA * sizeof(int4)) != hipSuccess) {
-    p->sens_el = nullptr; rsr_physics_destroy(p); return fail(RSR_ERR_NOMEM, "rsr_physics_create: hipMalloc(sensor table)");
-  }
-  if (hipMemset(p->sd, 0, sd_bytes) != hipSuccess) { rsr_physics_destroy(p); return fail(RSR_ERR_HIP, "rsr_physics_create: hipMemset"); }
+  const char* who = "rsr_physics_create";
+  int rc = zeroed_once(p, &p->out, (size_t)b->n * p->PL.stride * sizeof(float), "side buffer", who);
+  if (!rc) rc = zeroed_once(p, &p->sd, (size_t)b->n * RSR_MAX_SENSORDATA * sizeof(float), "sensordata", who);
+  if (!rc) rc = zeroed_once(p, &p->sens_el, RSR_MAX_SENSORDATA * sizeof(int4), "sensor table", who);
+  if (rc) { rsr_physics_destroy(p); return rc; }
   *out = p;
   return RSR_OK;
 }
@@ -64,40 +75,50 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
   delete p;
 }
 
-// One physics op on `grid` envs (ids: which, or null: the first `grid`), the handle's buffers as every op's arguments; reports the launch error as `who`.
-static int physics_launch(rsr_physics* ph, const float* ctrl, const int* ids, int grid, int nsteps, int op, void* hip_stream, const char* who,
-                          const rsr::RollArgs& r = rsr::RollArgs{}) {
-  rsr_batch* b = ph->b;
-  HIPCHK(hipSetDevice(b->device));
-  rsr::Launch x = launch_args(b, hip_stream);
+// The arguments of a physics op on `grid` envs (ids: which, or null: the first `grid`): the handle's buffers as every op's; the
+// caller adds the one struct its op owns (r, fd).
+static rsr::Launch physics_args(rsr_physics* ph, const float* ctrl, const int* ids, int grid, int nsteps, void* hip_stream) {
+  rsr::Launch x = launch_args(ph->b, hip_stream);
   x.grid = grid;
   x.a.debug = nullptr;
   x.p = rsr::PhysArgs{ctrl, ph->out, ids, nsteps, ph->sd, rsr::SensArgs{ph->sens_el, ph->nsd, ph->acc_site}};
-  x.r = r;
   x.d = rsr::DynArgs{ph->dyn, ids, ph->jac_sites, ph->njac};
   x.c = rsr::ConArgs{ph->con, ids};
   if (ph->applied) x.ap = rsr::Applied{ph->xfrc, ph->qfrc};
-  if (launch(b, op, x) < 0) return fail(RSR_ERR_UNSUPPORTED, std::string(who) + ": the model's kernels have no such op");
+  return x;
+}
+
+// sends one physics op; reports the launch error as `who`
+static int physics_launch(rsr_physics* ph, int op, const rsr::Launch& x, const char* who) {
+  HIPCHK(hipSetDevice(ph->b->device));
+  if (launch(ph->b, op, x) < 0) return fail(RSR_ERR_UNSUPPORTED, std::string(who) + ": the model's kernels have no such op");
   { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
+  return RSR_OK;
+}
+
+// the envs an env-list entry point runs, *n: the `count` listed ones, or with env_ids null every env of the batch
+static int env_count(const rsr_physics* p, const int32_t* env_ids, int count, const char* who, int* n) {
+  if (env_ids && count < 1) return fail(RSR_ERR_ARG, std::string(who) + ": count < 1 with env_ids");
+  *n = env_ids ? count : p->b->n;
   return RSR_OK;
 }
 
 extern "C" int rsr_physics_step(rsr_physics* p, const float* ctrl, int nsteps, void* hip_stream) {
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_step: null handle");
   if (nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_step: nsteps must be >= 1");
-  const int rc = physics_launch(p, ctrl, nullptr, p->b->n, nsteps, rsr::OP_PHYS_STEP, hip_stream, "rsr_physics_step");
+  const int rc = physics_launch(p, rsr::OP_PHYS_STEP, physics_args(p, ctrl, nullptr, p->b->n, nsteps, hip_stream), "rsr_physics_step");
   if (rc == RSR_OK && p->b->timing) p->b->launches++;
   return rc;
 }
 
 extern "C" int rsr_physics_forward(rsr_physics* p, void* hip_stream) {
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_forward: null handle");
-  return physics_launch(p, nullptr, nullptr, p->b->n, 1, rsr::OP_PHYS_FORWARD, hip_stream, "rsr_physics_forward");
+  return physics_launch(p, rsr::OP_PHYS_FORWARD, physics_args(p, nullptr, nullptr, p->b->n, 1, hip_stream), "rsr_physics_forward");
 }
 
 extern "C" int rsr_physics_forward_envs(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream) {
   if (!p || !env_ids || count < 1) return fail(RSR_ERR_ARG, "rsr_physics_forward_envs: null handle / ids or count < 1");
-  return physics_launch(p, nullptr, env_ids, count, 1, rsr::OP_PHYS_FORWARD, hip_stream, "rsr_physics_forward_envs");
+  return physics_launch(p, rsr::OP_PHYS_FORWARD, physics_args(p, nullptr, env_ids, count, 1, hip_stream), "rsr_physics_forward_envs");
 }
 
 // a view's answer: `w` floats per env from `ptr`, the envs `row` floats apart
@@ -167,12 +188,13 @@ extern "C" int rsr_physics_set_sensors(rsr_physics* p, const int32_t* table, int
 extern "C" int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int nsteps, const rsr_rollout_out* out, void* hip_stream) {
   if (!p || !ctrl) return fail(RSR_ERR_ARG, "rsr_physics_rollout: null handle or ctrl");
   if (T < 1 || nsteps < 1 || (int64_t)T * nsteps > INT32_MAX) return fail(RSR_ERR_ARG, "rsr_physics_rollout: T and nsteps must be >= 1 (T * nsteps < 2^31)");
-  rsr::RollArgs r{ctrl, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  rsr::Launch x = physics_args(p, nullptr, nullptr, p->b->n, nsteps, hip_stream);
+  rsr::RollArgs& r = x.r = rsr::RollArgs{ctrl, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (out) {
     if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_rollout: sensordata requested with no sensor table set");
     r.qpos = out->qpos; r.qvel = out->qvel; r.time = out->time; r.aforce = out->actuator_force; r.ncon = out->ncon; r.sd = out->sensordata;
   }
-  const int rc = physics_launch(p, nullptr, nullptr, p->b->n, nsteps, rsr::OP_PHYS_ROLLOUT, hip_stream, "rsr_physics_rollout", r);
+  const int rc = physics_launch(p, rsr::OP_PHYS_ROLLOUT, x, "rsr_physics_rollout");
   if (rc == RSR_OK && p->b->timing) p->b->launches++;
   return rc;
 }
@@ -209,19 +231,13 @@ extern "C" int rsr_physics_applied_view(rsr_physics* p, int field, void** dev_pt
   }
 }
 
-// the dynamics buffer and the site table, on first use (zeroed)
-static int dyn_alloc(rsr_physics* p, const char* who) {
-  if (p->dyn) return RSR_OK;
-  const size_t bytes = (size_t)p->b->n * rsr::dyn_layout(p->b->model->dims.nv).stride * sizeof(float);
-  HIPCHK(hipSetDevice(p->b->device));
-  float* dyn = nullptr; int* sites = nullptr;
-  if (hipMalloc(&dyn, bytes) != hipSuccess) return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(dynamics buffer)");
-  if (hipMalloc(&sites, RSR_MAX_JAC_SITES * sizeof(int)) != hipSuccess) { (void)hipFree(dyn); return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(site table)"); }
-  if (hipMemset(dyn, 0, bytes) != hipSuccess || hipMemset(sites, 0, RSR_MAX_JAC_SITES * sizeof(int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-    (void)hipFree(dyn); (void)hipFree(sites); return fail(RSR_ERR_HIP, std::string(who) + ": hipMemset");
-  }
-  p->dyn = dyn; p->jac_sites = sites;
-  return RSR_OK;
+// the dynamics buffer and the site table, on first use: both or neither
+static int dyn_buffers(rsr_physics* p, const char* who) {
+  const bool had = p->dyn != nullptr;
+  if (const int rc = zeroed_once(p, &p->dyn, (size_t)p->b->n * rsr::dyn_layout(p->b->model->dims.nv).stride * sizeof(float), "dynamics buffer", who)) return rc;
+  const int rc = zeroed_once(p, &p->jac_sites, RSR_MAX_JAC_SITES * sizeof(int), "site table", who);
+  if (rc && !had) { (void)hipFree(p->dyn); p->dyn = nullptr; }
+  return rc;
 }
 
 extern "C" int rsr_physics_set_jac_sites(rsr_physics* p, const int32_t* site_ids, int nsite) {
@@ -231,7 +247,7 @@ extern "C" int rsr_physics_set_jac_sites(rsr_physics* p, const int32_t* site_ids
   for (int k = 0; k < nsite; ++k)
     if (site_ids[k] < 0 || site_ids[k] >= p->b->model->dims.nsite)
       return fail(RSR_ERR_ARG, "rsr_physics_set_jac_sites: site " + std::to_string(k) + ": site id out of range");
-  if (const int rc = dyn_alloc(p, "rsr_physics_set_jac_sites")) return rc;
+  if (const int rc = dyn_buffers(p, "rsr_physics_set_jac_sites")) return rc;
   HIPCHK(hipSetDevice(p->b->device));
   HIPCHK(hipDeviceSynchronize());               // launches in flight read the table
   if (nsite > 0) HIPCHK(hipMemcpy(p->jac_sites, site_ids, nsite * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -241,9 +257,10 @@ extern "C" int rsr_physics_set_jac_sites(rsr_physics* p, const int32_t* site_ids
 
 extern "C" int rsr_physics_dynamics(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream) {
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_dynamics: null handle");
-  if (env_ids && count < 1) return fail(RSR_ERR_ARG, "rsr_physics_dynamics: count < 1 with env_ids");
-  if (const int rc = dyn_alloc(p, "rsr_physics_dynamics")) return rc;
-  return physics_launch(p, nullptr, env_ids, env_ids ? count : p->b->n, 1, rsr::OP_PHYS_DYNAMICS, hip_stream, "rsr_physics_dynamics");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, "rsr_physics_dynamics", &n)) return rc;
+  if (const int rc = dyn_buffers(p, "rsr_physics_dynamics")) return rc;
+  return physics_launch(p, rsr::OP_PHYS_DYNAMICS, physics_args(p, nullptr, env_ids, n, 1, hip_stream), "rsr_physics_dynamics");
 }
 
 extern "C" int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
@@ -260,30 +277,22 @@ extern "C" int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_p
     case RSR_D_JAC_SITE_XPOS: off = DL.sxpos; w = p->njac * 3; break;
     default: return fail(RSR_ERR_ARG, "rsr_physics_dynamics_view: unknown field id");
   }
-  if (const int rc = dyn_alloc(p, "rsr_physics_dynamics_view")) return rc;
+  if (const int rc = dyn_buffers(p, "rsr_physics_dynamics_view")) return rc;
   return view_out(p, p->dyn + off, w, DL.stride, dev_ptr, shape, stride);
 }
 
-// the constraint buffer, on first use (zeroed)
-static int con_alloc(rsr_physics* p, const char* who) {
-  if (p->con) return RSR_OK;
+// the constraint buffer, on first use
+static int con_buffer(rsr_physics* p, const char* who) {
   const rsr_dims& d = p->b->model->dims;
-  const size_t bytes = (size_t)p->b->n * rsr::con_layout(d.nv, d.nefc_max, d.ncon_max).stride * sizeof(float);
-  HIPCHK(hipSetDevice(p->b->device));
-  float* con = nullptr;
-  if (hipMalloc(&con, bytes) != hipSuccess) return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(constraint buffer)");
-  if (hipMemset(con, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-    (void)hipFree(con); return fail(RSR_ERR_HIP, std::string(who) + ": hipMemset");
-  }
-  p->con = con;
-  return RSR_OK;
+  return zeroed_once(p, &p->con, (size_t)p->b->n * rsr::con_layout(d.nv, d.nefc_max, d.ncon_max).stride * sizeof(float), "constraint buffer", who);
 }
 
 extern "C" int rsr_physics_constraint(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream) {
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_constraint: null handle");
-  if (env_ids && count < 1) return fail(RSR_ERR_ARG, "rsr_physics_constraint: count < 1 with env_ids");
-  if (const int rc = con_alloc(p, "rsr_physics_constraint")) return rc;
-  return physics_launch(p, nullptr, env_ids, env_ids ? count : p->b->n, 1, rsr::OP_PHYS_CONSTRAINT, hip_stream, "rsr_physics_constraint");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, "rsr_physics_constraint", &n)) return rc;
+  if (const int rc = con_buffer(p, "rsr_physics_constraint")) return rc;
+  return physics_launch(p, rsr::OP_PHYS_CONSTRAINT, physics_args(p, nullptr, env_ids, n, 1, hip_stream), "rsr_physics_constraint");
 }
 
 extern "C" int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
@@ -301,30 +310,14 @@ extern "C" int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev
     case RSR_C_CONTACT_WRENCH: off = CL.wrench; w = 7 * d.ncon_max; break;
     default: return fail(RSR_ERR_ARG, "rsr_physics_constraint_view: unknown field id");
   }
-  if (const int rc = con_alloc(p, "rsr_physics_constraint_view")) return rc;
+  if (const int rc = con_buffer(p, "rsr_physics_constraint_view")) return rc;
   return view_out(p, p->con + off, w, CL.stride, dev_ptr, shape, stride);
 }
 
-// the transition buffer and, with `states`, the states buffer, each on first use (zeroed)
-static int fd_alloc(rsr_physics* p, bool states, const char* who) {
-  if (p->fd && (!states || p->fd_states)) return RSR_OK;
-  const rsr_dims& d = p->b->model->dims;
-  const rsr::FdLayout FL = rsr::fd_layout(d.nq, d.nv, d.nu);
-  HIPCHK(hipSetDevice(p->b->device));
-  auto zeroed = [&](size_t floats, float** out, const char* what) {
-    float* buf = nullptr;
-    if (hipMalloc(&buf, floats * sizeof(float)) != hipSuccess) return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(" + what + ")");
-    if (hipMemset(buf, 0, floats * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-      (void)hipFree(buf); return fail(RSR_ERR_HIP, std::string(who) + ": hipMemset");
-    }
-    *out = buf;
-    return (int)RSR_OK;
-  };
-  if (!p->fd) { if (const int rc = zeroed((size_t)p->b->n * FL.env, &p->fd, "transition buffer")) return rc; }
-  if (states && !p->fd_states) {
-    if (const int rc = zeroed((size_t)p->b->n * FL.ncol * 2 * (FL.xw + FL.yw), &p->fd_states, "states buffer")) return rc;
-  }
-  return RSR_OK;
+// the transition buffer and, with `states`, the states buffer, each on first use
+static int fd_buffers(rsr_physics* p, const rsr::FdLayout& FL, bool states, const char* who) {
+  if (const int rc = zeroed_once(p, &p->fd, (size_t)p->b->n * FL.env * sizeof(float), "transition buffer", who)) return rc;
+  return states ? zeroed_once(p, &p->fd_states, (size_t)p->b->n * FL.ncol * 2 * (FL.xw + FL.yw) * sizeof(float), "states buffer", who) : RSR_OK;
 }
 
 extern "C" int rsr_physics_transition_fd(rsr_physics* p, const int32_t* env_ids, int count, int nsteps, float eps, int flags, void* hip_stream) {
@@ -332,15 +325,17 @@ extern "C" int rsr_physics_transition_fd(rsr_physics* p, const int32_t* env_ids,
   if (nsteps < 1 || nsteps > INT32_MAX / 2) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: nsteps must lie in [1, 2^30)");
   if (!std::isfinite(eps) || !(eps > 0.0f)) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: eps must be finite and > 0");
   if (flags & ~(RSR_FD_CENTERED | RSR_FD_STATES)) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: unknown flag bits");
-  if (env_ids && count < 1) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: count < 1 with env_ids");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, "rsr_physics_transition_fd", &n)) return rc;
   const rsr_dims& d = p->b->model->dims;
-  const int64_t grid = (int64_t)(env_ids ? count : p->b->n) * rsr::fd_layout(d.nq, d.nv, d.nu).ncol;      // one wave per (env, column)
+  const rsr::FdLayout FL = rsr::fd_layout(d.nq, d.nv, d.nu);
+  const int64_t grid = (int64_t)n * FL.ncol;      // one wave per (env, column)
   if (grid > INT32_MAX) return fail(RSR_ERR_ARG, "rsr_physics_transition_fd: envs x columns must stay below 2^31");
   const bool states = (flags & RSR_FD_STATES) != 0;
-  if (const int rc = fd_alloc(p, states, "rsr_physics_transition_fd")) return rc;
-  rsr::RollArgs r{};
-  r.fd = rsr::FdArgs{p->fd, states ? p->fd_states : nullptr, env_ids, eps, flags};
-  return physics_launch(p, nullptr, nullptr, (int)grid, nsteps, rsr::OP_PHYS_ROLLOUT, hip_stream, "rsr_physics_transition_fd", r);
+  if (const int rc = fd_buffers(p, FL, states, "rsr_physics_transition_fd")) return rc;
+  rsr::Launch x = physics_args(p, nullptr, nullptr, (int)grid, nsteps, hip_stream);
+  x.fd = rsr::FdArgs{p->fd, states ? p->fd_states : nullptr, env_ids, eps, flags};
+  return physics_launch(p, rsr::OP_PHYS_TRANSITION, x, "rsr_physics_transition_fd");
 }
 
 extern "C" int rsr_physics_transition_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
@@ -352,7 +347,7 @@ extern "C" int rsr_physics_transition_view(rsr_physics* p, int field, void** dev
     case RSR_T_COLUMNS: case RSR_T_STATES_X: case RSR_T_STATES_Y: break;
     default: return fail(RSR_ERR_ARG, "rsr_physics_transition_view: unknown field id");
   }
-  if (const int rc = fd_alloc(p, field != RSR_T_COLUMNS, "rsr_physics_transition_view")) return rc;
+  if (const int rc = fd_buffers(p, FL, field != RSR_T_COLUMNS, "rsr_physics_transition_view")) return rc;
   if (field == RSR_T_COLUMNS) return view_out(p, p->fd, FL.env, FL.env, dev_ptr, shape, stride);
   if (field == RSR_T_STATES_X) return view_out(p, p->fd_states, xrow, xrow, dev_ptr, shape, stride);
   return view_out(p, p->fd_states + (size_t)p->b->n * xrow, yrow, yrow, dev_ptr, shape, stride);

@@ -1,4 +1,4 @@
-// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics and constraint buffer) and the launch arguments of its ops,
+// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics, constraint and transition buffer) and the launch arguments of its ops,
 // one struct per op of rsr_launch.hpp that needs its own (host and device).
 #pragma once
 #include "../../../include/rsr_physics.h"
@@ -46,20 +46,19 @@ __host__ __device__ inline FdLayout fd_layout(int nq, int nv, int nu) {
   f.ncol = 2 * nv + nu; f.w = 2 * nv + RSR_MAX_SENSORDATA; f.env = f.ncol * f.w; f.xw = nq + nv + nu; f.yw = nq + nv;
   return f;
 }
+// The launch arguments of OP_PHYS_TRANSITION (Launch::fd)
 struct FdArgs {
-  float* out;           // the transition buffer [N][FdLayout::env]; null: the launch is a rollout
+  float* out;           // the transition buffer [N][FdLayout::env]
   float* states;        // the states buffer, or null: not kept
   const int* ids;       // [grid / ncol] the envs to run, or null: env = workgroup index / ncol
   float eps;
   int flags;            // RSR_FD_*
 };
-// rsr_physics_rollout: ctrl [N][T][nu]; trajectory rows [N][T][w], each pointer null = not recorded.  fd: the arguments of
-// rsr_physics_transition_fd, which rides on OP_PHYS_ROLLOUT until it gets an op of its own (launch_physics).
+// rsr_physics_rollout: ctrl [N][T][nu]; trajectory rows [N][T][w], each pointer null = not recorded
 struct RollArgs {
   const float* ctrl;
   int T;
   float *qpos, *qvel, *time, *aforce, *ncon, *sd;
-  FdArgs fd;
 };
 
 // rsr_physics_dynamics (rsr_dynamics.hpp).  Its buffer, per env, floats: qM [nv*nv] | qfrc_bias [nv] | qfrc_passive [nv] |

@@ -162,19 +162,15 @@ void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
 // the physics ops of a family's launch entry (rsr_launch.hpp)
 template <class C, int WAVES>
 int launch_physics(int op, const Launch& x) {
-  auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, args...); return 0; };
+  // (the transition's LDS: Smem<C> and the words the first run's end state waits in)
+  const size_t lds = op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>);
+  auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(64), lds, x.stream, x.dm, x.L, x.a, args...); return 0; };
   const bool ap = x.ap.xfrc != nullptr;      // applied forces on
   switch (op) {
     case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, true, WAVES>, x.p);
     case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, false, WAVES>, x.p);
-    case OP_PHYS_ROLLOUT:
-      // rsr_physics_transition_fd rides on this op (r.fd.out set; grid = envs x columns): enum Op and struct Launch are part of the
-      // sources the parity envelopes were measured on, so an op of its own comes with their next re-measurement
-      if (x.r.fd.out) {      // (its LDS: Smem<C> and the words the first run's end state waits in)
-        auto gofd = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(64), fd_lds_bytes<C>(), x.stream, x.dm, x.L, x.a, args...); return 0; };
-        return ap ? gofd(transition_kernel<C, WAVES, Applied>, x.p, x.r.fd, x.ap) : gofd(transition_kernel<C, WAVES>, x.p, x.r.fd);
-      }
-      return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
+    case OP_PHYS_ROLLOUT: return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
+    case OP_PHYS_TRANSITION: return ap ? go(transition_kernel<C, WAVES, Applied>, x.p, x.fd, x.ap) : go(transition_kernel<C, WAVES>, x.p, x.fd);
     case OP_PHYS_DYNAMICS: return go(dynamics_kernel<C, WAVES>, x.d);      // (applied forces enter none of its outputs)
     case OP_PHYS_CONSTRAINT: return ap ? go(constraint_kernel<C, WAVES, Applied>, x.c, x.ap) : go(constraint_kernel<C, WAVES>, x.c);
     default: return -1;

@@ -82,6 +82,8 @@ class Physics:
         self._con: Optional[Dict[str, Any]] = None
         # the transition buffer's and the states buffer's views (transition_fd): likewise
         self._fd: Dict[str, Any] = {}
+        # the env-id tensor of each entry point's last launch (_call_envs)
+        self._ids_in: Dict[str, Any] = {}
         if sensors is not None:
             self.set_sensors(sensors)
 
@@ -154,6 +156,21 @@ class Physics:
         if torch.unique(ids).numel() != ids.numel():
             raise ValueError(f"{who}: env_ids must not repeat")
         return ids
+
+    def _call_envs(self, fn: str, who: str, env_ids, *args, checked: bool = False) -> None:
+        """The library's env-list entry point `fn`(handle, ids, count, *args, stream) for the method `who`: env_ids None runs every
+        env (null, 0), an empty list nothing.  checked: env_ids already went through _ids.  The int32 ids stay alive in `who`'s
+        own slot until its next call: the launch is asynchronous, and another entry point's may follow it at once."""
+        import torch
+        ptr, k = None, 0
+        if env_ids is not None:
+            ids = env_ids if checked else self._ids(env_ids, who)
+            k = ids.numel()
+            if k == 0:
+                return
+            ids32 = self._ids_in[who] = ids.to(torch.int32).contiguous()
+            ptr = C.c_void_p(ids32.data_ptr())
+        _lib.check(getattr(_lib.lib(), fn)(self._h, ptr, k, *args, self._stream()))
 
     def set_applied(self, xfrc=None, qfrc=None, env_ids=None) -> None:
         """data.replace(xfrc_applied=..., qfrc_applied=...): turns applied forces on (zero everywhere the first time) and writes
@@ -241,16 +258,7 @@ class Physics:
         the state after the integration, whereas qacc, xquat and the contacts show the step's last forward pass.  Writes nothing
         else (not the record, the side buffer or sensordata).  Applied forces enter none of the outputs:
         qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator (+ the applied forces the caller set)."""
-        import torch
-        if env_ids is None:
-            _lib.check(_lib.lib().rsr_physics_dynamics(self._h, None, 0, self._stream()))
-            return
-        ids = self._ids(env_ids, "dynamics")
-        if ids.numel() == 0:
-            return
-        ids32 = ids.to(torch.int32).contiguous()
-        self._dyn_ids_in = ids32                   # kept alive until the next call (the launch is asynchronous)
-        _lib.check(_lib.lib().rsr_physics_dynamics(self._h, C.c_void_p(ids32.data_ptr()), ids.numel(), self._stream()))
+        self._call_envs("rsr_physics_dynamics", "dynamics", env_ids)
 
     def _con_views(self) -> Dict[str, Any]:
         if self._con is None:
@@ -272,16 +280,7 @@ class Physics:
         buffer.  Its qacc and contacts are bit for bit those forward() would give on the same record, and
         qM @ constraint_qacc = qfrc_passive - qfrc_bias + qfrc_actuator (+ applied forces) + qfrc_constraint to the solver's
         convergence."""
-        import torch
-        if env_ids is None:
-            _lib.check(_lib.lib().rsr_physics_constraint(self._h, None, 0, self._stream()))
-            return
-        ids = self._ids(env_ids, "constraint_forces")
-        if ids.numel() == 0:
-            return
-        ids32 = ids.to(torch.int32).contiguous()
-        self._con_ids_in = ids32                   # kept alive until the next call (the launch is asynchronous)
-        _lib.check(_lib.lib().rsr_physics_constraint(self._h, C.c_void_p(ids32.data_ptr()), ids.numel(), self._stream()))
+        self._call_envs("rsr_physics_constraint", "constraint_forces", env_ids)
 
     def contact_forces(self) -> Dict[str, Any]:
         """The contacts of the last constraint_forces() with their forces (mj_contactForce, in the world frame), per env and
@@ -335,7 +334,6 @@ class Physics:
         records the runs' inputs and end states (fd_x, fd_y).  Writes nothing else: not the record, the side buffer, sensordata,
         the dynamics or the constraint buffer."""
         import math
-        import torch
         nsteps = self.n_substeps if nsteps is None else int(nsteps)
         if nsteps < 1:
             raise ValueError(f"transition_fd: nsteps must be >= 1, got {nsteps}")
@@ -343,15 +341,7 @@ class Physics:
         if not (math.isfinite(eps) and eps > 0.0):
             raise ValueError(f"transition_fd: eps must be finite and > 0, got {eps}")
         flags = (_lib.FD_CENTERED if centered else 0) | (_lib.FD_STATES if keep_states else 0)
-        if env_ids is None:
-            _lib.check(_lib.lib().rsr_physics_transition_fd(self._h, None, 0, nsteps, eps, flags, self._stream()))
-            return
-        ids = self._ids(env_ids, "transition_fd")
-        if ids.numel() == 0:
-            return
-        ids32 = ids.to(torch.int32).contiguous()
-        self._fd_ids_in = ids32                    # kept alive until the next call (the launch is asynchronous)
-        _lib.check(_lib.lib().rsr_physics_transition_fd(self._h, C.c_void_p(ids32.data_ptr()), ids.numel(), nsteps, eps, flags, self._stream()))
+        self._call_envs("rsr_physics_transition_fd", "transition_fd", env_ids, nsteps, eps, flags)
 
     def rollout(self, ctrl, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), qpos0=None, qvel0=None,
                 ctrl0=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
@@ -441,9 +431,7 @@ class Physics:
         if env_ids is None:
             self.forward()
         else:
-            ids32 = ids.to(torch.int32).contiguous()
-            self._ids_in = ids32
-            _lib.check(_lib.lib().rsr_physics_forward_envs(self._h, C.c_void_p(ids32.data_ptr()), k, self._stream()))
+            self._call_envs("rsr_physics_forward_envs", "set_state", ids, checked=True)
 
     def contacts(self) -> Dict[str, Any]:
         """Active contacts of the last forward pass, per env: ncon [N] and ncon_dropped [N] (int), and per contact slot

@@ -59,19 +59,28 @@ def test_argument_checks_come_before_device_work():
     def body(name):
         b = src[src.index(name + "("):]
         return b[:b.index("\n}\n")]
-    dev = ("hipSetDevice", "hipDeviceSynchronize", "hipMalloc", "hipMemset", "hipMemcpy", "con_alloc", "dyn_alloc", "launch(")
+    dev = ("hipSetDevice", "hipDeviceSynchronize", "hipMalloc", "hipMemset", "hipMemcpy", "zeroed_once", "con_buffer", "dyn_buffers", "launch(")
     first_dev = lambda b: min(b.index(k) for k in dev if k in b)
     call = body("int rsr_physics_constraint")
-    assert call.index("!p)") < first_dev(call) and call.index("count < 1") < first_dev(call)
-    assert call.count("RSR_ERR_ARG") == 2 and "con_alloc(" in call and "OP_PHYS_CONSTRAINT" in call
-    assert "rsr::ConArgs{ph->con, ids}" in body("static int physics_launch")      # the op runs on the handle's buffer
+    assert call.index("!p)") < first_dev(call) and call.index("env_count(") < first_dev(call)
+    count = body("static int env_count")                                     # the shared refusal of a list with count < 1
+    assert 'if (env_ids && count < 1) return fail(RSR_ERR_ARG, std::string(who) + ": count < 1 with env_ids");' in count
+    assert not any(k in count for k in dev)
+    assert call.count("RSR_ERR_ARG") + count.count("RSR_ERR_ARG") == 2 and "con_buffer(" in call and "OP_PHYS_CONSTRAINT" in call
+    assert "rsr::ConArgs{ph->con, ids}" in body("static rsr::Launch physics_args")      # the op runs on the handle's buffer
+    launch = body("static int physics_launch")                               # no defaulted parameter: a prepared Launch
+    assert " = " not in launch[:launch.index(")")] and "const rsr::Launch& x" in launch[:launch.index(")")]
     view = body("int rsr_physics_constraint_view")
     assert view.index("default: return fail(RSR_ERR_ARG") < first_dev(view)
     for f in ("QFRC_CONSTRAINT", "QACC", "EFC_COUNTS", "EFC_FORCE", "NCON", "CONTACT", "CONTACT_WRENCH"):
         assert f"case RSR_C_{f}:" in view, f
-    alloc = body("static int con_alloc")
-    assert "if (p->con) return RSR_OK;" in alloc and "hipMemset(con, 0, bytes)" in alloc      # once, zeroed, never moved
-    assert src.count("p->con = ") == 1
+    alloc = body("static int zeroed_once")                                   # once, zeroed, never moved
+    alloc = alloc[alloc.index("{"):]
+    assert alloc.index("if (*slot) return RSR_OK;") < first_dev(alloc) and "hipMemset(buf, 0, bytes)" in alloc
+    assert alloc.count("*slot = ") == 1 and "p->con = " not in src
+    assert "con_buffer(" in view                                             # by the call or by its view, whichever is first
+    assert "return zeroed_once(p, &p->con, " in body("static int con_buffer") and src.count("&p->con,") == 1      # one size, one place
+    assert src.count("static int zeroed_once(") == 1 and "_alloc" not in src
     destroy = body("void rsr_physics_destroy")
     assert "hipFree(p->con)" in destroy
 
@@ -120,4 +129,5 @@ def test_physics_module_surface():
     src = inspect.getsource(Physics.contact_forces)
     for key in ("ncon=", "dist=", "pos=", "normal=", "geom1=", "geom2=", "normal_force=", "force=", "torque="):
         assert key in src, key
-    assert "rsr_physics_constraint(" in inspect.getsource(Physics.constraint_forces)
+    assert 'self._call_envs("rsr_physics_constraint", "constraint_forces", env_ids)' in inspect.getsource(Physics.constraint_forces)
+    assert "getattr(_lib.lib(), fn)(self._h, ptr, k, *args, self._stream())" in inspect.getsource(Physics._call_envs)

@@ -60,16 +60,24 @@ def test_argument_checks_come_before_device_work():
     def body(name):
         b = src[src.index(name + "("):]
         return b[:b.index("\n}\n")]
-    dev = ("hipSetDevice", "hipDeviceSynchronize", "hipMalloc", "hipMemset", "hipMemcpy", "dyn_alloc", "launch(")
+    dev = ("hipSetDevice", "hipDeviceSynchronize", "hipMalloc", "hipMemset", "hipMemcpy", "zeroed_once", "dyn_buffers", "launch(")
     first_dev = lambda b: min(b.index(k) for k in dev if k in b)
     sites = body("int rsr_physics_set_jac_sites")
     for check in ("!p)", "nsite > RSR_MAX_JAC_SITES", "site_ids[k] >= p->b->model->dims.nsite", "site_ids[k] < 0"):
         assert sites.index(check) < first_dev(sites), check
     assert sites.count("RSR_ERR_ARG") == 3 and first_dev(sites) < sites.index("p->njac = nsite")
     dyn = body("int rsr_physics_dynamics")
-    assert dyn.index("!p)") < first_dev(dyn) and dyn.index("count < 1") < first_dev(dyn)
+    assert dyn.index("!p)") < first_dev(dyn) and dyn.index("env_count(") < first_dev(dyn)
+    assert "count < 1" in body("static int env_count") and not any(k in body("static int env_count") for k in dev)
+    # the buffer and the site table come together, through the one allocation helper: a failure of the second undoes the first
+    bufs = body("static int dyn_buffers")
+    assert "zeroed_once(p, &p->dyn, " in bufs and "zeroed_once(p, &p->jac_sites, " in bufs
+    assert "if (rc && !had) { (void)hipFree(p->dyn); p->dyn = nullptr; }" in bufs
+    assert src.count("&p->dyn,") == 1 and src.count("&p->jac_sites,") == 1
     view = body("int rsr_physics_dynamics_view")
     assert view.index("default: return fail(RSR_ERR_ARG") < first_dev(view)
+    for entry in (sites, dyn, view):
+        assert "dyn_buffers(" in entry
     # the buffer goes with the handle
     destroy = body("void rsr_physics_destroy")
     assert "hipFree(p->dyn)" in destroy and "hipFree(p->jac_sites)" in destroy

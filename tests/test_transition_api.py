@@ -59,20 +59,29 @@ def test_refusals_come_before_device_work():
     def body(name):
         b = src[src.index(name + "("):]
         return b[:b.index("\n}\n")]
-    dev = ("hipSetDevice", "hipDeviceSynchronize", "hipMalloc", "hipMemset", "hipMemcpy", "fd_alloc", "launch(")
+    dev = ("hipSetDevice", "hipDeviceSynchronize", "hipMalloc", "hipMemset", "hipMemcpy", "zeroed_once", "fd_buffers", "launch(")
     first_dev = lambda b: min(b.index(k) for k in dev if k in b)
     call = body("int rsr_physics_transition_fd")
-    for check in ("!p)", "nsteps < 1", "nsteps > INT32_MAX / 2", "std::isfinite(eps)", "eps > 0.0f", "~(RSR_FD_CENTERED | RSR_FD_STATES)", "count < 1"):
+    for check in ("!p)", "nsteps < 1", "nsteps > INT32_MAX / 2", "std::isfinite(eps)", "eps > 0.0f", "~(RSR_FD_CENTERED | RSR_FD_STATES)", "env_count("):
         assert call.index(check) < first_dev(call), check
-    assert call.count("RSR_ERR_ARG") >= 5 and "fd_alloc(" in call
-    assert "OP_PHYS_ROLLOUT" in call and "r.fd = rsr::FdArgs{" in call       # rides on the rollout op
+    count = body("static int env_count")                                     # the shared refusal of a list with count < 1
+    assert 'if (env_ids && count < 1) return fail(RSR_ERR_ARG, std::string(who) + ": count < 1 with env_ids");' in count
+    assert not any(k in count for k in dev)
+    assert call.count("RSR_ERR_ARG") + count.count("RSR_ERR_ARG") >= 5 and "fd_buffers(" in call
+    assert "OP_PHYS_TRANSITION" in call and "x.fd = rsr::FdArgs{" in call and "OP_PHYS_ROLLOUT" not in call      # an op of its own
+    assert "RollArgs" not in call and "x.r" not in call
     view = body("int rsr_physics_transition_view")
     assert view.index("default: return fail(RSR_ERR_ARG") < first_dev(view)
     for f in ("COLUMNS", "STATES_X", "STATES_Y"):
         assert f"RSR_T_{f}" in view, f
-    alloc = body("static int fd_alloc")
-    assert "if (p->fd && (!states || p->fd_states)) return RSR_OK;" in alloc and "hipMemset(buf, 0," in alloc
-    assert "if (states && !p->fd_states)" in alloc                           # the states buffer only on request
+    bufs = body("static int fd_buffers")
+    assert 'zeroed_once(p, &p->fd, ' in bufs and "return states ? zeroed_once(p, &p->fd_states, " in bufs     # the states buffer only on request
+    assert src.count("&p->fd,") == 1 and src.count("&p->fd_states,") == 1 and "p->fd = " not in src and "p->fd_states = " not in src
+    alloc = body("static int zeroed_once")                                   # once, zeroed, never moved; null after a failure
+    alloc = alloc[alloc.index("{"):]
+    assert alloc.index("if (*slot) return RSR_OK;") < first_dev(alloc)
+    assert alloc.count("*slot = ") == 1 and alloc.index("hipMemset(buf, 0, bytes)") < alloc.index("*slot = buf;")
+    assert src.count("static int zeroed_once(") == 1 and "_alloc" not in src
     destroy = body("void rsr_physics_destroy")
     assert "hipFree(p->fd)" in destroy and "hipFree(p->fd_states)" in destroy
 
@@ -80,7 +89,8 @@ def test_refusals_come_before_device_work():
 def test_the_kernel_lives_in_the_physics_layer():
     """transition_kernel is a file of its own under csrc/physics that calls the step's stages instead of restating them: one
     forward<C> in the loop over the two runs' substeps (or two calls), no inline assembly, no read-modify-write memory
-    operations; no source directly under csrc/ knows of it, so the hashed sources are those the parity envelopes were measured on."""
+    operations.  Its launch is an op of its own, a member of enum Op with its arguments a field of struct Launch, which every
+    unit forwards; no source directly under csrc/ knows of the kernel, and the parity envelopes were measured on these sources."""
     kern = open(os.path.join(CSRC, "physics", "rsr_transition.hpp")).read()
     assert "void transition_kernel(" in kern
     code = re.sub(r"//.*", "", kern)
@@ -95,20 +105,30 @@ def test_the_kernel_lives_in_the_physics_layer():
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
             text = open(os.path.join(CSRC, f)).read()
-            assert "transition_kernel" not in text and "FdArgs" not in text and "rsr_transition" not in text, f
+            assert "transition_kernel" not in text and "FdLayout" not in text and "rsr_transition" not in text, f
+    launch = open(os.path.join(CSRC, "rsr_launch.hpp")).read()
+    assert "OP_PHYS_TRANSITION" in re.search(r"enum Op \{(.*?)\};", launch, re.S).group(1)
+    assert re.search(r"\bFdArgs fd;", re.search(r"struct Launch \{(.*?)\};", launch, re.S).group(1))
+    for unit in ("rsr_cube.hip", "rsr_tshape.hip", "rsr_go2.hip"):          # the units name the ops they forward; no catch-all
+        text = open(os.path.join(CSRC, unit)).read()
+        assert "case OP_PHYS_TRANSITION:" in text and "default: return -1;" in text, unit
     kernels = open(os.path.join(CSRC, "physics", "rsr_physics_kernels.hpp")).read()
     lp = kernels[kernels.index("int launch_physics("):]
-    roll_case = lp[lp.index("case OP_PHYS_ROLLOUT:"):lp.index("case OP_PHYS_DYNAMICS:")]
-    assert "if (x.r.fd.out)" in roll_case
-    assert "transition_kernel<C, WAVES, Applied>" in roll_case and "transition_kernel<C, WAVES>" in roll_case
+    assert "switch (op)" in lp and "gofd" not in lp and lp.count("hipLaunchKernelGGL(") == 1      # one launch lambda
+    assert "op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>)" in lp
+    roll_case = lp[lp.index("case OP_PHYS_ROLLOUT:"):lp.index("case OP_PHYS_TRANSITION:")]
     assert "rollout_kernel<C, WAVES, Applied>" in roll_case and "rollout_kernel<C, WAVES>" in roll_case
-    assert "transition_kernel" not in lp[lp.index("case OP_PHYS_DYNAMICS:"):]
+    assert re.findall(r"\b\w+_kernel\b", roll_case) == ["rollout_kernel"] * 2 and "fd" not in roll_case and roll_case.count("\n") == 1
+    fd_case = lp[lp.index("case OP_PHYS_TRANSITION:"):lp.index("case OP_PHYS_DYNAMICS:")]
+    assert "transition_kernel<C, WAVES, Applied>" in fd_case and "transition_kernel<C, WAVES>" in fd_case and "x.fd" in fd_case
+    assert re.findall(r"\b\w+_kernel\b", fd_case) == ["transition_kernel"] * 2
+    assert "transition_kernel" not in lp[lp.index("case OP_PHYS_DYNAMICS:"):] and lp.count("transition_kernel") == 2
     phys = open(os.path.join(CSRC, "physics", "rsr_physics.hpp")).read()
     assert "struct FdArgs" in phys and "struct FdLayout" in phys
-    assert re.search(r"\bFdArgs fd;", re.search(r"struct RollArgs \{(.*?)\};", phys, re.S).group(1))
+    roll = re.search(r"struct RollArgs \{(.*?)\};", phys, re.S).group(1)      # again exactly what rollout_kernel reads
+    assert "fd" not in roll and "FdArgs" not in roll
     import bench
     import parity_envelopes as PE
-    # (the hashed sources are unchanged; the binaries of the units are not: DESIGN.md 4g)
     assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
 
 
@@ -122,6 +142,17 @@ def test_physics_module_surface():
     for view in ("fd_A", "fd_B", "fd_C", "fd_D", "fd_x", "fd_y"):
         assert isinstance(getattr(Physics, view), property), view
     src = inspect.getsource(Physics.transition_fd)
-    assert "rsr_physics_transition_fd(" in src and 'self._ids(env_ids, "transition_fd")' in src and "self._fd_ids_in = ids32" in src
+    assert 'self._call_envs("rsr_physics_transition_fd", "transition_fd", env_ids, nsteps, eps, flags)' in src
     assert "n_substeps" in src
+    # one helper carries the env-list calling convention of every entry point that takes one, and keeps each caller's ids alive
+    # in a slot of its own (two entry points' launches can be in flight at once)
+    for method, fn in (("dynamics", "rsr_physics_dynamics"), ("constraint_forces", "rsr_physics_constraint"),
+                       ("transition_fd", "rsr_physics_transition_fd"), ("set_state", "rsr_physics_forward_envs")):
+        text = inspect.getsource(getattr(Physics, method))
+        assert f'self._call_envs("{fn}", "{method}", ' in text and "data_ptr()" not in text and "_lib.lib()" not in text, method
+    helper = inspect.getsource(Physics._call_envs)
+    assert "self._ids(env_ids, who)" in helper and "ids32 = self._ids_in[who] = ids.to(torch.int32).contiguous()" in helper
+    assert helper.index("self._ids_in[who] = ") < helper.index("getattr(_lib.lib(), fn)(self._h, ptr, k, *args, self._stream())")
+    assert "self._ids_in: Dict[str, Any] = {}" in inspect.getsource(Physics.__init__)
+    assert not re.search(r"self\._\w*ids_in = ", inspect.getsource(Physics))      # no single shared attribute
     assert "Physics.transition_fd()" in physics.__doc__ and "mjd_transitionFD" in physics.__doc__
