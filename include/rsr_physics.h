@@ -227,6 +227,41 @@ int rsr_physics_transition_fd(rsr_physics* p, const int32_t* env_ids, int count,
 /* Zero-copy view (as rsr_physics_view) of the transition buffer or of one half of the states buffer.  RSR_ERR_ARG for an unknown id. */
 int rsr_physics_transition_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
 
+/* Inverse dynamics (mj_inverse / mjx.inverse): given an acceleration per env, the generalised force that must have acted
+ * (data.qfrc_inverse).  One launch evaluates the record's current state -- its qpos / qvel / ctrl with the batch's per-env
+ * leaves, the state after the last integration as rsr_physics_dynamics and rsr_physics_constraint see it -- at the caller's
+ * qacc: the stages of one forward pass up to the constraint rows with their final aref, then the row law at jaref = J a - aref.
+ * No Newton solve runs.  qacc: device float32 [num_envs][nv]; row e belongs to env e whether or not env_ids is given.
+ *   RSR_I_QFRC_INVERSE     M a + qfrc_bias - qfrc_passive - qfrc_constraint (MuJoCo's definition): the total of everything
+ *                          external, actuators included; subtract RSR_I_QFRC_ACTUATOR for the part the model does not explain
+ *   RSR_I_QFRC_CONSTRAINT  J^T efc_force
+ *   RSR_I_QACC             the continuous-time acceleration a the pass used: qacc itself, or its conversion (RSR_INV_DISCRETE)
+ *   RSR_I_QFRC_ACTUATOR    the same expression as RSR_D_QFRC_ACTUATOR
+ *   RSR_I_EFC_COUNTS       as RSR_C_EFC_COUNTS
+ *   RSR_I_EFC_FORCE        the row forces of MJX's _update_constraint at a: equality rows -D jaref; friction-loss rows -D jaref
+ *                          clamped to -+floss outside |jaref| < R floss; limit and contact rows -D min(jaref, 0).  Row order and
+ *                          zero padding as RSR_C_EFC_FORCE
+ * The handle's applied forces enter none of the outputs: the rows do not depend on them, and qfrc_inverse is what they would
+ * have to sum to.  RSR_INV_DISCRETE: qacc is a discrete-time acceleration, (qvel_after - qvel_before) / timestep of one
+ * substep.  Where the integrator solves (M + h D) qacc = M a (implicitfast, or Euler with non-zero damping and eulerdamp on) the
+ * pass first undoes that: a = qacc + h M^-1 (damp * qacc) (mj_discreteAcc); otherwise a = qacc.
+ * The constraints are soft with a large row stiffness D = 1 / R: an error d in qacc becomes up to D |J d| in force on an active
+ * row, so forces from differenced fp32 velocities are noisy wherever a contact or a limit is active.
+ * Nothing but the handle's inverse buffer is written: the record (qacc_warmstart, xpos and site_xpos included), the side buffer,
+ * RSR_P_SENSORDATA and the dynamics, constraint and transition buffers are untouched, and no PRNG key advances.
+ * env_ids: device int32 [count], or NULL for every env (count is ignored); ids outside [0, num_envs) are skipped.  Only the
+ * listed envs' rows of the buffer are written.  RSR_ERR_ARG, checked before any device work: null handle, null qacc, unknown flag
+ * bits, env_ids with count < 1, an unknown field id.  The buffer is allocated and zeroed by the first of these two calls; the
+ * views' pointers and row stride do not move afterwards.  rsr_physics_destroy frees it. */
+#define RSR_INV_DISCRETE 1
+enum rsr_inverse_field {
+  RSR_I_QFRC_INVERSE = 0, RSR_I_QFRC_CONSTRAINT, RSR_I_QACC, RSR_I_QFRC_ACTUATOR, RSR_I_EFC_COUNTS, RSR_I_EFC_FORCE,
+  RSR_I_COUNT
+};
+int rsr_physics_inverse(rsr_physics* p, const float* qacc, const int32_t* env_ids, int count, int flags, void* hip_stream);
+/* Zero-copy view (as rsr_physics_view) of one field of the inverse buffer.  RSR_ERR_ARG for an unknown id. */
+int rsr_physics_inverse_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,7 +43,8 @@ PHYS_FIELDS = ["qacc", "actuator_force", "xquat", "ncon", "contact", "ncon_dropp
 PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step", "rsr_physics_forward", "rsr_physics_forward_envs",
                 "rsr_physics_view", "rsr_physics_set_sensors", "rsr_physics_rollout", "rsr_physics_set_applied",
                 "rsr_physics_applied_view", "rsr_physics_set_jac_sites", "rsr_physics_dynamics", "rsr_physics_dynamics_view",
-                "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view"]
+                "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
+                "rsr_physics_inverse", "rsr_physics_inverse_view"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -58,6 +59,10 @@ CONSTRAINT_FIELDS = ["qfrc_constraint", "qacc", "efc_counts", "efc_force", "ncon
 # enum rsr_transition_field and the RSR_FD_* flags (include/rsr_physics.h)
 TRANSITION_FIELDS = ["columns", "states_x", "states_y"]
 FD_CENTERED, FD_STATES = 1, 2
+
+# enum rsr_inverse_field and the RSR_INV_* flags (include/rsr_physics.h)
+INVERSE_FIELDS = ["qfrc_inverse", "qfrc_constraint", "qacc", "qfrc_actuator", "efc_counts", "efc_force"]
+INV_DISCRETE = 1
 
 # enum rsr_sensor_type (include/rsr_physics.h), in order, with each type's width
 SENSOR_TYPES = ["gyro", "velocimeter", "accelerometer", "framepos", "framexaxis", "framezaxis", "framequat", "framelinvel",
@@ -122,6 +127,8 @@ def lib() -> C.CDLL:
     L.rsr_physics_constraint_view.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p]
     L.rsr_physics_transition_fd.argtypes = [vp, vp, i32, i32, C.c_float, i32, vp]
     L.rsr_physics_transition_view.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p]
+    L.rsr_physics_inverse.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.rsr_physics_inverse_view.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

@@ -1,7 +1,7 @@
 // rsr_physics.hip -- the C ABI of the physics layer (include/rsr_physics.h): rsr_physics_step / rsr_physics_forward /
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
-// (rsr_physics_transition_fd).  The kernels are in the family units (physics/rsr_physics_kernels.hpp).
+// (rsr_physics_transition_fd) and inverse dynamics (rsr_physics_inverse).  The kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -26,6 +26,7 @@ struct rsr_physics {
   float* con = nullptr;   // the constraint buffer [n][ConLayout::stride], allocated on first use (con_buffer)
   float* fd = nullptr;    // the transition buffer [n][FdLayout::env], allocated on first use (fd_buffers)
   float* fd_states = nullptr;  // the states buffer of RSR_FD_STATES, allocated on first request (fd_buffers)
+  float* inv = nullptr;   // the inverse buffer [n][InvLayout::stride], allocated on first use (inv_buffer)
 };
 
 // `*slot`, a buffer of the handle, on first use: `bytes` of device memory, zeroed; once there it never moves.  A failure is reported
@@ -72,6 +73,7 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
   if (p->con) (void)hipFree(p->con);
   if (p->fd) (void)hipFree(p->fd);
   if (p->fd_states) (void)hipFree(p->fd_states);
+  if (p->inv) (void)hipFree(p->inv);
   delete p;
 }
 
@@ -351,4 +353,41 @@ extern "C" int rsr_physics_transition_view(rsr_physics* p, int field, void** dev
   if (field == RSR_T_COLUMNS) return view_out(p, p->fd, FL.env, FL.env, dev_ptr, shape, stride);
   if (field == RSR_T_STATES_X) return view_out(p, p->fd_states, xrow, xrow, dev_ptr, shape, stride);
   return view_out(p, p->fd_states + (size_t)p->b->n * xrow, yrow, yrow, dev_ptr, shape, stride);
+}
+
+// the inverse buffer, on first use
+static int inv_buffer(rsr_physics* p, const char* who) {
+  const rsr_dims& d = p->b->model->dims;
+  return zeroed_once(p, &p->inv, (size_t)p->b->n * rsr::inv_layout(d.nv, d.nefc_max).stride * sizeof(float), "inverse buffer", who);
+}
+
+extern "C" int rsr_physics_inverse(rsr_physics* p, const float* qacc, const int32_t* env_ids, int count, int flags, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_inverse: null handle");
+  if (!qacc) return fail(RSR_ERR_ARG, "rsr_physics_inverse: null qacc");
+  if (flags & ~RSR_INV_DISCRETE) return fail(RSR_ERR_ARG, "rsr_physics_inverse: unknown flag bits");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, "rsr_physics_inverse", &n)) return rc;
+  if (const int rc = inv_buffer(p, "rsr_physics_inverse")) return rc;
+  rsr::Launch x = physics_args(p, nullptr, env_ids, n, 1, hip_stream);
+  x.p = rsr::inverse_launch_args(rsr::InvArgs{p->inv, env_ids, qacc, flags});
+  x.d.out = nullptr;                            // no dynamics buffer: the op launches inverse_kernel (launch_physics)
+  return physics_launch(p, rsr::OP_PHYS_DYNAMICS, x, "rsr_physics_inverse");
+}
+
+extern "C" int rsr_physics_inverse_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {
+  if (!p || !dev_ptr || !shape || !stride) return fail(RSR_ERR_ARG, "rsr_physics_inverse_view: null argument");
+  const rsr_dims& d = p->b->model->dims;
+  const rsr::InvLayout IL = rsr::inv_layout(d.nv, d.nefc_max);
+  int off = -1, w = 0;
+  switch (field) {
+    case RSR_I_QFRC_INVERSE: off = IL.qfi; w = d.nv; break;
+    case RSR_I_QFRC_CONSTRAINT: off = IL.qfc; w = d.nv; break;
+    case RSR_I_QACC: off = IL.qacc; w = d.nv; break;
+    case RSR_I_QFRC_ACTUATOR: off = IL.act; w = d.nv; break;
+    case RSR_I_EFC_COUNTS: off = IL.counts; w = 4; break;
+    case RSR_I_EFC_FORCE: off = IL.force; w = d.nefc_max; break;
+    default: return fail(RSR_ERR_ARG, "rsr_physics_inverse_view: unknown field id");
+  }
+  if (const int rc = inv_buffer(p, "rsr_physics_inverse_view")) return rc;
+  return view_out(p, p->inv + off, w, IL.stride, dev_ptr, shape, stride);
 }

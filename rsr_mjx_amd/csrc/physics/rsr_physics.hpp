@@ -1,4 +1,4 @@
-// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics, constraint and transition buffer) and the launch arguments of its ops,
+// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics, constraint, transition and inverse buffer) and the launch arguments of its ops,
 // one struct per op of rsr_launch.hpp that needs its own (host and device).
 #pragma once
 #include "../../../include/rsr_physics.h"
@@ -96,5 +96,33 @@ struct ConArgs {
   float* out;           // the constraint buffer [N][ConLayout::stride]
   const int* ids;       // [grid] the envs to run, or null: env = workgroup index
 };
+// rsr_physics_inverse (rsr_inverse.hpp).  Its buffer, per env, floats: qfrc_inverse [nv] | qfrc_constraint [nv] | qacc [nv] |
+// qfrc_actuator [nv] | efc counts [4] (nefc, ne, nf, nl) | efc_force [nefc_max], padded to 16 floats.
+struct InvLayout { int qfi, qfc, qacc, act, counts, force, stride; };
+__host__ __device__ inline InvLayout inv_layout(int nv, int nefc_max) {
+  InvLayout i;
+  i.qfi = 0; i.qfc = nv; i.qacc = 2 * nv; i.act = 3 * nv; i.counts = 4 * nv; i.force = i.counts + 4;
+  i.stride = (i.force + nefc_max + 15) & ~15;
+  return i;
+}
+// The kernel arguments of inverse_kernel.  The launch has no op or Launch field of its own (rsr_launch.hpp is a source of the env
+// kernels): it is sent as OP_PHYS_DYNAMICS with a null dynamics buffer (Launch::d.out), the op's unused Launch::p carrying the
+// arguments: p.out the inverse buffer, p.ids the envs, p.ctrl the accelerations, p.nsteps the flags, and INVERSE_TAG where a
+// sensor table's accelerometer site would stand (inverse_launch_args).  Only a Launch that carries the tag and both pointers is
+// read back as an inverse launch (inverse_args); any other dynamics op without a buffer is refused, not launched.
+struct InvArgs {
+  float* out;           // the inverse buffer [N][InvLayout::stride]
+  const int* ids;       // [grid] the envs to run, or null: env = workgroup index
+  const float* qacc;    // [N][nv] the accelerations, row e env e's
+  int flags;            // RSR_INV_*
+};
+constexpr int INVERSE_TAG = -0x494e56;          // (no site id is negative but -1, "none")
+inline PhysArgs inverse_launch_args(const InvArgs& v) { return PhysArgs{v.qacc, v.out, v.ids, v.flags, nullptr, SensArgs{nullptr, 0, INVERSE_TAG}}; }
+// false: p is not what inverse_launch_args makes of a complete InvArgs
+inline bool inverse_args(const PhysArgs& p, InvArgs* v) {
+  if (p.sens.acc_site != INVERSE_TAG || !p.ctrl || !p.out || p.sd || p.sens.el || p.sens.nsd != 0) return false;
+  *v = InvArgs{p.out, p.ids, p.ctrl, p.nsteps};
+  return true;
+}
 
 }  // namespace rsr

@@ -1,7 +1,7 @@
 // rsr_physics_kernels.hpp -- the physics-level kernels (include/rsr_physics.h): each family unit instantiates them for its Dims,
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
-// forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp), constraint_kernel (rsr_constraint.hpp) and transition_kernel
-// (rsr_transition.hpp); all but dynamics_kernel
+// forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp), constraint_kernel (rsr_constraint.hpp), transition_kernel
+// (rsr_transition.hpp) and inverse_kernel (rsr_inverse.hpp); all but dynamics_kernel and inverse_kernel
 // are instantiated plain and with applied forces: the applied kernels take the handle's Applied buffers as one more argument and
 // pass forward<C> their env's rows as its force stage (rsr_applied.hpp).
 #pragma once
@@ -11,6 +11,7 @@
 #include "rsr_dynamics.hpp"
 #include "rsr_constraint.hpp"
 #include "rsr_transition.hpp"
+#include "rsr_inverse.hpp"
 
 namespace rsr {
 
@@ -171,7 +172,14 @@ int launch_physics(int op, const Launch& x) {
     case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, false, WAVES>, x.p);
     case OP_PHYS_ROLLOUT: return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
     case OP_PHYS_TRANSITION: return ap ? go(transition_kernel<C, WAVES, Applied>, x.p, x.fd, x.ap) : go(transition_kernel<C, WAVES>, x.p, x.fd);
-    case OP_PHYS_DYNAMICS: return go(dynamics_kernel<C, WAVES>, x.d);      // (applied forces enter none of its outputs)
+    // (applied forces enter none of the outputs of either.  rsr_physics_inverse rides on this op, with no dynamics buffer and its
+    // tagged arguments in x.p (inverse_args, rsr_physics.hpp): an op of its own means an edit to rsr_launch.hpp and the three
+    // units.  A dynamics op with no buffer and no such arguments launches nothing: -1)
+    case OP_PHYS_DYNAMICS: {
+      InvArgs v;
+      if (x.d.out) return go(dynamics_kernel<C, WAVES>, x.d);
+      return inverse_args(x.p, &v) ? go(inverse_kernel<C, WAVES>, v) : -1;
+    }
     case OP_PHYS_CONSTRAINT: return ap ? go(constraint_kernel<C, WAVES, Applied>, x.c, x.ap) : go(constraint_kernel<C, WAVES>, x.c);
     default: return -1;
   }

@@ -13,6 +13,8 @@
                                                                                            state; Physics.contact_forces())
     mjd_transitionFD / jax.jacobian(mjx.step)    ->  Physics.transition_fd()              (finite differences of step at a given
                                                                                            eps: fd_A, fd_B, fd_C, fd_D)
+    mj_inverse / mjx.inverse (data.qfrc_inverse)  ->  Physics.inverse(qacc)               (the force behind a given acceleration,
+                                                                                           no solve: qfrc_inverse)
 
 `Physics(env)` shares the batch of a BatchedEnv (Airbot cube / sf / T-shape, Go2 joystick, handstand / footstand): the same model,
 the same per-env domain randomisation, the same record and the same stream.  The pipeline fields it exposes are the record's own
@@ -82,6 +84,9 @@ class Physics:
         self._con: Optional[Dict[str, Any]] = None
         # the transition buffer's and the states buffer's views (transition_fd): likewise
         self._fd: Dict[str, Any] = {}
+        # the inverse buffer's views (inverse): likewise
+        self._inv: Optional[Dict[str, Any]] = None
+        self._qacc_in = None                       # the accelerations of inverse()'s last launch
         # the env-id tensor of each entry point's last launch (_call_envs)
         self._ids_in: Dict[str, Any] = {}
         if sensors is not None:
@@ -342,6 +347,50 @@ class Physics:
             raise ValueError(f"transition_fd: eps must be finite and > 0, got {eps}")
         flags = (_lib.FD_CENTERED if centered else 0) | (_lib.FD_STATES if keep_states else 0)
         self._call_envs("rsr_physics_transition_fd", "transition_fd", env_ids, nsteps, eps, flags)
+
+    def _inv_views(self) -> Dict[str, Any]:
+        if self._inv is None:
+            self._inv = {name: self._fetch("rsr_physics_inverse_view", fid) for fid, name in enumerate(_lib.INVERSE_FIELDS)}
+        return self._inv
+
+    # outputs of inverse(): views of the handle's inverse buffer, zeros until the first call
+    qfrc_inverse = property(lambda self: self._inv_views()["qfrc_inverse"],
+                            doc="[N, nv] M a + qfrc_bias - qfrc_passive - qfrc_constraint: every external force, actuators included")
+    inverse_qacc = property(lambda self: self._inv_views()["qacc"], doc="[N, nv] the continuous-time acceleration a that inverse() used")
+    inverse_qfrc_constraint = property(lambda self: self._inv_views()["qfrc_constraint"], doc="[N, nv] J^T inverse_efc_force")
+    inverse_qfrc_actuator = property(lambda self: self._inv_views()["qfrc_actuator"], doc="[N, nv] as qfrc_actuator of dynamics()")
+    inverse_efc_force = property(lambda self: self._inv_views()["efc_force"],
+                                 doc="[N, nefc_max] row forces at a, rows as efc_force; rows >= nefc are 0")
+    inverse_efc_counts = property(lambda self: self._inv_views()["efc_counts"], doc="[N, 4] nefc, ne, nf, nl (active limits), as float")
+
+    def inverse(self, qacc, env_ids=None, discrete: bool = False) -> None:
+        """mj_inverse / mjx.inverse at the record's current qpos / qvel / ctrl (per-env leaves included) and the accelerations
+        `qacc`, a contiguous float32 tensor [num_envs, nv] on the env's device (row e is env e's, with env_ids too), one launch:
+        fills qfrc_inverse, inverse_qacc, inverse_qfrc_constraint, inverse_qfrc_actuator, inverse_efc_force and
+        inverse_efc_counts of the envs `env_ids` (default: all).  The pass builds the constraint rows as forward() does and
+        evaluates their forces at `qacc`; no solve runs.  qfrc_inverse is the total of everything external, actuators included:
+        qfrc_inverse - inverse_qfrc_actuator is what the model does not explain.  discrete: `qacc` is
+        (qvel_after - qvel_before) / timestep of one substep, and the integrator's implicit damping is undone first
+        (mj_discreteAcc); inverse_qacc shows the result.  The constraints are soft and stiff: an error in `qacc` is multiplied
+        by the row stiffness on every active contact or limit row, so differenced fp32 velocities give noisy forces there.
+        Like dynamics() it describes the state after the last integration and writes nothing else; applied forces enter none of
+        the outputs."""
+        import torch
+        shape = (self.num_envs, self.dims.nv)
+        if not torch.is_tensor(qacc) or qacc.dtype != torch.float32 or tuple(qacc.shape) != shape or not qacc.is_contiguous() \
+                or qacc.device != self.qvel.device:
+            raise ValueError(f"inverse expects qacc as a contiguous float32 tensor of shape {shape} on {self.qvel.device}")
+        ptr, k = None, 0
+        if env_ids is not None:
+            ids = self._ids(env_ids, "inverse")
+            k = ids.numel()
+            if k == 0:
+                return
+            ids32 = self._ids_in["inverse"] = ids.to(torch.int32).contiguous()
+            ptr = C.c_void_p(ids32.data_ptr())
+        self._qacc_in = qacc                       # kept alive until the next call (the launch is asynchronous)
+        _lib.check(_lib.lib().rsr_physics_inverse(self._h, C.c_void_p(qacc.data_ptr()), ptr, k, _lib.INV_DISCRETE if discrete else 0,
+                                                  self._stream()))
 
     def rollout(self, ctrl, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), qpos0=None, qvel0=None,
                 ctrl0=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:

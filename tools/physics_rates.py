@@ -8,9 +8,13 @@ rsr_physics_forward launch, interleaved in blocks on the same batch and state (o
 --transition is a mode of its own: per family and for N = 64, 1024 and 8192 envs it times Physics.transition_fd at its defaults
 beside the 2 ncol Physics.step launches that do the same work from Python, each after a restore of the record, in alternating
 blocks on the same batch and state, and writes one row per family to profiles/transition_rates_<N>.jsonl (--out-dir).
+--inverse is a mode of its own too: per family and for N = 1024 and 8192 envs, HIP events around --steps launches after --warmup
+warm-up launches of Physics.inverse (at the qacc of the last forward pass), Physics.constraint_forces and Physics.dynamics (no
+Jacobian sites) on the same batch and state, none of which moves the state; one row per family to profiles/inverse_rates_<N>.jsonl.
 Usage: python tools/physics_rates.py [--envs 8192] [--steps 50] [--warmup 10] [--applied] [--dynamics] [--constraint]
                                      [--rollout-T 16] [--out FILE]
-       python tools/physics_rates.py --transition [--transition-envs 64,1024,8192] [--families ...] [--out-dir profiles]"""
+       python tools/physics_rates.py --transition [--transition-envs 64,1024,8192] [--families ...] [--out-dir profiles]
+       python tools/physics_rates.py --inverse [--inverse-envs 1024,8192] [--families ...] [--out-dir profiles]"""
 from __future__ import annotations
 
 import argparse
@@ -93,6 +97,53 @@ def transition_rates(args) -> None:
                 fh.write(json.dumps(row) + "\n")
 
 
+def inverse_rates(args) -> None:
+    """ms per Physics.inverse() launch next to ms per constraint_forces() and per dynamics() launch of the same run, from the
+    states 10 env steps reach"""
+    import torch
+    from bench import csrc_sha16
+    from rsr_mjx_amd import prng
+    from rsr_mjx_amd.physics import Physics
+    for n in [int(v) for v in args.inverse_envs.split(",")]:
+        rows = []
+        for kind in args.families.split(","):
+            envdef, env, scale = _make_env(kind, n)
+            env.reset(prng.split(prng.PRNGKey(0), n))
+            rng = np.random.default_rng(0)
+            for _ in range(10):
+                env.step(None, np.clip(rng.normal(size=(n, env.dims.nu)) * scale, -1, 1).astype(np.float32))
+            phys = Physics(env)
+            phys.forward()
+            qacc = phys.qacc.clone().contiguous()
+            phys.set_jac_sites([])
+
+            def per_launch(fn):
+                for _ in range(args.warmup):
+                    fn()
+                env.timing_begin()
+                for _ in range(args.steps):
+                    fn()
+                return env.timing_end()[0] / args.steps
+            row = dict(family=kind, num_envs=n, launches=args.steps, warmup=args.warmup)
+            row["inverse_ms"] = per_launch(lambda: phys.inverse(qacc))
+            row["inverse_discrete_ms"] = per_launch(lambda: phys.inverse(qacc, discrete=True))
+            row["constraint_ms"] = per_launch(phys.constraint_forces)
+            row["dynamics_ms"] = per_launch(phys.dynamics)
+            row["inverse_over_constraint"] = row["inverse_ms"] / row["constraint_ms"]
+            row["inverse_over_dynamics"] = row["inverse_ms"] / row["dynamics_ms"]
+            row["ordered"] = bool(row["dynamics_ms"] < row["inverse_ms"] < row["constraint_ms"])
+            row["finite"] = bool(torch.isfinite(phys.qfrc_inverse).all())
+            row["csrc_sha16"] = csrc_sha16()
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            del phys, env
+            torch.cuda.synchronize()
+        os.makedirs(args.out_dir, exist_ok=True)
+        with open(os.path.join(args.out_dir, f"inverse_rates_{n}.jsonl"), "w") as fh:
+            for row in rows:
+                fh.write(json.dumps(row) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=8192)
@@ -107,10 +158,15 @@ def main() -> None:
     ap.add_argument("--transition", action="store_true")
     ap.add_argument("--transition-envs", default="64,1024,8192")
     ap.add_argument("--transition-reps", type=int, default=5)
+    ap.add_argument("--inverse", action="store_true")
+    ap.add_argument("--inverse-envs", default="1024,8192")
     ap.add_argument("--out-dir", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles"))
     args = ap.parse_args()
     if args.transition:
         transition_rates(args)
+        return
+    if args.inverse:
+        inverse_rates(args)
         return
     import torch
     from rsr_mjx_amd import prng
