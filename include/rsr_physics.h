@@ -6,6 +6,8 @@
  *                          (qacc_warmstart as the record holds it; the caller zeroes it first to match init).
  *   rsr_physics_step    <- mjx_env.step(model, data, ctrl, n_substeps): writes ctrl into the record, then nsteps x mjx.step.
  *   rsr_physics_rollout <- mujoco.rollout.rollout / lax.scan(mjx.step): T control steps in one launch, trajectories [N, T, w].
+ *   rsr_physics_sample_rollouts <- mujoco.rollout.rollout on K copies of a state / vmap(lax.scan(mjx.step)): K ctrl sequences
+ *                          per env from its current state, trajectories [M, K, T, w]; the record is read only.
  *   rsr_physics_set_sensors: the site sensors of data.sensordata (RSR_P_SENSORDATA, and a rollout's sensordata rows).
  *   rsr_physics_set_applied / rsr_physics_applied_view: data.xfrc_applied and data.qfrc_applied, per-env inputs of every forward
  *                          pass of these calls (zero until set).
@@ -114,6 +116,23 @@ typedef struct rsr_rollout_out {
  * with ctrl[:, t, :] would.  out may be NULL (nothing recorded).  RSR_ERR_ARG: null handle or ctrl, T < 1, nsteps < 1,
  * sensordata requested with no sensor table set. */
 int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int nsteps, const rsr_rollout_out* out, void* hip_stream);
+
+/* Sampled rollouts, for sampling planners (predictive sampling, MPPI, CEM): from the state each listed env is in now, K control
+ * sequences of T control steps, one launch with one wavefront per (env, sample).  M = count, or num_envs with env_ids NULL.
+ * Sample (s, k) starts from the record of env e = env_ids[s] as it stands (qpos, qvel, qacc_warmstart, time), with env e's
+ * per-env leaves and, while they are on, its applied forces (held for all T control steps), and runs ctrl[s, k, t] then
+ * nsteps x mjx.step for t = 0 .. T-1: bit for bit the trajectory rsr_physics_rollout would record on a batch whose env holds
+ * that record row and those leaves.  ctrl: device float32 [M, K, T, nu].  out: the non-NULL members are [M, K, T, width], the
+ * fields and their meaning per control step as for rsr_physics_rollout; rows are indexed by slot s, the position in env_ids,
+ * not by env id.  Only these buffers are written: the record (the K samples of an env share its row, read only), the side
+ * buffer, RSR_P_SENSORDATA and the dynamics, constraint, transition and inverse buffers are untouched, and no PRNG key advances;
+ * the handle owns no buffer for this call.  A member of out holds 4 M K T width bytes: record only what the planner's cost reads.
+ * env_ids: device int32 [count], or NULL for every env (count is ignored); an id outside [0, num_envs) runs nothing and its
+ * slot's rows are left alone.  RSR_ERR_ARG, checked before any device work: null handle, null ctrl, null out or an out with all
+ * six members NULL, K < 1, T < 1, nsteps < 1, env_ids with count < 1, sensordata requested with no sensor table set, M K or
+ * T nsteps at or above 2^31. */
+int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int K, int T, int nsteps,
+                                const rsr_rollout_out* out, void* hip_stream);
 
 /* Applied forces (MuJoCo's data.xfrc_applied / data.qfrc_applied): per-env state of the handle, added in every forward pass of
  * rsr_physics_step (each substep), _forward, _forward_envs and _rollout (each substep, held for all T control steps):

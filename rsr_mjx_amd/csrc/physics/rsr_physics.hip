@@ -1,7 +1,7 @@
 // rsr_physics.hip -- the C ABI of the physics layer (include/rsr_physics.h): rsr_physics_step / rsr_physics_forward /
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
-// (rsr_physics_transition_fd) and inverse dynamics (rsr_physics_inverse).  The kernels are in the family units (physics/rsr_physics_kernels.hpp).
+// (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse) and sampled rollouts (rsr_physics_sample_rollouts).  The kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -197,6 +197,28 @@ extern "C" int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int
     r.qpos = out->qpos; r.qvel = out->qvel; r.time = out->time; r.aforce = out->actuator_force; r.ncon = out->ncon; r.sd = out->sensordata;
   }
   const int rc = physics_launch(p, rsr::OP_PHYS_ROLLOUT, x, "rsr_physics_rollout");
+  if (rc == RSR_OK && p->b->timing) p->b->launches++;
+  return rc;
+}
+
+extern "C" int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int K, int T, int nsteps,
+                                           const rsr_rollout_out* out, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: null handle");
+  if (!ctrl) return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: null ctrl");
+  if (!out || !(out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata))
+    return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: null out, or nothing to record");
+  if (K < 1 || T < 1 || nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: K, T and nsteps must be >= 1");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, "rsr_physics_sample_rollouts", &n)) return rc;
+  if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: sensordata requested with no sensor table set");
+  const int64_t grid = (int64_t)n * K;           // one wave per (slot, sample)
+  if (grid > INT32_MAX || (int64_t)T * nsteps > INT32_MAX)
+    return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: envs x K and T x nsteps must stay below 2^31");
+  rsr::Launch x = physics_args(p, nullptr, env_ids, (int)grid, nsteps, hip_stream);
+  // no constraint buffer (physics_args copies the handle's, which may exist): the op launches sample_kernel (launch_physics)
+  rsr::sample_launch_args(x, env_ids, rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata}, K);
+  x.c.out = nullptr;
+  const int rc = physics_launch(p, rsr::OP_PHYS_CONSTRAINT, x, "rsr_physics_sample_rollouts");
   if (rc == RSR_OK && p->b->timing) p->b->launches++;
   return rc;
 }

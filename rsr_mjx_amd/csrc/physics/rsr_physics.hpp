@@ -124,5 +124,31 @@ inline bool inverse_args(const PhysArgs& p, InvArgs* v) {
   *v = InvArgs{p.out, p.ids, p.ctrl, p.nsteps};
   return true;
 }
+// rsr_physics_sample_rollouts (rsr_sample.hpp).  sample_kernel takes a PhysArgs, a RollArgs and K; like the inverse launch it
+// has no op or Launch field of its own: it is sent as OP_PHYS_CONSTRAINT with a null constraint buffer (Launch::c.out; the
+// constraint entry point always has one).  Launch::p carries the env list, nsteps and the sensor table, with its three buffers
+// null; Launch::r ctrl [M][K][T][nu], T and the trajectory rows [M][K][T][w]; and two fields the op never reads carry the rest:
+// Launch::fd.flags K, Launch::d.nsite SAMPLE_TAG (sample_launch_args; X is the Launch, which is declared after this file).  Only
+// a Launch that carries the tag and a complete set of arguments is read back as a sampled-rollout launch (sample_args); any other
+// constraint op without a buffer is refused, not launched.
+constexpr int SAMPLE_TAG = -0x534d50;           // (no site count is negative)
+template <class X>
+inline void sample_launch_args(X& x, const int* ids, const RollArgs& r, int K) {
+  x.p.ctrl = nullptr; x.p.out = nullptr; x.p.ids = ids; x.p.sd = nullptr;
+  x.r = r;
+  x.c = ConArgs{nullptr, nullptr};
+  x.d = DynArgs{nullptr, nullptr, nullptr, SAMPLE_TAG};
+  x.fd = FdArgs{nullptr, nullptr, nullptr, 0.0f, K};
+}
+// false: x is not what sample_launch_args makes of complete arguments; otherwise *K
+template <class X>
+inline bool sample_args(const X& x, int* K) {
+  const RollArgs& r = x.r;
+  if (x.c.out || x.d.out || x.d.nsite != SAMPLE_TAG || x.fd.out || x.fd.states || x.fd.flags < 1) return false;
+  if (x.p.ctrl || x.p.out || x.p.sd || x.p.nsteps < 1 || !r.ctrl || r.T < 1) return false;
+  if (!(r.qpos || r.qvel || r.time || r.aforce || r.ncon || r.sd) || (r.sd && x.p.sens.nsd < 1)) return false;
+  *K = x.fd.flags;
+  return true;
+}
 
 }  // namespace rsr

@@ -1,7 +1,7 @@
 // rsr_physics_kernels.hpp -- the physics-level kernels (include/rsr_physics.h): each family unit instantiates them for its Dims,
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
 // forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp), constraint_kernel (rsr_constraint.hpp), transition_kernel
-// (rsr_transition.hpp) and inverse_kernel (rsr_inverse.hpp); all but dynamics_kernel and inverse_kernel
+// (rsr_transition.hpp), inverse_kernel (rsr_inverse.hpp) and sample_kernel (rsr_sample.hpp); all but dynamics_kernel and inverse_kernel
 // are instantiated plain and with applied forces: the applied kernels take the handle's Applied buffers as one more argument and
 // pass forward<C> their env's rows as its force stage (rsr_applied.hpp).
 #pragma once
@@ -12,6 +12,7 @@
 #include "rsr_constraint.hpp"
 #include "rsr_transition.hpp"
 #include "rsr_inverse.hpp"
+#include "rsr_sample.hpp"
 
 namespace rsr {
 
@@ -180,9 +181,17 @@ int launch_physics(int op, const Launch& x) {
       if (x.d.out) return go(dynamics_kernel<C, WAVES>, x.d);
       return inverse_args(x.p, &v) ? go(inverse_kernel<C, WAVES>, v) : -1;
     }
-    case OP_PHYS_CONSTRAINT: return ap ? go(constraint_kernel<C, WAVES, Applied>, x.c, x.ap) : go(constraint_kernel<C, WAVES>, x.c);
+    case OP_PHYS_CONSTRAINT:
+      if (x.c.out) return ap ? go(constraint_kernel<C, WAVES, Applied>, x.c, x.ap) : go(constraint_kernel<C, WAVES>, x.c);
+      break;                                   // (no constraint buffer: below)
     default: return -1;
   }
+  // OP_PHYS_CONSTRAINT with no constraint buffer: rsr_physics_sample_rollouts rides on the op as rsr_physics_inverse rides on the
+  // dynamics op, with its tagged arguments in x.p, x.r, x.d and x.fd (sample_args, rsr_physics.hpp).  grid = slots x K.  A
+  // constraint op with no buffer and no such arguments launches nothing: -1
+  int K;
+  if (!sample_args(x, &K)) return -1;
+  return ap ? go(sample_kernel<C, WAVES, Applied>, x.p, x.r, K, x.ap) : go(sample_kernel<C, WAVES>, x.p, x.r, K);
 }
 
 }  // namespace rsr

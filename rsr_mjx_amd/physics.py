@@ -3,6 +3,9 @@
     mjx_env.init(model, qpos, qvel, ctrl)      ->  Physics.set_state(qpos, qvel, ctrl)   (one mjx.forward)
     mjx_env.step(model, data, ctrl, n_substeps) ->  Physics.step(ctrl, nsteps)           (nsteps x mjx.step)
     mujoco.rollout.rollout / lax.scan(mjx.step)  ->  Physics.rollout(ctrl [N, T, nu])     (one launch, trajectories [N, T, w])
+    mujoco.rollout on K copies of a state / vmap(lax.scan(mjx.step)) ->  Physics.sample_rollouts(ctrl [M, K, T, nu])
+                                                                                          (K sequences per env from its current
+                                                                                           state, [M, K, T, w]; the record stays)
     mjx_env.get_sensor_data(model, data, name)  ->  Physics.sensor(name)                 (site sensors, Physics.set_sensors)
     data.replace(xfrc_applied=..., qfrc_applied=...) ->  Physics.set_applied(xfrc, qfrc)  (held by every later step / forward /
                                                                                            rollout, like a Data field)
@@ -87,6 +90,7 @@ class Physics:
         # the inverse buffer's views (inverse): likewise
         self._inv: Optional[Dict[str, Any]] = None
         self._qacc_in = None                       # the accelerations of inverse()'s last launch
+        self._sample_ctrl_in = None                # the control sequences of sample_rollouts()'s last launch
         # the env-id tensor of each entry point's last launch (_call_envs)
         self._ids_in: Dict[str, Any] = {}
         if sensors is not None:
@@ -431,6 +435,53 @@ class Physics:
         c = c.contiguous()
         self._ctrl_in = c                          # kept alive until the next call (the launch is asynchronous)
         _lib.check(_lib.lib().rsr_physics_rollout(self._h, C.c_void_p(c.data_ptr()), T, nsteps, C.byref(ptrs), self._stream()))
+        return res
+
+    def sample_rollouts(self, ctrl, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), env_ids=None,
+                        out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """What a sampling planner asks (predictive sampling, MPPI, CEM): from the state each env is in now, K control sequences
+        of T control steps, one launch with one wave per (env, sample).  ctrl is a float32 tensor [M, K, T, nu] on the env's
+        device, M = len(env_ids) (default: every env, M = num_envs); sample (s, k) starts from the record of env env_ids[s] as it
+        stands (qpos, qvel, qacc_warmstart, time), with that env's per-env leaves and applied forces, and runs ctrl[s, k, t] then
+        `nsteps` (default n_substeps) x mjx.step for t < T: bit for bit the trajectory rollout() records on a batch whose env
+        holds that record row and those leaves.  Returns {field: [M, K, T, w]} for `fields` (ROLLOUT_FIELDS, as rollout), rows in
+        env_ids order.  `out`: caller-owned float32 tensors to fill instead of new ones.  Writes nothing else: the record, the
+        side buffer, sensordata and every other buffer of the handle stay as they are, so step() goes on from where the batch
+        stood.  A field takes 4 * M * K * T * w bytes: asking for fewer fields is the only lever (a cost on sensor values needs
+        fields=("sensordata",) alone)."""
+        import torch
+        nsteps = self.n_substeps if nsteps is None else int(nsteps)
+        if nsteps < 1:
+            raise ValueError(f"sample_rollouts: nsteps must be >= 1, got {nsteps}")
+        ids = None if env_ids is None else self._ids(env_ids, "sample_rollouts")
+        M, nu = self.num_envs if ids is None else int(ids.numel()), self.dims.nu
+        if not torch.is_tensor(ctrl) or ctrl.dtype != torch.float32 or ctrl.dim() != 4 or ctrl.shape[0] != M or ctrl.shape[3] != nu \
+                or ctrl.shape[1] < 1 or ctrl.shape[2] < 1 or ctrl.device != self.qvel.device:
+            raise ValueError(f"sample_rollouts expects ctrl as a float32 tensor of shape ({M}, K >= 1, T >= 1, {nu}) on {self.qvel.device}")
+        K, T = int(ctrl.shape[1]), int(ctrl.shape[2])
+        fields = tuple(fields)
+        bad = [f for f in fields if f not in ROLLOUT_FIELDS]
+        if bad or not fields:
+            raise ValueError(f"sample_rollouts: unknown or no fields {bad}; recordable: {ROLLOUT_FIELDS}")
+        if "sensordata" in fields and self.nsensordata == 0:
+            raise ValueError("sample_rollouts: sensordata requested but no sensors are set (set_sensors)")
+        d = self.dims
+        width = dict(qpos=d.nq, qvel=d.nv, time=1, actuator_force=d.nu, ncon=1, sensordata=self.nsensordata)
+        res, ptrs = {}, _lib.RolloutOut()
+        out = out or {}
+        for f in fields:
+            shape = (M, K, T, width[f])
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=torch.float32, device=ctrl.device)
+            elif (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != ctrl.device):
+                raise ValueError(f"sample_rollouts: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {ctrl.device}")
+            res[f] = t
+            setattr(ptrs, f, t.data_ptr())
+        c = ctrl.contiguous()
+        self._sample_ctrl_in = c                   # kept alive until the next call (the launch is asynchronous)
+        self._call_envs("rsr_physics_sample_rollouts", "sample_rollouts", ids, C.c_void_p(c.data_ptr()), K, T, nsteps, C.byref(ptrs),
+                        checked=True)
         return res
 
     def forward(self) -> None:

@@ -1,0 +1,158 @@
+"""Sampled rollouts of the physics layer (rsr_physics_sample_rollouts, Physics.sample_rollouts), host side only: the ABI, the
+dispatch and the Python surface.  The kernel is covered by tests/test_sample_gpu.py."""
+import ctypes as C
+import inspect
+import os
+import re
+import types
+
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
+SIG = ("int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, "
+       "int K, int T, int nsteps, const rsr_rollout_out* out, void* hip_stream);")
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+
+
+def test_header_declares_the_sample_api():
+    h = _header()
+    assert SIG in re.sub(r"\s+", " ", h)                          # (the declaration may break its line)
+    doc = h[h.index("/* Sampled rollouts"):h.index("int rsr_physics_sample_rollouts(")]
+    for word in ("[M, K, T, nu]", "[M, K, T, width]", "bit for bit", "qacc_warmstart", "position in env_ids", "untouched",
+                 "no PRNG key advances", "left alone", "before any device work", "2^31"):
+        assert word in doc, word
+    assert h.count("typedef struct rsr_rollout_out") == 1          # the existing struct, not a second one
+    from rsr_mjx_amd import _lib, physics
+    assert len(_lib.PHYS_FIELDS) == 7 and len(_lib.DYNAMICS_FIELDS) == 6 and len(_lib.CONSTRAINT_FIELDS) == 7
+    assert len(_lib.TRANSITION_FIELDS) == 3 and tuple(n for n, _ in _lib.RolloutOut._fields_) == physics.ROLLOUT_FIELDS
+
+
+def test_library_exports_and_null_handle():
+    from rsr_mjx_amd import _lib
+    L = _lib.lib()
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert "rsr_physics_sample_rollouts" in _lib.PHYS_SYMBOLS
+    fn = L.rsr_physics_sample_rollouts
+    assert fn.argtypes is not None and len(fn.argtypes) == 9
+    ids = (C.c_int32 * 2)(0, 1)
+    ctrl = (C.c_float * 8)()
+    o = _lib.RolloutOut()
+    for table, k in ((None, 0), (ids, 2), (ids, 0)):
+        assert fn(None, table, k, ctrl, 1, 1, 1, C.byref(o), None) == -1
+        assert b"null handle" in L.rsr_last_error()
+
+
+def _body(src, name):
+    b = src[src.index(name + "("):]
+    return b[:b.index("\n}\n")]
+
+
+def test_refusals_come_before_device_work():
+    """Every refusal of rsr_physics_sample_rollouts is RSR_ERR_ARG ahead of every device call (by source order, as a handle needs
+    a device), and the call allocates nothing: the handle owns no buffer for it."""
+    src = open(os.path.join(CSRC, "physics", "rsr_physics.hip")).read()
+    call = _body(src, "int rsr_physics_sample_rollouts")
+    dev = ("hipSetDevice", "hipMalloc", "hipMemset", "hipMemcpy", "zeroed_once", "launch(")
+    first_dev = min(call.index(k) for k in dev if k in call)
+    assert "launch(" in call and first_dev == call.index("physics_launch(") + len("physics_")
+    checks = ("!p)", "!ctrl)", "!out ||", "out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata)",
+              "K < 1", "T < 1", "nsteps < 1", "env_count(", "out->sensordata && p->nsd == 0", "grid > INT32_MAX",
+              "(int64_t)T * nsteps > INT32_MAX")
+    at = [call.index(c) for c in checks]
+    assert all(i < first_dev for i in at), [c for c, i in zip(checks, at) if i >= first_dev]
+    assert "(int64_t)n * K" in call and call.count("RSR_ERR_ARG") == 6
+    assert "count < 1" in _body(src, "static int env_count")
+    for k in ("hipMalloc", "hipMemset", "hipMemcpy", "hipFree", "zeroed_once", "_buffer", "new ", "std::vector"):
+        assert k not in call, k
+    assert "_alloc" not in src and src.count("static int zeroed_once(") == 1
+    # the dispatch: the constraint op with the buffer taken out of the arguments physics_args copied from the handle
+    assert "rsr::OP_PHYS_CONSTRAINT" in call and "rsr::sample_launch_args(x, env_ids, " in call
+    assert call.index("physics_args(") < call.index("x.c.out = nullptr;") < call.index("physics_launch(")
+
+
+def test_the_kernel_is_the_rollouts_loop_on_a_read_only_record():
+    kern = open(os.path.join(CSRC, "physics", "rsr_sample.hpp")).read()
+    assert "void sample_kernel(" in kern
+    code = re.sub(r"//.*", "", kern)
+    assert code.count("forward<C>(") == 1 and code.count("integrate<C>(") == 1
+    for k in ("sensor_stage<C>(", "force_stage<C>(e, ", "load_overrides<C>(m, s, a, e, lane)", "lrec_lane(lane)", "if constexpr (C::XFRC)"):
+        assert k in code, k
+    for k in ("store_pipeline", "store_side", "asm", "atomic"):
+        assert k not in kern, k
+    named = re.findall(r"\b(kinematics|com_crb_mass|load_mrow|smooth_forces|\w+_factor|\w+_solve|collision|make_constraint|solve)\b", code)
+    assert not named, named
+    # the record is read only, and neither the side buffer nor the sensordata row is written
+    assert "const float* rec = a.state + (size_t)e * L.rec;" in code and not re.search(r"(?<!const )float\* rec\b", code)
+    assert not re.search(r"\brec\[[^\]]*\]\s*=[^=]", code) and "p.sd" not in code and "p.out" not in code
+    # one flattened loop, rows and ctrl by workgroup in size_t
+    assert len(re.findall(r"\bfor \(int k = 0; k < total; \+\+k\)", code)) == 1 and "const int total = r.T * p.nsteps;" in code
+    assert "(size_t)b * r.T * C::NU" in code and "const size_t row = (size_t)b * r.T + t;" in code
+    assert "slot = b / K" in code and "p.ids ? p.ids[slot] : slot" in code and "if (e < 0 || e >= a.n) return;" in code
+
+
+def test_nothing_outside_the_physics_layer_knows():
+    for f in os.listdir(CSRC):
+        if f.endswith((".hip", ".hpp")):
+            text = open(os.path.join(CSRC, f)).read()
+            assert "sample_kernel" not in text and "rsr_sample" not in text and "SAMPLE_TAG" not in text, f
+    kernels = open(os.path.join(CSRC, "physics", "rsr_physics_kernels.hpp")).read()
+    assert '#include "rsr_sample.hpp"' in kernels
+    lp = kernels[kernels.index("int launch_physics("):]
+    at = lp.index("case OP_PHYS_CONSTRAINT:")
+    # (both after the case's label and nowhere else: the case leaves the switch for them when there is no constraint buffer)
+    assert "sample_kernel" not in lp[:at]
+    con = lp[at:]
+    assert con.count("sample_kernel<C, WAVES, Applied>") == 1 and con.count("sample_kernel<C, WAVES>") == 1
+    assert con.count("sample_kernel") == 2 and "if (!sample_args(x, &K)) return -1;" in con
+    assert con.index("if (x.c.out) return") < con.index("sample_args(") < con.index("sample_kernel")
+    assert lp.count("hipLaunchKernelGGL(") == 1 and "op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>)" in lp
+    phys = open(os.path.join(CSRC, "physics", "rsr_physics.hpp")).read()
+    assert "constexpr int SAMPLE_TAG" in phys and "inline void sample_launch_args(" in phys and "inline bool sample_args(" in phys
+    import bench
+    import parity_envelopes as PE
+    assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
+
+
+def test_physics_module_surface():
+    import torch
+    from rsr_mjx_amd import physics
+    from rsr_mjx_amd.physics import Physics
+    sig = inspect.signature(Physics.sample_rollouts)
+    assert list(sig.parameters) == ["self", "ctrl", "nsteps", "fields", "env_ids", "out"]
+    d = {k: v.default for k, v in sig.parameters.items() if k not in ("self", "ctrl")}
+    assert d == dict(nsteps=None, fields=("qpos", "qvel", "time"), env_ids=None, out=None)
+    assert sig.parameters["ctrl"].default is inspect.Parameter.empty
+    assert "Physics.sample_rollouts(ctrl [M, K, T, nu])" in physics.__doc__ and "vmap(lax.scan(mjx.step))" in physics.__doc__
+    assert "4 * M * K * T * w bytes" in Physics.sample_rollouts.__doc__
+    src = inspect.getsource(Physics.sample_rollouts)
+    assert 'self._call_envs("rsr_physics_sample_rollouts", "sample_rollouts", ' in src and "_lib.lib()" not in src
+    assert src.rindex("raise ValueError") < src.index("self._call_envs(")
+    assert "self._sample_ctrl_in = c" in src
+    assert "self._ids_in: Dict[str, Any] = {}" in inspect.getsource(Physics.__init__)
+    assert not re.search(r"self\._\w*ids_in = ", inspect.getsource(Physics))
+    # every bad input is refused before the C call (the stand-in has no handle to call with)
+    p = Physics.__new__(Physics)
+    p._h = None
+    p.num_envs, p.dims, p.qvel, p.device = 4, types.SimpleNamespace(nu=3, nq=5, nv=4, n_frames=2), torch.zeros((4, 4)), torch.device("cpu")
+    p.sensordata = torch.zeros((4, 0))                      # no sensors set
+    good = torch.zeros((4, 2, 3, 3), dtype=torch.float32)
+    cases = [(dict(ctrl=torch.zeros((4, 3, 3))), "expects ctrl"),                         # 3-D
+             (dict(ctrl=torch.zeros((4, 2, 3, 2))), "expects ctrl"),                      # wrong nu
+             (dict(ctrl=good.double()), "expects ctrl"),                                  # float64
+             (dict(ctrl=torch.zeros((4, 2, 3, 3), device="meta")), "expects ctrl"),       # wrong device
+             (dict(ctrl=good.numpy()), "expects ctrl"),
+             (dict(ctrl=good, env_ids=[0, 2]), "expects ctrl"),                           # M != len(env_ids)
+             (dict(ctrl=good[:3]), "expects ctrl"),                                       # M != num_envs
+             (dict(ctrl=good[:2], env_ids=[0, 4]), "env_ids must lie in"),
+             (dict(ctrl=good, fields=("qpos", "qacc")), "unknown"),
+             (dict(ctrl=good, fields=("sensordata",)), "no sensors are set"),
+             (dict(ctrl=good, nsteps=0), "nsteps must be >= 1"),
+             (dict(ctrl=good, out={"qpos": torch.zeros((4, 2, 3, 4))}), "out\\['qpos'\\]")]
+    for kw, msg in cases:
+        with pytest.raises(ValueError, match=msg):
+            p.sample_rollouts(**kw)

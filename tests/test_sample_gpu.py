@@ -1,0 +1,214 @@
+"""Sampled rollouts (rsr_physics_sample_rollouts, Physics.sample_rollouts) on every built family: K control sequences per env from
+the env's record as it stands are, bit for bit, what Physics.rollout records on a replica batch of N * K envs that hold the same
+record rows and per-env leaves; nothing but the caller's buffers is written; rows go by slot; the refusals hold on the device.
+No tolerance anywhere: the existing tests tie rollout_kernel to physics_kernel, to rsr_step and to the oracle."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from rsr_mjx_amd import prng
+from test_physics_rollout_gpu import ALL, FAMILIES, _assert_bitwise, _pair, _spec
+
+N, K, T = 64, 5, 4              # K odd, no divisor of N; N * K = 320 workgroups
+SIDE = ("qacc", "actuator_force", "xquat", "ncon", "contact", "ncon_dropped", "sensordata")
+
+
+def _dr(kind, envdef, n):
+    """the randomisation _pair gives its batches (same keys), or None"""
+    from rsr_mjx_amd.envs import airbot, go2
+    if kind == "tshape":
+        return None
+    if kind == "cube":
+        return airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n))
+    return go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n))
+
+
+def _replica(kind, envdef, A, k):
+    """N * k envs: env e * k + j holds env e's record row and per-env leaves"""
+    import torch
+    dr = _dr(kind, envdef, A.num_envs)
+    R = envdef.batched(A.num_envs * k, randomization=None if dr is None else {f: np.repeat(np.asarray(v), k, 0) for f, v in dr.items()})
+    R.reset(prng.split(prng.PRNGKey(7), A.num_envs * k))
+    R.record.copy_(A.record.repeat_interleave(k, 0))
+    torch.cuda.synchronize()
+    return R
+
+
+def _forces(envdef, n, nv, rng):
+    """xfrc of the order of a third of each body's weight on every body, and a qfrc"""
+    m = np.maximum(envdef.sys.arrays["body_mass"], 0.05)[None, :, None]
+    x = rng.normal(size=(n, m.shape[1], 6))
+    x[:, :, :3] *= 9.81 * m * 0.3
+    x[:, :, 3:] *= 0.981 * m * 0.3
+    return x.astype(np.float32), (rng.normal(size=(n, nv)) * 0.5).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(kind, applied=False):
+    """Batch A (reset, 3 random env steps: cube on the table, feet on the ground), its untouched twin, ctrl [N, K, T, nu] uniform
+    in the ctrl range, A's sampled rollouts and the replica batch's rollout, each computed once and left unchanged."""
+    import torch
+    from rsr_mjx_amd.physics import Physics
+    envdef, A, twin, scale, rng = _pair(kind, N)
+    spec = _spec(kind, envdef)
+    pa = Physics(A, sensors=spec)
+    R = _replica(kind, envdef, A, K)
+    pr = Physics(R, sensors=spec)
+    if applied:
+        x, q = _forces(envdef, N, A.dims.nv, rng)
+        pa.set_applied(x, q)
+        pr.set_applied(np.repeat(x, K, 0), np.repeat(q, K, 0))
+    rng_c = envdef.sys.arrays["actuator_ctrlrange"]
+    lo, hi = rng_c[:, 0], rng_c[:, 1]
+    ctrl = torch.as_tensor((lo + (hi - lo) * rng.uniform(size=(N, K, T, A.dims.nu))).astype(np.float32), device=A.device)
+    before = dict(record=A.record.clone(), **{"side " + k: pa._side[k].clone() for k in SIDE})
+    full = pa.sample_rollouts(ctrl, fields=ALL)
+    torch.cuda.synchronize()
+    after = dict(record=A.record.clone(), **{"side " + k: pa._side[k].clone() for k in SIDE})
+    ref = pr.rollout(ctrl.reshape(N * K, T, A.dims.nu), fields=ALL)
+    torch.cuda.synchronize()
+    del pr, R
+    return dict(envdef=envdef, A=A, twin=twin, pa=pa, scale=scale, ctrl=ctrl, full=full, ref=ref, before=before, after=after)
+
+
+def _check_against_replica(kind, c):
+    import torch
+    assert c["pa"].nsensordata > 0
+    for f in ALL:
+        assert c["full"][f].shape[:3] == (N, K, T)
+        _assert_bitwise(f"{kind} sample {f}", c["full"][f], c["ref"][f].reshape(N, K, T, -1))
+        assert torch.isfinite(c["full"][f]).all(), f
+    assert (c["full"]["ncon"] > 0).any()                                  # contacts were active
+    for k, v in c["before"].items():                                      # the whole record, the side buffer, sensordata
+        _assert_bitwise(f"{kind} untouched {k}", c["after"][k], v)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", FAMILIES)
+def test_samples_are_the_replica_rollout_bit_for_bit(kind):
+    import torch
+    c = _case(kind)
+    _check_against_replica(kind, c)
+    # env.step goes on as on a twin that never ran a sampled rollout
+    A, twin = c["A"], c["twin"]
+    A.record.copy_(c["before"]["record"]); twin.record.copy_(c["before"]["record"])
+    c["pa"].sample_rollouts(c["ctrl"], fields=("qpos",))
+    act = np.clip(np.random.default_rng(11).normal(size=(N, A.dims.nu)) * c["scale"], -1, 1).astype(np.float32)
+    A.step(None, act)
+    twin.step(None, act)
+    torch.cuda.synchronize()
+    _assert_bitwise(f"{kind} env.step after sample_rollouts", A.record, twin.record)
+    A.record.copy_(c["before"]["record"])
+    torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["cube", "go2flat"])
+def test_applied_forces_are_the_envs_own(kind):
+    c = _case(kind, True)
+    assert c["pa"].xfrc_applied is not None and bool((c["pa"].xfrc_applied != 0).any())
+    _check_against_replica(kind, c)
+    plain = _case(kind)
+    assert not (c["full"]["qvel"] == plain["full"]["qvel"]).all()         # (the forces were felt)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["cube", "go2rough"])
+def test_rows_go_by_slot(kind):
+    import torch
+    from rsr_mjx_amd import _lib
+    c = _case(kind)
+    A, pa, full = c["A"], c["pa"], c["full"]
+    A.record.copy_(c["before"]["record"])
+    ids = [41, 3, 17]
+    sub_ctrl = c["ctrl"][ids].contiguous()
+    # caller-owned tensors for M = 3, each the head of a larger sentinel-filled buffer: written in full, and nothing beyond
+    buf = {f: torch.full((len(ids) + 1,) + tuple(full[f].shape[1:]), -7.25, device=A.device) for f in ALL}
+    out = pa.sample_rollouts(sub_ctrl, fields=ALL, env_ids=ids, out={f: b[:len(ids)] for f, b in buf.items()})
+    torch.cuda.synchronize()
+    for f in ALL:
+        assert out[f].data_ptr() == buf[f].data_ptr()
+        for s, e in enumerate(ids):
+            _assert_bitwise(f"{kind} slot {s} (env {e}) {f}", out[f][s], full[f][e])
+        assert (buf[f][len(ids)] == -7.25).all(), f
+    _assert_bitwise(f"{kind} record", A.record, c["before"]["record"])
+    # an empty list launches nothing
+    empty = pa.sample_rollouts(sub_ctrl[:0], env_ids=[])
+    assert {f: tuple(t.shape) for f, t in empty.items()} == dict(qpos=(0, K, T, A.dims.nq), qvel=(0, K, T, A.dims.nv), time=(0, K, T, 1))
+    # the raw call: an id of num_envs runs nothing and leaves its slot's rows as they were; the other slots are right
+    for b in buf.values():
+        b.fill_(-7.25)
+    raw = torch.tensor([41, N, 17], dtype=torch.int32, device=A.device)
+    o = _lib.RolloutOut()
+    for f in ALL:
+        setattr(o, f, buf[f].data_ptr())
+    rc = _lib.lib().rsr_physics_sample_rollouts(pa._h, C.c_void_p(raw.data_ptr()), 3, C.c_void_p(sub_ctrl.data_ptr()), K, T,
+                                                pa.n_substeps, C.byref(o), pa._stream())
+    torch.cuda.synchronize()
+    assert rc == 0, _lib.lib().rsr_last_error()
+    for f in ALL:
+        _assert_bitwise(f"{kind} raw slot 0 {f}", buf[f][0], full[f][41])
+        _assert_bitwise(f"{kind} raw slot 2 {f}", buf[f][2], full[f][17])
+        assert (buf[f][1] == -7.25).all() and (buf[f][3] == -7.25).all(), f
+    _assert_bitwise(f"{kind} record after the raw call", A.record, c["before"]["record"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["cube", "go2flat"])
+def test_samples_are_indexed_by_k(kind):
+    import torch
+    from rsr_mjx_amd.physics import Physics
+    c = _case(kind)
+    A, twin, pa, ctrl = c["A"], c["twin"], c["pa"], c["ctrl"]
+    A.record.copy_(c["before"]["record"])
+    same = pa.sample_rollouts(ctrl[:, :1].expand(N, K, T, A.dims.nu).contiguous(), fields=ALL)
+    torch.cuda.synchronize()
+    for f in ALL:
+        for k in range(1, K):
+            _assert_bitwise(f"{kind} same ctrl, sample {k} {f}", same[f][:, k], same[f][:, 0])
+        _assert_bitwise(f"{kind} same ctrl is sample 0 of the distinct ones {f}", same[f][:, 0], c["full"][f][:, 0])
+    assert any(not torch.equal(c["full"]["qpos"][:, k], c["full"]["qpos"][:, 0]) for k in range(1, K))
+    # K = 1 is rollout on a copy of the batch
+    one = pa.sample_rollouts(ctrl[:, :1].contiguous(), fields=ALL)
+    twin.record.copy_(c["before"]["record"])
+    ref = Physics(twin, sensors=_spec(kind, c["envdef"])).rollout(ctrl[:, 0].contiguous(), fields=ALL)
+    torch.cuda.synchronize()
+    for f in ALL:
+        _assert_bitwise(f"{kind} K = 1 {f}", one[f][:, 0], ref[f])
+    _assert_bitwise(f"{kind} record", A.record, c["before"]["record"])
+
+
+@pytest.mark.gpu
+def test_refusals_on_the_device():
+    import torch
+    from rsr_mjx_amd import _lib
+    from rsr_mjx_amd.physics import Physics
+    c = _case("cube")
+    A, pa = c["A"], c["pa"]
+    A.record.copy_(c["before"]["record"])
+    bare = Physics(A)                                                    # a handle with no sensor table
+    L = _lib.lib()
+    fn = L.rsr_physics_sample_rollouts
+    ctrl = C.c_void_p(c["ctrl"].data_ptr())
+    ids = torch.tensor([0, 1], dtype=torch.int32, device=A.device)
+    idp = C.c_void_p(ids.data_ptr())
+    qpos = torch.full((N, K, T, A.dims.nq), -7.25, device=A.device)
+    sd = torch.full((N, K, T, pa.nsensordata), -7.25, device=A.device)
+    o, none, osd = _lib.RolloutOut(), _lib.RolloutOut(), _lib.RolloutOut()
+    o.qpos = qpos.data_ptr()
+    osd.sensordata = sd.data_ptr()
+    nf = pa.n_substeps
+    torch.cuda.synchronize()
+    before = A.record.clone()
+    for what, args in (("K = 0", (pa._h, None, 0, ctrl, 0, T, nf, C.byref(o))), ("T = 0", (pa._h, None, 0, ctrl, K, 0, nf, C.byref(o))),
+                       ("nsteps = 0", (pa._h, None, 0, ctrl, K, T, 0, C.byref(o))), ("count = 0", (pa._h, idp, 0, ctrl, K, T, nf, C.byref(o))),
+                       ("null ctrl", (pa._h, None, 0, None, K, T, nf, C.byref(o))), ("null out", (pa._h, None, 0, ctrl, K, T, nf, None)),
+                       ("all-null out", (pa._h, None, 0, ctrl, K, T, nf, C.byref(none))),
+                       ("sensordata, no table", (bare._h, None, 0, ctrl, K, T, nf, C.byref(osd)))):
+        assert fn(*args, pa._stream()) == -1, what                       # RSR_ERR_ARG
+        assert b"rsr_physics_sample_rollouts" in L.rsr_last_error(), what
+    torch.cuda.synchronize()
+    _assert_bitwise("record after the refusals", A.record, before)
+    assert (qpos == -7.25).all() and (sd == -7.25).all()
