@@ -78,24 +78,30 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
 }
 
 // The arguments of a physics op on `grid` envs (ids: which, or null: the first `grid`): the handle's buffers as every op's; the
-// caller adds the one struct its op owns (r, fd).
+// caller adds what its op owns (r, fd, inv, K).
 static rsr::Launch physics_args(rsr_physics* ph, const float* ctrl, const int* ids, int grid, int nsteps, void* hip_stream) {
   rsr::Launch x = launch_args(ph->b, hip_stream);
   x.grid = grid;
   x.a.debug = nullptr;
-  x.p = rsr::PhysArgs{ctrl, ph->out, ids, nsteps, ph->sd, rsr::SensArgs{ph->sens_el, ph->nsd, ph->acc_site}};
-  x.d = rsr::DynArgs{ph->dyn, ids, ph->jac_sites, ph->njac};
-  x.c = rsr::ConArgs{ph->con, ids};
-  if (ph->applied) x.ap = rsr::Applied{ph->xfrc, ph->qfrc};
+  x.ph.p = rsr::PhysArgs{ctrl, ph->out, ids, nsteps, ph->sd, rsr::SensArgs{ph->sens_el, ph->nsd, ph->acc_site}};
+  x.ph.d = rsr::DynArgs{ph->dyn, ids, ph->jac_sites, ph->njac};
+  x.ph.c = rsr::ConArgs{ph->con, ids};
+  if (ph->applied) x.ph.ap = rsr::Applied{ph->xfrc, ph->qfrc};
   return x;
 }
 
-// sends one physics op; reports the launch error as `who`
+// sends one physics op (rsr::PhysOp); reports the launch error as `who`
 static int physics_launch(rsr_physics* ph, int op, const rsr::Launch& x, const char* who) {
   HIPCHK(hipSetDevice(ph->b->device));
   if (launch(ph->b, op, x) < 0) return fail(RSR_ERR_UNSUPPORTED, std::string(who) + ": the model's kernels have no such op");
   { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
   return RSR_OK;
+}
+
+// a launch that advances the state, for the batch's timing: counted when it was sent
+static int counted(rsr_physics* p, int rc) {
+  if (rc == RSR_OK && p->b->timing) p->b->launches++;
+  return rc;
 }
 
 // the envs an env-list entry point runs, *n: the `count` listed ones, or with env_ids null every env of the batch
@@ -108,9 +114,7 @@ static int env_count(const rsr_physics* p, const int32_t* env_ids, int count, co
 extern "C" int rsr_physics_step(rsr_physics* p, const float* ctrl, int nsteps, void* hip_stream) {
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_step: null handle");
   if (nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_step: nsteps must be >= 1");
-  const int rc = physics_launch(p, rsr::OP_PHYS_STEP, physics_args(p, ctrl, nullptr, p->b->n, nsteps, hip_stream), "rsr_physics_step");
-  if (rc == RSR_OK && p->b->timing) p->b->launches++;
-  return rc;
+  return counted(p, physics_launch(p, rsr::OP_PHYS_STEP, physics_args(p, ctrl, nullptr, p->b->n, nsteps, hip_stream), "rsr_physics_step"));
 }
 
 extern "C" int rsr_physics_forward(rsr_physics* p, void* hip_stream) {
@@ -191,14 +195,12 @@ extern "C" int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int
   if (!p || !ctrl) return fail(RSR_ERR_ARG, "rsr_physics_rollout: null handle or ctrl");
   if (T < 1 || nsteps < 1 || (int64_t)T * nsteps > INT32_MAX) return fail(RSR_ERR_ARG, "rsr_physics_rollout: T and nsteps must be >= 1 (T * nsteps < 2^31)");
   rsr::Launch x = physics_args(p, nullptr, nullptr, p->b->n, nsteps, hip_stream);
-  rsr::RollArgs& r = x.r = rsr::RollArgs{ctrl, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  rsr::RollArgs& r = x.ph.r = rsr::RollArgs{ctrl, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (out) {
     if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_rollout: sensordata requested with no sensor table set");
     r.qpos = out->qpos; r.qvel = out->qvel; r.time = out->time; r.aforce = out->actuator_force; r.ncon = out->ncon; r.sd = out->sensordata;
   }
-  const int rc = physics_launch(p, rsr::OP_PHYS_ROLLOUT, x, "rsr_physics_rollout");
-  if (rc == RSR_OK && p->b->timing) p->b->launches++;
-  return rc;
+  return counted(p, physics_launch(p, rsr::OP_PHYS_ROLLOUT, x, "rsr_physics_rollout"));
 }
 
 extern "C" int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int K, int T, int nsteps,
@@ -215,11 +217,17 @@ extern "C" int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_id
   if (grid > INT32_MAX || (int64_t)T * nsteps > INT32_MAX)
     return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: envs x K and T x nsteps must stay below 2^31");
   rsr::Launch x = physics_args(p, nullptr, env_ids, (int)grid, nsteps, hip_stream);
-  // no constraint buffer (physics_args copies the handle's, which may exist): the op launches sample_kernel (launch_physics)
-  rsr::sample_launch_args(x, env_ids, rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata}, K);
-  x.c.out = nullptr;
-  const int rc = physics_launch(p, rsr::OP_PHYS_CONSTRAINT, x, "rsr_physics_sample_rollouts");
-  if (rc == RSR_OK && p->b->timing) p->b->launches++;
+  x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
+  x.ph.K = K;
+  return counted(p, physics_launch(p, rsr::OP_PHYS_SAMPLE, x, "rsr_physics_sample_rollouts"));
+}
+
+// the applied-force buffers, on first use: both or neither
+static int applied_buffers(rsr_physics* p, size_t xb, size_t qb, const char* who) {
+  const bool had = p->xfrc != nullptr;
+  if (const int rc = zeroed_once(p, &p->xfrc, xb, "xfrc", who)) return rc;
+  const int rc = zeroed_once(p, &p->qfrc, qb, "qfrc", who);
+  if (rc && !had) { (void)hipFree(p->xfrc); p->xfrc = nullptr; }
   return rc;
 }
 
@@ -231,13 +239,9 @@ extern "C" int rsr_physics_set_applied(rsr_physics* p, int on) {
   const size_t xb = (size_t)p->b->n * d.nbody * 6 * sizeof(float), qb = (size_t)p->b->n * d.nv * sizeof(float);
   HIPCHK(hipSetDevice(p->b->device));
   HIPCHK(hipDeviceSynchronize());               // launches in flight read the buffers (and were launched with the old choice)
-  if (on && !p->xfrc) {
-    if (hipMalloc(&p->xfrc, xb) != hipSuccess) { p->xfrc = nullptr; return fail(RSR_ERR_NOMEM, "rsr_physics_set_applied: hipMalloc(xfrc)"); }
-    if (hipMalloc(&p->qfrc, qb) != hipSuccess) {
-      (void)hipFree(p->xfrc); p->xfrc = p->qfrc = nullptr; return fail(RSR_ERR_NOMEM, "rsr_physics_set_applied: hipMalloc(qfrc)");
-    }
-  }
-  HIPCHK(hipMemset(p->xfrc, 0, xb));            // first use: zeroed; off: back to zero for the next time on
+  // (a failure reads "rsr_physics_set_applied: hipMalloc(xfrc)" / "(qfrc)")
+  if (const int rc = applied_buffers(p, xb, qb, "rsr_physics_set_applied")) return rc;
+  HIPCHK(hipMemset(p->xfrc, 0, xb));            // off: back to zero for the next time on
   HIPCHK(hipMemset(p->qfrc, 0, qb));
   HIPCHK(hipDeviceSynchronize());
   p->applied = on != 0;
@@ -358,7 +362,7 @@ extern "C" int rsr_physics_transition_fd(rsr_physics* p, const int32_t* env_ids,
   const bool states = (flags & RSR_FD_STATES) != 0;
   if (const int rc = fd_buffers(p, FL, states, "rsr_physics_transition_fd")) return rc;
   rsr::Launch x = physics_args(p, nullptr, nullptr, (int)grid, nsteps, hip_stream);
-  x.fd = rsr::FdArgs{p->fd, states ? p->fd_states : nullptr, env_ids, eps, flags};
+  x.ph.fd = rsr::FdArgs{p->fd, states ? p->fd_states : nullptr, env_ids, eps, flags};
   return physics_launch(p, rsr::OP_PHYS_TRANSITION, x, "rsr_physics_transition_fd");
 }
 
@@ -391,9 +395,8 @@ extern "C" int rsr_physics_inverse(rsr_physics* p, const float* qacc, const int3
   if (const int rc = env_count(p, env_ids, count, "rsr_physics_inverse", &n)) return rc;
   if (const int rc = inv_buffer(p, "rsr_physics_inverse")) return rc;
   rsr::Launch x = physics_args(p, nullptr, env_ids, n, 1, hip_stream);
-  x.p = rsr::inverse_launch_args(rsr::InvArgs{p->inv, env_ids, qacc, flags});
-  x.d.out = nullptr;                            // no dynamics buffer: the op launches inverse_kernel (launch_physics)
-  return physics_launch(p, rsr::OP_PHYS_DYNAMICS, x, "rsr_physics_inverse");
+  x.ph.inv = rsr::InvArgs{p->inv, env_ids, qacc, flags};
+  return physics_launch(p, rsr::OP_PHYS_INVERSE, x, "rsr_physics_inverse");
 }
 
 extern "C" int rsr_physics_inverse_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]) {

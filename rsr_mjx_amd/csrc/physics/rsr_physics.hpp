@@ -1,5 +1,5 @@
-// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics, constraint, transition and inverse buffer) and the launch arguments of its ops,
-// one struct per op of rsr_launch.hpp that needs its own (host and device).
+// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics, constraint, transition and inverse buffer) its ops (PhysOp) and their launch
+// arguments, one struct per op that needs its own (host and device).
 #pragma once
 #include "../../../include/rsr_physics.h"
 #include "../rsr_solver.hpp"
@@ -31,7 +31,7 @@ struct PhysArgs {
   SensArgs sens;
 };
 // data.xfrc_applied [nbody*6] (force, torque: world frame, at the body's COM) and data.qfrc_applied [nv] (rsr_physics_set_applied):
-// the handle's buffers [N][...], xfrc null = off (Launch::ap), or one env's rows (AppliedStage, rsr_applied.hpp)
+// the handle's buffers [N][...], xfrc null = off (PhysLaunch::ap), or one env's rows (AppliedStage, rsr_applied.hpp)
 struct Applied {
   const float* xfrc;
   const float* qfrc;
@@ -46,7 +46,7 @@ __host__ __device__ inline FdLayout fd_layout(int nq, int nv, int nu) {
   f.ncol = 2 * nv + nu; f.w = 2 * nv + RSR_MAX_SENSORDATA; f.env = f.ncol * f.w; f.xw = nq + nv + nu; f.yw = nq + nv;
   return f;
 }
-// The launch arguments of OP_PHYS_TRANSITION (Launch::fd)
+// The launch arguments of OP_PHYS_TRANSITION (PhysLaunch::fd)
 struct FdArgs {
   float* out;           // the transition buffer [N][FdLayout::env]
   float* states;        // the states buffer, or null: not kept
@@ -83,7 +83,7 @@ __host__ __device__ inline ConLayout con_layout(int nv, int nefc_max, int ncon_m
   c.stride = (c.wrench + 7 * ncon_max + 15) & ~15;
   return c;
 }
-// The launch arguments of OP_PHYS_DYNAMICS (Launch::d)
+// The launch arguments of OP_PHYS_DYNAMICS (PhysLaunch::d)
 struct DynArgs {
   float* out;           // the dynamics buffer [N][DynLayout::stride]
   const int* ids;       // [grid] the envs to run, or null: env = workgroup index
@@ -91,7 +91,7 @@ struct DynArgs {
   int nsite;
 };
 static_assert(sizeof(DynArgs) == 32, "dynamics_kernel's kernel-argument block");
-// The launch arguments of OP_PHYS_CONSTRAINT (Launch::c)
+// The launch arguments of OP_PHYS_CONSTRAINT (PhysLaunch::c)
 struct ConArgs {
   float* out;           // the constraint buffer [N][ConLayout::stride]
   const int* ids;       // [grid] the envs to run, or null: env = workgroup index
@@ -105,50 +105,38 @@ __host__ __device__ inline InvLayout inv_layout(int nv, int nefc_max) {
   i.stride = (i.force + nefc_max + 15) & ~15;
   return i;
 }
-// The kernel arguments of inverse_kernel.  The launch has no op or Launch field of its own (rsr_launch.hpp is a source of the env
-// kernels): it is sent as OP_PHYS_DYNAMICS with a null dynamics buffer (Launch::d.out), the op's unused Launch::p carrying the
-// arguments: p.out the inverse buffer, p.ids the envs, p.ctrl the accelerations, p.nsteps the flags, and INVERSE_TAG where a
-// sensor table's accelerometer site would stand (inverse_launch_args).  Only a Launch that carries the tag and both pointers is
-// read back as an inverse launch (inverse_args); any other dynamics op without a buffer is refused, not launched.
+// The launch arguments of OP_PHYS_INVERSE (PhysLaunch::inv)
 struct InvArgs {
   float* out;           // the inverse buffer [N][InvLayout::stride]
   const int* ids;       // [grid] the envs to run, or null: env = workgroup index
   const float* qacc;    // [N][nv] the accelerations, row e env e's
   int flags;            // RSR_INV_*
 };
-constexpr int INVERSE_TAG = -0x494e56;          // (no site id is negative but -1, "none")
-inline PhysArgs inverse_launch_args(const InvArgs& v) { return PhysArgs{v.qacc, v.out, v.ids, v.flags, nullptr, SensArgs{nullptr, 0, INVERSE_TAG}}; }
-// false: p is not what inverse_launch_args makes of a complete InvArgs
-inline bool inverse_args(const PhysArgs& p, InvArgs* v) {
-  if (p.sens.acc_site != INVERSE_TAG || !p.ctrl || !p.out || p.sd || p.sens.el || p.sens.nsd != 0) return false;
-  *v = InvArgs{p.out, p.ids, p.ctrl, p.nsteps};
-  return true;
-}
-// rsr_physics_sample_rollouts (rsr_sample.hpp).  sample_kernel takes a PhysArgs, a RollArgs and K; like the inverse launch it
-// has no op or Launch field of its own: it is sent as OP_PHYS_CONSTRAINT with a null constraint buffer (Launch::c.out; the
-// constraint entry point always has one).  Launch::p carries the env list, nsteps and the sensor table, with its three buffers
-// null; Launch::r ctrl [M][K][T][nu], T and the trajectory rows [M][K][T][w]; and two fields the op never reads carry the rest:
-// Launch::fd.flags K, Launch::d.nsite SAMPLE_TAG (sample_launch_args; X is the Launch, which is declared after this file).  Only
-// a Launch that carries the tag and a complete set of arguments is read back as a sampled-rollout launch (sample_args); any other
-// constraint op without a buffer is refused, not launched.
-constexpr int SAMPLE_TAG = -0x534d50;           // (no site count is negative)
-template <class X>
-inline void sample_launch_args(X& x, const int* ids, const RollArgs& r, int K) {
-  x.p.ctrl = nullptr; x.p.out = nullptr; x.p.ids = ids; x.p.sd = nullptr;
-  x.r = r;
-  x.c = ConArgs{nullptr, nullptr};
-  x.d = DynArgs{nullptr, nullptr, nullptr, SAMPLE_TAG};
-  x.fd = FdArgs{nullptr, nullptr, nullptr, 0.0f, K};
-}
-// false: x is not what sample_launch_args makes of complete arguments; otherwise *K
-template <class X>
-inline bool sample_args(const X& x, int* K) {
-  const RollArgs& r = x.r;
-  if (x.c.out || x.d.out || x.d.nsite != SAMPLE_TAG || x.fd.out || x.fd.states || x.fd.flags < 1) return false;
-  if (x.p.ctrl || x.p.out || x.p.sd || x.p.nsteps < 1 || !r.ctrl || r.T < 1) return false;
-  if (!(r.qpos || r.qvel || r.time || r.aforce || r.ncon || r.sd) || (r.sd && x.p.sens.nsd < 1)) return false;
-  *K = x.fd.flags;
-  return true;
-}
+
+// The physics ops of a family unit's launch entry (launch_physics, rsr_physics_kernels.hpp).  An entry takes its op as an int, of
+// enum Op (rsr_launch.hpp) or of this enum: these start above enum Op's, so that no value names two ops.  A new op is a member
+// here, a field of PhysLaunch if it needs one, and a case of launch_physics: nothing outside physics/ changes.
+enum PhysOp {
+  OP_PHYS_FORWARD = 64,  // rsr_physics_forward[_envs] (p): grid = envs or listed envs (p.ids)
+  OP_PHYS_STEP,          // rsr_physics_step (p)
+  OP_PHYS_ROLLOUT,       // rsr_physics_rollout (p, r)
+  OP_PHYS_DYNAMICS,      // rsr_physics_dynamics (d): grid = envs or listed envs (d.ids)
+  OP_PHYS_CONSTRAINT,    // rsr_physics_constraint (c): grid = envs or listed envs (c.ids)
+  OP_PHYS_TRANSITION,    // rsr_physics_transition_fd (p, fd): grid = envs x columns, or listed envs (fd.ids) x columns
+  OP_PHYS_INVERSE,       // rsr_physics_inverse (inv): grid = envs or listed envs (inv.ids)
+  OP_PHYS_SAMPLE,        // rsr_physics_sample_rollouts (p, r, K): grid = envs x K, or listed envs (p.ids) x K; r.ctrl [M][K][T][nu],
+                         // the trajectory rows [M][K][T][w]
+};
+// The physics ops' arguments (Launch::ph), one field per op that needs its own
+struct PhysLaunch {
+  PhysArgs p;           // OP_PHYS_FORWARD, OP_PHYS_STEP, OP_PHYS_ROLLOUT, OP_PHYS_TRANSITION, OP_PHYS_SAMPLE
+  RollArgs r;           // OP_PHYS_ROLLOUT, OP_PHYS_SAMPLE
+  DynArgs d;            // OP_PHYS_DYNAMICS
+  ConArgs c;            // OP_PHYS_CONSTRAINT
+  FdArgs fd;            // OP_PHYS_TRANSITION
+  InvArgs inv;          // OP_PHYS_INVERSE
+  int K;                // OP_PHYS_SAMPLE: the control sequences per env
+  Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
+};
 
 }  // namespace rsr

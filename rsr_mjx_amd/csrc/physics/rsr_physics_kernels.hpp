@@ -161,37 +161,26 @@ void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
   if (p.out) store_side<C>(m, s, p.out, e, lane, f.qacc);
 }
 
-// the physics ops of a family's launch entry (rsr_launch.hpp)
+// the physics ops (PhysOp, rsr_physics.hpp) of a family's launch entry, one case each; -1: not one of them (nothing is launched)
+static_assert((int)OP_STEP_OCCUPANCY < (int)OP_PHYS_FORWARD, "an entry takes an Op or a PhysOp as one int: the values must not meet");
 template <class C, int WAVES>
 int launch_physics(int op, const Launch& x) {
   // (the transition's LDS: Smem<C> and the words the first run's end state waits in)
   const size_t lds = op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>);
   auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(64), lds, x.stream, x.dm, x.L, x.a, args...); return 0; };
-  const bool ap = x.ap.xfrc != nullptr;      // applied forces on
+  const PhysLaunch& ph = x.ph;
+  const bool ap = ph.ap.xfrc != nullptr;     // applied forces on
   switch (op) {
-    case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, true, WAVES>, x.p);
-    case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, x.p, x.ap) : go(physics_kernel<C, false, WAVES>, x.p);
-    case OP_PHYS_ROLLOUT: return ap ? go(rollout_kernel<C, WAVES, Applied>, x.p, x.r, x.ap) : go(rollout_kernel<C, WAVES>, x.p, x.r);
-    case OP_PHYS_TRANSITION: return ap ? go(transition_kernel<C, WAVES, Applied>, x.p, x.fd, x.ap) : go(transition_kernel<C, WAVES>, x.p, x.fd);
-    // (applied forces enter none of the outputs of either.  rsr_physics_inverse rides on this op, with no dynamics buffer and its
-    // tagged arguments in x.p (inverse_args, rsr_physics.hpp): an op of its own means an edit to rsr_launch.hpp and the three
-    // units.  A dynamics op with no buffer and no such arguments launches nothing: -1)
-    case OP_PHYS_DYNAMICS: {
-      InvArgs v;
-      if (x.d.out) return go(dynamics_kernel<C, WAVES>, x.d);
-      return inverse_args(x.p, &v) ? go(inverse_kernel<C, WAVES>, v) : -1;
-    }
-    case OP_PHYS_CONSTRAINT:
-      if (x.c.out) return ap ? go(constraint_kernel<C, WAVES, Applied>, x.c, x.ap) : go(constraint_kernel<C, WAVES>, x.c);
-      break;                                   // (no constraint buffer: below)
+    case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, ph.p, ph.ap) : go(physics_kernel<C, true, WAVES>, ph.p);
+    case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, ph.p, ph.ap) : go(physics_kernel<C, false, WAVES>, ph.p);
+    case OP_PHYS_ROLLOUT: return ap ? go(rollout_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.ap) : go(rollout_kernel<C, WAVES>, ph.p, ph.r);
+    case OP_PHYS_TRANSITION: return ap ? go(transition_kernel<C, WAVES, Applied>, ph.p, ph.fd, ph.ap) : go(transition_kernel<C, WAVES>, ph.p, ph.fd);
+    case OP_PHYS_DYNAMICS: return go(dynamics_kernel<C, WAVES>, ph.d);      // (applied forces enter none of its outputs, nor the inverse's)
+    case OP_PHYS_CONSTRAINT: return ap ? go(constraint_kernel<C, WAVES, Applied>, ph.c, ph.ap) : go(constraint_kernel<C, WAVES>, ph.c);
+    case OP_PHYS_INVERSE: return go(inverse_kernel<C, WAVES>, ph.inv);
+    case OP_PHYS_SAMPLE: return ap ? go(sample_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.K, ph.ap) : go(sample_kernel<C, WAVES>, ph.p, ph.r, ph.K);
     default: return -1;
   }
-  // OP_PHYS_CONSTRAINT with no constraint buffer: rsr_physics_sample_rollouts rides on the op as rsr_physics_inverse rides on the
-  // dynamics op, with its tagged arguments in x.p, x.r, x.d and x.fd (sample_args, rsr_physics.hpp).  grid = slots x K.  A
-  // constraint op with no buffer and no such arguments launches nothing: -1
-  int K;
-  if (!sample_args(x, &K)) return -1;
-  return ap ? go(sample_kernel<C, WAVES, Applied>, x.p, x.r, K, x.ap) : go(sample_kernel<C, WAVES>, x.p, x.r, K);
 }
 
 }  // namespace rsr

@@ -1,4 +1,4 @@
-// rsr_cube.hip -- unit of the Airbot cube / sf kernels: env reset and step, physics forward, step, rollout, dynamics, constraint forces and transition Jacobians.
+// rsr_cube.hip -- unit of the Airbot cube / sf kernels: env reset and step, and the physics layer's kernels (launch_physics).
 #include "rsr_airbot.hpp"
 #include "physics/rsr_physics_kernels.hpp"
 
@@ -10,10 +10,7 @@ int launch_cube(int op, const Launch& x) {
     case OP_RESET: hipLaunchKernelGGL((reset_kernel<C, ENV_CUBE>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a); return 0;
     case OP_STEP: hipLaunchKernelGGL((step_kernel<C, ENV_CUBE>), dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a, x.sc); return 0;
     case OP_STEP_OCCUPANCY: return step_occupancy(step_kernel<C, ENV_CUBE>, sizeof(Smem<C>));
-    case OP_PHYS_FORWARD: case OP_PHYS_STEP: case OP_PHYS_ROLLOUT: case OP_PHYS_DYNAMICS: case OP_PHYS_CONSTRAINT:
-    case OP_PHYS_TRANSITION:
-      return launch_physics<C, RSR_WAVES_PER_EU>(op, x);
-    default: return -1;
+    default: return launch_physics<C, RSR_WAVES_PER_EU>(op, x);      // a physics op, or -1: an op the unit does not know
   }
 }
 

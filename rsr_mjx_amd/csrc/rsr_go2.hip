@@ -1,5 +1,5 @@
 // rsr_go2.hip -- unit of the Go2 kernels: joystick on a plane (Go2FlatDims) or a height field (Go2Dims), handstand / footstand
-// (HandDims); env reset and step, physics forward, step, rollout, dynamics, constraint forces and transition Jacobians of each.
+// (HandDims); env reset and step, and the physics layer's kernels (launch_physics) of each.
 #include "rsr_go2.hpp"
 #include "physics/rsr_physics_kernels.hpp"
 
@@ -13,10 +13,7 @@ static int launch_dims(int op, const Launch& x, EnvKernel reset, EnvKernel step)
     case OP_RESET: hipLaunchKernelGGL(reset, dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a); return 0;
     case OP_STEP: hipLaunchKernelGGL(step, dim3(x.grid), dim3(64), sizeof(Smem<C>), x.stream, x.dm, x.L, x.a); return 0;
     case OP_STEP_OCCUPANCY: return step_occupancy(step, sizeof(Smem<C>));
-    case OP_PHYS_FORWARD: case OP_PHYS_STEP: case OP_PHYS_ROLLOUT: case OP_PHYS_DYNAMICS: case OP_PHYS_CONSTRAINT:
-    case OP_PHYS_TRANSITION:
-      return launch_physics<C, WAVES>(op, x);
-    default: return -1;
+    default: return launch_physics<C, WAVES>(op, x);      // a physics op, or -1: an op the unit does not know
   }
 }
 

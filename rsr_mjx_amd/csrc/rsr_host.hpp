@@ -95,5 +95,5 @@ struct rsr_batch {
 rsr::StepArgs make_args(rsr_batch* b);
 // the batch's launch arguments: grid = envs, its model view, record layout and StepArgs, on the caller's stream
 rsr::Launch launch_args(rsr_batch* b, void* hip_stream);
-// op (rsr::Op) by the family unit of the batch's model (KernelSpec::family); returns what the unit's launch entry returns
+// op (rsr::Op or rsr::PhysOp) by the family unit of the batch's model (KernelSpec::family); returns what the unit's launch entry returns
 int launch(const rsr_batch* b, int op, const rsr::Launch& x);

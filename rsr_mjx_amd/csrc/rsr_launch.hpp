@@ -8,16 +8,11 @@
 
 namespace rsr {
 
+// The env ops.  The physics ops are enum PhysOp (physics/rsr_physics.hpp), whose values start above these: an entry takes either.
 enum Op {
   OP_RESET,              // rsr_reset: grid = envs
   OP_STEP,               // rsr_step: the Airbot units' persistent work-queue grid (sc), the Go2 unit's grid = envs
   OP_STEP_OCCUPANCY,     // returns the resident workgroups per CU of the step kernel (0: unknown); launches nothing
-  OP_PHYS_FORWARD,       // rsr_physics_forward[_envs]: grid = envs or listed envs (p.ids)
-  OP_PHYS_STEP,          // rsr_physics_step
-  OP_PHYS_ROLLOUT,       // rsr_physics_rollout (r)
-  OP_PHYS_DYNAMICS,      // rsr_physics_dynamics (d): grid = envs or listed envs (d.ids)
-  OP_PHYS_CONSTRAINT,    // rsr_physics_constraint (c): grid = envs or listed envs (c.ids)
-  OP_PHYS_TRANSITION,    // rsr_physics_transition_fd (fd): grid = envs x columns, or listed envs (fd.ids) x columns
 };
 
 struct Launch {
@@ -27,12 +22,7 @@ struct Launch {
   Layout L;
   StepArgs a;
   Sched sc;             // OP_STEP of the Airbot units
-  PhysArgs p;           // OP_PHYS_FORWARD, OP_PHYS_STEP, OP_PHYS_ROLLOUT, OP_PHYS_TRANSITION
-  RollArgs r;           // OP_PHYS_ROLLOUT
-  DynArgs d;            // OP_PHYS_DYNAMICS
-  ConArgs c;            // OP_PHYS_CONSTRAINT
-  FdArgs fd;            // OP_PHYS_TRANSITION
-  Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
+  PhysLaunch ph;        // the physics ops, each its own field
   int env_kind;         // the Go2 unit's pick: handstand / footstand, or the joystick with (hfield) or without the height field
   bool hfield;
 };

@@ -106,7 +106,7 @@ def test_the_kernel_lives_in_the_physics_layer():
     lp = kernels[kernels.index("int launch_physics("):]
     dyn_case = lp[lp.index("case OP_PHYS_DYNAMICS:"):lp.index("case OP_PHYS_CONSTRAINT:")]
     assert "dynamics_kernel<C, WAVES>" in dyn_case and "constraint_kernel" not in dyn_case
-    con_case = lp[lp.index("case OP_PHYS_CONSTRAINT:"):lp.index("default: return -1;")]
+    con_case = re.search(r"case OP_PHYS_CONSTRAINT:(.*?)\n\s*(?:case |default:)", lp, re.S).group(1)      # (up to the next case label)
     assert "constraint_kernel<C, WAVES, Applied>" in con_case and "constraint_kernel<C, WAVES>" in con_case
     assert re.findall(r"\b\w+_kernel\b", con_case) == ["constraint_kernel"] * 2
     dyn = open(os.path.join(CSRC, "physics", "rsr_dynamics.hpp")).read()

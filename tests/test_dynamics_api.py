@@ -84,8 +84,9 @@ def test_argument_checks_come_before_device_work():
 
 
 def test_the_dynamics_op_is_an_ordinary_op():
-    """The op is a member of enum Op and its arguments a field of struct Launch, like every other op's; nothing is carried through
-    another op's arguments.  The kernel, its arguments' type and its buffer layout stay in the physics layer."""
+    """The op is a member of the physics op enum and its arguments a field of the physics launch struct, like every other physics
+    op's (all eight are checked here); nothing is carried through another op's arguments.  The enum, the struct, the kernel, its
+    arguments' type and its buffer layout are in the physics layer: no source directly under csrc/ names a physics op."""
     import re
     csrc = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
     for d in (csrc, os.path.join(csrc, "physics")):
@@ -96,16 +97,39 @@ def test_the_dynamics_op_is_an_ordinary_op():
                 if d == csrc:
                     assert "dynamics_kernel" not in text and "struct DynArgs" not in text, f
     launch = open(os.path.join(csrc, "rsr_launch.hpp")).read()
-    assert "OP_PHYS_DYNAMICS" in re.search(r"enum Op \{(.*?)\};", launch, re.S).group(1)
-    assert re.search(r"\bDynArgs d;", re.search(r"struct Launch \{(.*?)\};", launch, re.S).group(1))
-    for unit in ("rsr_cube.hip", "rsr_tshape.hip", "rsr_go2.hip"):          # the units name the ops they forward; no catch-all
-        text = open(os.path.join(csrc, unit)).read()
-        assert "case OP_PHYS_DYNAMICS:" in text and "default: return -1;" in text, unit
     phys = open(os.path.join(csrc, "physics", "rsr_physics.hpp")).read()
-    assert "OP_PHYS_DYNAMICS = " not in phys and "struct DynArgs" in phys and "struct DynLayout" in phys
     kernels = open(os.path.join(csrc, "physics", "rsr_physics_kernels.hpp")).read()
     lp = kernels[kernels.index("int launch_physics("):]
-    assert "switch (op)" in lp and "case OP_PHYS_DYNAMICS:" in lp and "default: return -1;" in lp and "case OP_PHYS_ROLLOUT:" in lp
+    assert re.search(r"\bPhysLaunch ph;", re.search(r"struct Launch \{(.*?)\};", launch, re.S).group(1))
+    enum = re.sub(r"//.*", "", re.search(r"enum PhysOp \{(.*?)\};", phys, re.S).group(1))
+    fields = re.search(r"struct PhysLaunch \{(.*?)\};", phys, re.S).group(1)
+    # op: the field it owns (forward and step share the one struct physics_kernel takes), and every field its case may read
+    ops = {"FORWARD": ("PhysArgs p", "p ap"), "STEP": ("PhysArgs p", "p ap"), "ROLLOUT": ("RollArgs r", "p r ap"),
+           "DYNAMICS": ("DynArgs d", "d"), "CONSTRAINT": ("ConArgs c", "c ap"), "TRANSITION": ("FdArgs fd", "p fd ap"),
+           "INVERSE": ("InvArgs inv", "inv"), "SAMPLE": ("int K", "p r K ap")}
+    assert sorted(re.findall(r"\bOP_PHYS_(\w+)", enum)) == sorted(ops) and "switch (op)" in lp
+    assert len(re.findall(r"\bcase \w+:", lp)) == len(ops)                   # one case per op, nothing else
+    for op, (own, reads) in ops.items():
+        assert re.search(rf"\b{own};", fields), op
+        assert lp.count(f"case OP_PHYS_{op}:") == 1, op
+        case = re.search(rf"case OP_PHYS_{op}:(.*?)\n\s*(?:case |default:)", lp, re.S).group(1)
+        assert set(re.findall(r"\bph\.(\w+)", case)) == set(reads.split()), op
+        assert not re.search(r"\bx\.", case.replace("x.ph", "")), op         # (and nothing of the Launch but through the lambda)
+    # the two enums share the entries' int: the physics ops start above the env ops, stated next to both and checked
+    env_ops = re.findall(r"\bOP_\w+", re.sub(r"//.*", "", re.search(r"enum Op \{(.*?)\};", launch, re.S).group(1)))
+    assert env_ops == ["OP_RESET", "OP_STEP", "OP_STEP_OCCUPANCY"]
+    assert int(re.search(r"OP_PHYS_FORWARD = (\d+),", enum).group(1)) > len(env_ops) and enum.count("=") == 1
+    assert "static_assert((int)OP_STEP_OCCUPANCY < (int)OP_PHYS_FORWARD," in kernels
+    # no source directly under csrc/ names an individual physics op; each unit sends what it does not handle itself to
+    # launch_physics, which launches nothing for an op it does not know
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".hpp")):
+            assert "OP_PHYS_" not in open(os.path.join(csrc, f)).read(), f
+    for unit in ("rsr_cube.hip", "rsr_tshape.hip", "rsr_go2.hip"):
+        text = open(os.path.join(csrc, unit)).read()
+        assert text.count("default: return launch_physics<") == 1 and "default: return -1;" not in text, unit
+    assert lp.rstrip().endswith("default: return -1;\n  }\n}\n\n}  // namespace rsr")
+    assert "struct DynArgs" in phys and "struct DynLayout" in phys
     kern = open(os.path.join(csrc, "physics", "rsr_dynamics.hpp")).read()
     assert "void dynamics_kernel(" in kern
     for stage in ("kinematics<C>(", "com_crb_mass<C>(", "smooth_forces<C>("):

@@ -70,6 +70,10 @@ def test_refusals_come_before_device_work():
     for check in ("!p)", "!qacc)", "flags & ~RSR_INV_DISCRETE", "env_count("):
         assert call.index(check) < first_dev(call), check
     assert "count < 1" in body("static int env_count") and first_dev(call) < call.index("physics_launch(")
+    # the dispatch: its own op with its own field, filled after the arguments physics_args shares; no other op's field is touched
+    assert "rsr::OP_PHYS_INVERSE" in call and len(re.findall(r"\bOP_PHYS_\w+", call)) == 1
+    assert call.index("physics_args(") < call.index("x.ph.inv = rsr::InvArgs{p->inv, env_ids, qacc, flags};") < call.index("physics_launch(")
+    assert set(re.findall(r"\bx\.ph\.(\w+)", call)) == {"inv"}
     view = body("int rsr_physics_inverse_view")
     assert view.index("default: return fail(RSR_ERR_ARG") < first_dev(view) and "inv_buffer(" in view
     for f in ("QFRC_INVERSE", "QFRC_CONSTRAINT", "QACC", "QFRC_ACTUATOR", "EFC_COUNTS", "EFC_FORCE"):
@@ -101,8 +105,22 @@ def test_the_kernel_restates_the_pass_without_the_solve():
     kernels = open(os.path.join(CSRC, "physics", "rsr_physics_kernels.hpp")).read()
     lp = kernels[kernels.index("int launch_physics("):]
     assert lp.count("inverse_kernel<C, WAVES>") == 1
+    # the op's own case, up to the next case label: its kernel with its arguments, and no other kernel
+    case = re.search(r"case OP_PHYS_INVERSE:(.*?)\n\s*(?:case |default:)", lp, re.S).group(1)
+    assert "go(inverse_kernel<C, WAVES>, ph.inv)" in case and re.findall(r"\b\w+_kernel\b", case) == ["inverse_kernel"]
     phys = open(os.path.join(CSRC, "physics", "rsr_physics.hpp")).read()
     assert "struct InvLayout" in phys and "struct InvArgs" in phys
+    for top in (CSRC, os.path.join(ROOT, "include")):      # the protocol that carried the launch on the dynamics op is gone
+        for d, _, files in os.walk(top):
+            for f in files:
+                if f.endswith((".hip", ".hpp", ".h")):
+                    text = open(os.path.join(d, f)).read()
+                    for gone in ("INVERSE_TAG", "SAMPLE_TAG", "inverse_launch_args", "inverse_args", "sample_launch_args", "sample_args"):
+                        assert gone not in text, (f, gone)
+    for f in os.listdir(CSRC):                             # nothing outside the physics layer knows
+        if f.endswith((".hip", ".hpp")):
+            text = open(os.path.join(CSRC, f)).read()
+            assert "inverse_kernel" not in text and "rsr_inverse" not in text and "OP_PHYS_INVERSE" not in text and "InvArgs" not in text, f
 
 
 def test_physics_module_surface():

@@ -70,9 +70,10 @@ def test_refusals_come_before_device_work():
     for k in ("hipMalloc", "hipMemset", "hipMemcpy", "hipFree", "zeroed_once", "_buffer", "new ", "std::vector"):
         assert k not in call, k
     assert "_alloc" not in src and src.count("static int zeroed_once(") == 1
-    # the dispatch: the constraint op with the buffer taken out of the arguments physics_args copied from the handle
-    assert "rsr::OP_PHYS_CONSTRAINT" in call and "rsr::sample_launch_args(x, env_ids, " in call
-    assert call.index("physics_args(") < call.index("x.c.out = nullptr;") < call.index("physics_launch(")
+    # the dispatch: its own op with its own fields, filled after the arguments physics_args shares; no other op's field is touched
+    assert "rsr::OP_PHYS_SAMPLE" in call and len(re.findall(r"\bOP_PHYS_\w+", call)) == 1
+    assert call.index("physics_args(") < call.index("x.ph.r = rsr::RollArgs{ctrl, T, ") < call.index("x.ph.K = K;") < call.index("physics_launch(")
+    assert sorted(set(re.findall(r"\bx\.ph\.(\w+)", call))) == ["K", "r"]
 
 
 def test_the_kernel_is_the_rollouts_loop_on_a_read_only_record():
@@ -99,20 +100,26 @@ def test_nothing_outside_the_physics_layer_knows():
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
             text = open(os.path.join(CSRC, f)).read()
-            assert "sample_kernel" not in text and "rsr_sample" not in text and "SAMPLE_TAG" not in text, f
+            assert "sample_kernel" not in text and "rsr_sample" not in text and "OP_PHYS_SAMPLE" not in text, f
     kernels = open(os.path.join(CSRC, "physics", "rsr_physics_kernels.hpp")).read()
     assert '#include "rsr_sample.hpp"' in kernels
     lp = kernels[kernels.index("int launch_physics("):]
-    at = lp.index("case OP_PHYS_CONSTRAINT:")
-    # (both after the case's label and nowhere else: the case leaves the switch for them when there is no constraint buffer)
-    assert "sample_kernel" not in lp[:at]
-    con = lp[at:]
-    assert con.count("sample_kernel<C, WAVES, Applied>") == 1 and con.count("sample_kernel<C, WAVES>") == 1
-    assert con.count("sample_kernel") == 2 and "if (!sample_args(x, &K)) return -1;" in con
-    assert con.index("if (x.c.out) return") < con.index("sample_args(") < con.index("sample_kernel")
+    # the op's own case, up to the next case label: its kernel, plain and applied, with p, r and K, and no other kernel
+    case = re.search(r"case OP_PHYS_SAMPLE:(.*?)\n\s*(?:case |default:)", lp, re.S).group(1)
+    assert case.count("sample_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.K, ph.ap)") == 1 and case.count("sample_kernel<C, WAVES>, ph.p, ph.r, ph.K)") == 1
+    assert re.findall(r"\b\w+_kernel\b", case) == ["sample_kernel"] * 2 and lp.count("sample_kernel") == 2
     assert lp.count("hipLaunchKernelGGL(") == 1 and "op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>)" in lp
+    assert lp.rstrip().endswith("default: return -1;\n  }\n}\n\n}  // namespace rsr")      # nothing follows the switch
     phys = open(os.path.join(CSRC, "physics", "rsr_physics.hpp")).read()
-    assert "constexpr int SAMPLE_TAG" in phys and "inline void sample_launch_args(" in phys and "inline bool sample_args(" in phys
+    assert re.search(r"\bint K;", re.search(r"struct PhysLaunch \{(.*?)\};", phys, re.S).group(1))
+    # the protocol that carried this launch and the inverse's on other ops is gone from every source
+    for top in (CSRC, os.path.join(ROOT, "include")):
+        for d, _, files in os.walk(top):
+            for f in files:
+                if f.endswith((".hip", ".hpp", ".h")):
+                    text = open(os.path.join(d, f)).read()
+                    for gone in ("INVERSE_TAG", "SAMPLE_TAG", "inverse_launch_args", "inverse_args", "sample_launch_args", "sample_args"):
+                        assert gone not in text, (f, gone)
     import bench
     import parity_envelopes as PE
     assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()

@@ -1,6 +1,7 @@
 """Sampled rollouts (rsr_physics_sample_rollouts, Physics.sample_rollouts) on every built family: K control sequences per env from
 the env's record as it stands are, bit for bit, what Physics.rollout records on a replica batch of N * K envs that hold the same
-record rows and per-env leaves; nothing but the caller's buffers is written; rows go by slot; the refusals hold on the device.
+record rows and per-env leaves; nothing but the caller's buffers is written; rows go by slot; the handle's other buffers do not
+enter the dispatch; the refusals hold on the device.
 No tolerance anywhere: the existing tests tie rollout_kernel to physics_kernel, to rsr_step and to the oracle."""
 import ctypes as C
 import functools
@@ -178,6 +179,43 @@ def test_samples_are_indexed_by_k(kind):
     for f in ALL:
         _assert_bitwise(f"{kind} K = 1 {f}", one[f][:, 0], ref[f])
     _assert_bitwise(f"{kind} record", A.record, c["before"]["record"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", FAMILIES)
+def test_dispatch_ignores_the_handles_other_buffers(kind):
+    """Which kernel a call launches depends on the call alone, not on which of the handle's buffers exist: sample_rollouts and
+    inverse on a fresh handle, and on a second handle of the same batch that has run dynamics, constraint_forces and
+    transition_fd (so that it owns those buffers) and has applied forces on, all zero, give bit-identical outputs from the same
+    state.  Nothing about the values is asserted (the tests above and tests/test_inverse_gpu.py do that)."""
+    import torch
+    from rsr_mjx_amd.physics import Physics
+    n, k, t = 2, 2, 2
+    envdef, A, _, _, rng = _pair(kind, n)
+    spec = _spec(kind, envdef)
+    lo, hi = envdef.sys.arrays["actuator_ctrlrange"].T
+    ctrl = torch.as_tensor((lo + (hi - lo) * rng.uniform(size=(n, k, t, A.dims.nu))).astype(np.float32), device=A.device)
+    qacc = (5.0 * torch.randn((n, A.dims.nv), generator=torch.Generator(device="cpu").manual_seed(2))).to(A.device).contiguous()
+    state = {f: A.view(f).clone() for f in ("qpos", "qvel", "ctrl")}
+
+    def run(phys):
+        phys.set_state(**state)                                           # the same record for both handles
+        out = {"sample " + f: v.clone() for f, v in phys.sample_rollouts(ctrl, nsteps=1, fields=ALL).items()}
+        phys.inverse(qacc)
+        out.update({"inverse " + f: v.clone() for f, v in phys._inv_views().items()})
+        torch.cuda.synchronize()
+        return out
+    first = run(Physics(A, sensors=spec))
+    second = Physics(A, sensors=spec)
+    second.dynamics()
+    second.constraint_forces()
+    second.transition_fd(nsteps=1)
+    second.set_applied()                                                  # on, zero everywhere
+    assert second.xfrc_applied is not None and not bool(second.xfrc_applied.any()) and not bool(second.qfrc_applied.any())
+    again = run(second)
+    assert sorted(first) == sorted(again) and len(first) == len(ALL) + 6
+    for f, v in first.items():
+        _assert_bitwise(f"{kind} {f}", again[f], v)
 
 
 @pytest.mark.gpu

@@ -68,8 +68,8 @@ def test_refusals_come_before_device_work():
     assert 'if (env_ids && count < 1) return fail(RSR_ERR_ARG, std::string(who) + ": count < 1 with env_ids");' in count
     assert not any(k in count for k in dev)
     assert call.count("RSR_ERR_ARG") + count.count("RSR_ERR_ARG") >= 5 and "fd_buffers(" in call
-    assert "OP_PHYS_TRANSITION" in call and "x.fd = rsr::FdArgs{" in call and "OP_PHYS_ROLLOUT" not in call      # an op of its own
-    assert "RollArgs" not in call and "x.r" not in call
+    assert "OP_PHYS_TRANSITION" in call and "x.ph.fd = rsr::FdArgs{" in call and "OP_PHYS_ROLLOUT" not in call      # an op of its own
+    assert "RollArgs" not in call and "x.ph.r" not in call and set(re.findall(r"\bx\.ph\.(\w+)", call)) == {"fd"}
     view = body("int rsr_physics_transition_view")
     assert view.index("default: return fail(RSR_ERR_ARG") < first_dev(view)
     for f in ("COLUMNS", "STATES_X", "STATES_Y"):
@@ -89,8 +89,9 @@ def test_refusals_come_before_device_work():
 def test_the_kernel_lives_in_the_physics_layer():
     """transition_kernel is a file of its own under csrc/physics that calls the step's stages instead of restating them: one
     forward<C> in the loop over the two runs' substeps (or two calls), no inline assembly, no read-modify-write memory
-    operations.  Its launch is an op of its own, a member of enum Op with its arguments a field of struct Launch, which every
-    unit forwards; no source directly under csrc/ knows of the kernel, and the parity envelopes were measured on these sources."""
+    operations.  Its launch is an op of its own, a member of the physics op enum with its arguments a field of the physics launch
+    struct (tests/test_dynamics_api.py checks every physics op's), which every unit forwards without naming it; no source directly
+    under csrc/ knows of the kernel or the op, and the parity envelopes were measured on these sources."""
     kern = open(os.path.join(CSRC, "physics", "rsr_transition.hpp")).read()
     assert "void transition_kernel(" in kern
     code = re.sub(r"//.*", "", kern)
@@ -105,25 +106,24 @@ def test_the_kernel_lives_in_the_physics_layer():
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
             text = open(os.path.join(CSRC, f)).read()
-            assert "transition_kernel" not in text and "FdLayout" not in text and "rsr_transition" not in text, f
-    launch = open(os.path.join(CSRC, "rsr_launch.hpp")).read()
-    assert "OP_PHYS_TRANSITION" in re.search(r"enum Op \{(.*?)\};", launch, re.S).group(1)
-    assert re.search(r"\bFdArgs fd;", re.search(r"struct Launch \{(.*?)\};", launch, re.S).group(1))
-    for unit in ("rsr_cube.hip", "rsr_tshape.hip", "rsr_go2.hip"):          # the units name the ops they forward; no catch-all
-        text = open(os.path.join(CSRC, unit)).read()
-        assert "case OP_PHYS_TRANSITION:" in text and "default: return -1;" in text, unit
+            assert "transition_kernel" not in text and "FdLayout" not in text and "rsr_transition" not in text and "OP_PHYS_" not in text, f
+    phys = open(os.path.join(CSRC, "physics", "rsr_physics.hpp")).read()
+    assert "OP_PHYS_TRANSITION" in re.search(r"enum PhysOp \{(.*?)\};", phys, re.S).group(1)
+    assert re.search(r"\bFdArgs fd;", re.search(r"struct PhysLaunch \{(.*?)\};", phys, re.S).group(1))
+    for unit in ("rsr_cube.hip", "rsr_tshape.hip", "rsr_go2.hip"):          # each unit reaches launch_physics, which knows the ops
+        assert "launch_physics<" in open(os.path.join(CSRC, unit)).read(), unit
     kernels = open(os.path.join(CSRC, "physics", "rsr_physics_kernels.hpp")).read()
     lp = kernels[kernels.index("int launch_physics("):]
+    assert lp.rstrip().endswith("default: return -1;\n  }\n}\n\n}  // namespace rsr")
     assert "switch (op)" in lp and "gofd" not in lp and lp.count("hipLaunchKernelGGL(") == 1      # one launch lambda
     assert "op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>)" in lp
     roll_case = lp[lp.index("case OP_PHYS_ROLLOUT:"):lp.index("case OP_PHYS_TRANSITION:")]
     assert "rollout_kernel<C, WAVES, Applied>" in roll_case and "rollout_kernel<C, WAVES>" in roll_case
     assert re.findall(r"\b\w+_kernel\b", roll_case) == ["rollout_kernel"] * 2 and "fd" not in roll_case and roll_case.count("\n") == 1
     fd_case = lp[lp.index("case OP_PHYS_TRANSITION:"):lp.index("case OP_PHYS_DYNAMICS:")]
-    assert "transition_kernel<C, WAVES, Applied>" in fd_case and "transition_kernel<C, WAVES>" in fd_case and "x.fd" in fd_case
+    assert "transition_kernel<C, WAVES, Applied>" in fd_case and "transition_kernel<C, WAVES>" in fd_case and "ph.fd" in fd_case
     assert re.findall(r"\b\w+_kernel\b", fd_case) == ["transition_kernel"] * 2
     assert "transition_kernel" not in lp[lp.index("case OP_PHYS_DYNAMICS:"):] and lp.count("transition_kernel") == 2
-    phys = open(os.path.join(CSRC, "physics", "rsr_physics.hpp")).read()
     assert "struct FdArgs" in phys and "struct FdLayout" in phys
     roll = re.search(r"struct RollArgs \{(.*?)\};", phys, re.S).group(1)      # again exactly what rollout_kernel reads
     assert "fd" not in roll and "FdArgs" not in roll
