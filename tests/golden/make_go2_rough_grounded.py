@@ -1,8 +1,8 @@
 """Rough-terrain Go2 states that stand on the terrain, for the physics-layer tests (tests/test_go2_rough_grounded_gpu.py): the reset
-distribution spawns the robots clear of the ground, so the states of test_physics_gpu._random_states hardly ever touch the height
+distribution spawns the robots clear of the ground, so the states of physics_support.random_states hardly ever touch the height
 field.  Generated with this repository's fp64 oracle: the oracle's reset states of Go2JoystickRoughTerrain for PRNGKey(SEED),
 position targets at the reset pose (the home keyframe), SETTLE physics substeps so that the robots land, then the perturbation of
-_random_states (hinge angles + N(0, 0.05), qvel + N(0, 0.2)) with the ctrl kept within N(0, 0.02) of the pose so that the feet stay
+random_states (hinge angles + N(0, 0.05), qvel + N(0, 0.2)) with the ctrl kept within N(0, 0.02) of the pose so that the feet stay
 loaded, the trunk lowered to where a third foot touches and the velocity perturbation of an env halved until each of its contacts
 carries load (both below; 12 halvings in all).  Written to
 tests/golden/go2_rough_grounded_states.npz: inputs only (qpos, qvel, ctrl of 256 envs, float32).

@@ -20,10 +20,10 @@ def run(request, oracle_mod):
     import torch
     from rsr_mjx_amd import prng
     from rsr_mjx_amd.physics import Physics
-    from test_physics_gpu import _make
+    from physics_support import make
     S = load_scene(oracle_mod, request.param, near=False)
     n = len(S["qpos"])
-    envdef, E, _, _ = _make(S["name"], n, False)
+    envdef, E, _, _ = make(S["name"], n, False)
     assert E.dims.ncon_max == S["cap"]
     E.reset(prng.split(prng.PRNGKey(2), n))
     phys = Physics(E)
@@ -200,12 +200,12 @@ def test_branch_census_of_existing_states(run, oracle_mod):
     pair in contact (fp64 labels).  Printed; the figures are in DESIGN.md."""
     import torch
     from rsr_mjx_amd import prng
-    from test_physics_gpu import _make, _random_states
+    from physics_support import make, random_states
     S = run
     n = 256
-    envdef, E, _, _ = _make(S["name"], n, False)
+    envdef, E, _, _ = make(S["name"], n, False)
     E.reset(prng.split(prng.PRNGKey(2), n))
-    qpos, _, _ = _random_states(envdef, S["name"], n, 12)
+    qpos, _, _ = random_states(envdef, S["name"], n, 12)
     torch.cuda.synchronize()
     o64 = oracle_mod.Oracle(E.blob, "f64")
     old = [BC.pair_results(S["arrays"], *BC.oracle_contacts(o64, q, E.dims.nv, E.dims.nu)[2:]) for q in qpos]

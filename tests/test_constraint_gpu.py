@@ -2,141 +2,26 @@
 family: efc_force, qfrc_constraint and qacc against the CPU oracle, the contact wrench against the oracle's Jacobian rows, sign and
 closure on the device alone, consistency with dynamics(), bit identity with forward(), no side effects, the Go2 warm start.
 
-States: _random_states(envdef, kind, 256, 11), the states of test_physics_gpu's forward test, DR off.  Errors are relative as
-there, |hip - ref| / max(1, |ref|_inf of that env's field), and the bound is the project's rule (_rule of test_dynamics_gpu):
-p99 <= 1e-5 or <= 3 x the fp32 oracle's own p99 distance from the fp64 oracle, and every env within max(1e-4, 20 x the largest
-such distance).  An env whose row counts (ne, nf, nl, ncon) differ between the kernel and the fp64 oracle, or between the fp32 and
-fp64 oracles, is excluded (a contact or limit mode flip); at most 2 % of the envs may be.  On the CPU, with the oracle's own reset
-states for seed 11 and the same perturbation, the fp32-vs-fp64 part of that excludes 0 (cube), 0 (tshape), 0 (go2flat),
-0 (go2rough) and 0 (footstand) of 256 envs, so seed 11 stays.
+States: random_states(envdef, kind, 256, 11), the states of test_physics_gpu's forward test, DR off.  Errors, the rule and the
+exclusion of envs whose row counts flip: tests/physics_support.py.  On the CPU, with the oracle's own reset states for seed 11 and
+the same perturbation, the fp32-vs-fp64 part of that excludes 0 (cube), 0 (tshape), 0 (go2flat), 0 (go2rough) and 0 (footstand) of
+256 envs, so seed 11 stays.
 
 Contact slots: the kernel and the oracle list the contacts of an env in the same order (geom pair by geom pair); the tests check
 that on the geom ids of every kept env rather than assume it."""
 import numpy as np
 import pytest
 
+from physics_support import (FAMILIES, GO2, PIPE, all_but, assert_unchanged, bits, closure_residual, free_trees, handle_snapshot,
+                             handle_views, keep_constraint, make, oracle_pass, ref_wrench, rel, rule, setup, wrench_on_root)
+from physics_support import npyr as npyr_of
 from rsr_mjx_amd import prng
-from test_dynamics_gpu import _rule
-from test_physics_gpu import FAMILIES, PIPE, _make, _random_states, _rel
 
 N = 256
-SEED = 11
-GO2 = ("go2flat", "go2rough", "footstand")
 
 
-def oracle_rows(oracle_mod, blob, nv, ncon_max, nefc_max, qpos, qvel, ctrl, warm=None):
-    """{precision: per-env list of dicts} of Oracle.forward(qpos, qvel, ctrl, warm or zeros): efc_force (padded to nefc_max),
-    efc_J [nefc, nv], qfrc_constraint, qacc, counts (ne, nf, nl, ncon), contacts [ncon, 10], xpos, xmat, M, qfrc_smooth."""
-    out = {}
-    for p in ("f32", "f64"):
-        o = oracle_mod.Oracle(blob, p)
-        o.set_ncon_cap(ncon_max)
-        rows = []
-        for e in range(len(qpos)):
-            w = np.zeros(nv) if warm is None else warm[e].astype(np.float64)
-            o.forward(qpos[e].astype(np.float64), qvel[e].astype(np.float64), ctrl[e], w, step=False)
-            nefc, ne, nf, ncon = (int(x) for x in o.get("counts")[:4])
-            con = o.get("contacts").reshape(-1, 10)
-            f = np.zeros(nefc_max)
-            f[:nefc] = o.get("efc_force")
-            rows.append(dict(nefc=nefc, efc_force=f, efc_J=o.get("efc_J").reshape(nefc, nv), qfrc_constraint=o.get("qfrc_constraint"),
-                             qacc=o.get("qacc"), contacts=con, xpos=o.get("xpos").reshape(-1, 3), xmat=o.get("xmat").reshape(-1, 3, 3),
-                             M=o.get("M").reshape(nv, nv), qfrc_smooth=o.get("qfrc_smooth"), ne=ne, nf=nf, ncon=ncon))
-        out[p] = rows
-    return out
-
-
-def counts_of(rows, npyr):
-    """[n, 4] (ne, nf, nl, ncon) of oracle_rows' per-env list"""
-    return np.array([[r["ne"], r["nf"], r["nefc"] - r["ne"] - r["nf"] - npyr * r["ncon"], r["ncon"]] for r in rows])
-
-
-def free_trees(A):
-    """{root body: first dof} of the kinematic trees that hang on a free joint"""
-    return {int(A["jnt_bodyid"][j]): int(A["jnt_dofadr"][j]) for j in range(len(A["jnt_type"])) if int(A["jnt_type"][j]) == 0}
-
-
-def ref_wrench(r, A, npyr, ncon_max):
-    """The force and torque (about the root body's origin, in its frame) that each contact of oracle env `r` puts on a free-jointed
-    tree, from the oracle's own rows: sum over the contact's pyramid rows of efc_J[row, d:d+3] f and efc_J[row, d+3:d+6] f (d: the
-    tree's free joint).  Returns force [ncon_max, 2, 3], torque [ncon_max, 2, 3] (index 1: the side, 0 = body1's tree,
-    1 = body2's), on [ncon_max, 2] (the side's tree is free-jointed) and root [ncon_max, 2]."""
-    free = free_trees(A)
-    F, T = np.zeros((ncon_max, 2, 3)), np.zeros((ncon_max, 2, 3))
-    on, root = np.zeros((ncon_max, 2), bool), np.zeros((ncon_max, 2), int)
-    rcon = r["nefc"] - npyr * r["ncon"]
-    for c in range(r["ncon"]):
-        rows = slice(rcon + npyr * c, rcon + npyr * (c + 1))
-        f = r["efc_force"][rows]
-        for side in (0, 1):
-            rb = int(A["body_rootid"][int(r["contacts"][c, 7 + side])])
-            if rb in free:
-                d = free[rb]
-                # a tree on both sides of one contact would put both sides' columns in the same dofs
-                other = int(A["body_rootid"][int(r["contacts"][c, 8 - side])])
-                assert other != rb
-                on[c, side], root[c, side] = True, rb
-                F[c, side] = f @ r["efc_J"][rows, d:d + 3]
-                T[c, side] = f @ r["efc_J"][rows, d + 3:d + 6]
-    return F, T, on, root
-
-
-def wrench_on_root(pos, force, torque, r, root, sign):
-    """R_root^T [(pos - xpos_root) x F + tau] with F = sign * force, tau = sign * torque: the generalised force a wrench at `pos`
-    puts on a free joint's rotational dofs (they are expressed in the body frame)"""
-    Fw, tw = sign * np.asarray(force, np.float64), sign * np.asarray(torque, np.float64)
-    return r["xmat"][root].T @ (np.cross(np.asarray(pos, np.float64) - r["xpos"][root], Fw) + tw)
-
-
-def _setup(kind, oracle_mod=None, zero_floss=False):
-    import torch
-    from rsr_mjx_amd.physics import Physics
-    envdef, E, _, _ = _make(kind, N, False)
-    if zero_floss:
-        E.set_randomization({"dof_frictionloss": np.zeros((N, E.dims.nv), np.float32)})
-    E.reset(prng.split(prng.PRNGKey(1), N))
-    qpos, qvel, ctrl = _random_states(envdef, kind, N, SEED)
-    phys = Physics(E)
-    return envdef, E, phys, qpos, qvel, ctrl
-
-
-_REF = {}
-
-
-def _ref(oracle_mod, kind, E, qpos, qvel, ctrl, blob=None, tag=""):
-    key = (kind, tag)
-    if key not in _REF:
-        _REF[key] = oracle_rows(oracle_mod, blob or E.blob, E.dims.nv, E.dims.ncon_max, E.dims.nefc_max, qpos, qvel, ctrl)
-    return _REF[key]
-
-
-def _npyr(E):
-    """pyramid edges per contact: 2 (condim - 1), one condim per model"""
-    condim = np.unique(E.sys.arrays["pair_condim"])
-    assert len(condim) == 1
-    return 2 * (int(condim[0]) - 1)
-
-
-def _keep(kind, phys, ref, npyr):
-    """envs whose (ne, nf, nl, ncon) agree between the kernel, the f64 oracle and the f32 oracle; asserts the 2 % condition and
-    that the kept envs list their contacts in the oracle's order"""
-    A = phys.env.sys.arrays
-    hc = phys.efc_counts.cpu().numpy().astype(int)
-    hip = np.stack([hc[:, 1], hc[:, 2], hc[:, 3], phys.contact_forces()["ncon"].cpu().numpy()], 1)
-    assert (hc[:, 0] == hip[:, 0] + hip[:, 1] + hip[:, 2] + npyr * hip[:, 3]).all()
-    c64, c32 = counts_of(ref["f64"], npyr), counts_of(ref["f32"], npyr)
-    flips = (hip != c64).any(1) | (c32 != c64).any(1)
-    print(kind, "excluded envs: %d of %d (kernel vs f64 %d, f32 vs f64 %d)" % (flips.sum(), N, (hip != c64).any(1).sum(), (c32 != c64).any(1).sum()))
-    assert flips.mean() <= 0.02, f"{kind}: row counts differ in {flips.sum()} of {N} envs"
-    keep = ~flips
-    cf = phys.contact_forces()
-    g1, g2 = cf["geom1"].cpu().numpy(), cf["geom2"].cpu().numpy()
-    for e in np.nonzero(keep)[0]:
-        for p in ("f32", "f64"):
-            pair = ref[p][e]["contacts"][:, 9].astype(int)
-            nc = len(pair)
-            assert (g1[e, :nc] == A["pair_geom1"][pair]).all() and (g2[e, :nc] == A["pair_geom2"][pair]).all(), (kind, e, "contact order")
-    return keep
+def _ref(oracle_mod, E, qpos, qvel, ctrl, blob=None):
+    return oracle_pass(oracle_mod, blob or E.blob, E.dims, qpos, qvel, ctrl)
 
 
 @pytest.mark.gpu
@@ -147,7 +32,7 @@ def test_constraint_forces_match_the_oracle(oracle_mod, kind):
     is given zeros, so the record's warm start is zeroed before the call (the Go2 solve is one Newton iteration: the start
     matters, and the two sides must start alike)."""
     import torch
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind)
     assert float(phys.efc_force.abs().max()) == 0.0 and float(phys.contact_forces()["force"].abs().max()) == 0.0      # zeros until the first call
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.qacc_warmstart.zero_()                                    # (set_state leaves the forward pass's qacc there)
@@ -156,15 +41,15 @@ def test_constraint_forces_match_the_oracle(oracle_mod, kind):
     d = E.dims
     assert phys.efc_force.shape == (N, d.nefc_max) and phys.qfrc_constraint.shape == (N, d.nv)
     assert phys.efc_counts.shape == (N, 4) and phys.constraint_qacc.shape == (N, d.nv)
-    ref = _ref(oracle_mod, kind, E, qpos, qvel, ctrl)
-    npyr = _npyr(E)
-    keep = _keep(kind, phys, ref, npyr)
+    ref = _ref(oracle_mod, E, qpos, qvel, ctrl)
+    npyr = npyr_of(E)
+    keep = keep_constraint(kind, phys, ref, npyr)
     hip = dict(efc_force=phys.efc_force, qfrc_constraint=phys.qfrc_constraint, qacc=phys.constraint_qacc)
     fails = []
     for f, t in hip.items():
         h = t.cpu().numpy().astype(np.float64)
         r64, r32 = (np.stack([r[f] for r in ref[p]]) for p in ("f64", "f32"))
-        _rule(kind, f, _rel(h, r64)[keep], _rel(r32, r64)[keep], fails)
+        rule(kind, f, rel(h, r64)[keep], rel(r32, r64)[keep], fails)
     # rows >= nefc are zero
     nefc = phys.efc_counts[:, 0].cpu().numpy().astype(int)
     ef = phys.efc_force.cpu().numpy()
@@ -186,15 +71,15 @@ def test_contact_wrench_matches_the_oracle_rows(oracle_mod, kind):
     (The rough-terrain Go2 spawns clear of the ground: a handful of contacts in 256 envs, all of them checked.)  normal_force >= 0 and equal to the sum of the contact's edge forces (summed in pairs, as the kernel folds
     them) to 1 ulp; slots >= ncon are zero."""
     import torch
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind)
     A = envdef.sys.arrays
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.qacc_warmstart.zero_()
     phys.constraint_forces()
     torch.cuda.synchronize()
-    ref = _ref(oracle_mod, kind, E, qpos, qvel, ctrl)
-    npyr, K = _npyr(E), E.dims.ncon_max
-    keep = _keep(kind, phys, ref, npyr)
+    ref = _ref(oracle_mod, E, qpos, qvel, ctrl)
+    npyr, K = npyr_of(E), E.dims.ncon_max
+    keep = keep_constraint(kind, phys, ref, npyr)
     cf = {k: v.cpu().numpy() for k, v in phys.contact_forces().items()}
     assert cf["force"].shape == (N, K, 3) and cf["torque"].shape == (N, K, 3) and cf["normal_force"].shape == (N, K)
     refF, refT = ({p: np.zeros((N, K, 2, 3)) for p in ("f32", "f64")} for _ in range(2))
@@ -211,8 +96,8 @@ def test_contact_wrench_matches_the_oracle_rows(oracle_mod, kind):
     print(kind, "contacts on free-jointed trees:", seen)
     assert seen > (0 if kind == "go2rough" else N // 4), f"{kind}: only {seen} contacts on free-jointed trees"
     fails = []
-    _rule(kind, "contact force", _rel(hipF, refF["f64"])[keep], _rel(refF["f32"], refF["f64"])[keep], fails)
-    _rule(kind, "contact torque on the root", _rel(hipT, refT["f64"])[keep], _rel(refT["f32"], refT["f64"])[keep], fails)
+    rule(kind, "contact force", rel(hipF, refF["f64"])[keep], rel(refF["f32"], refF["f64"])[keep], fails)
+    rule(kind, "contact torque on the root", rel(hipT, refT["f64"])[keep], rel(refT["f32"], refT["f64"])[keep], fails)
     # the normal force: non-negative, the sum of the edges; empty slots zero
     ncon = cf["ncon"]
     hc = phys.efc_counts.cpu().numpy().astype(int)
@@ -233,11 +118,6 @@ def test_contact_wrench_matches_the_oracle_rows(oracle_mod, kind):
     assert not fails, fails
 
 
-def closure_residual(F_sum, qfc_lin):
-    """per env: |sum of the contact forces on the tree - qfrc_constraint[d:d+3]| / max(1, |qfrc_constraint[d:d+3]|_inf)"""
-    return _rel(F_sum, qfc_lin)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", FAMILIES)
 def test_contact_forces_close_on_the_free_joint(oracle_mod, kind):
@@ -255,7 +135,7 @@ def test_contact_forces_close_on_the_free_joint(oracle_mod, kind):
     itself, f32 and f64, leaves 361 of 994 (flat) and 673 of 1252 (footstand) listed contacts without force there.  On the
     standing pose the f64 and f32 oracles load all 4 x 256 contacts, CPU, set_state's pass and then this one.)"""
     import torch
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind)
     A = envdef.sys.arrays
     free = free_trees(A)
     stand_qpos, stand_ctrl = phys.qpos.clone(), phys.ctrl.clone()   # the reset state, before the random states overwrite it
@@ -264,8 +144,8 @@ def test_contact_forces_close_on_the_free_joint(oracle_mod, kind):
     torch.cuda.synchronize()
     cf = {k: v.cpu().numpy() for k, v in phys.contact_forces().items()}
     qfc = phys.qfrc_constraint.cpu().numpy()
-    ref32 = _ref(oracle_mod, kind, E, qpos, qvel, ctrl)["f32"]
-    npyr, K = _npyr(E), E.dims.ncon_max
+    ref32 = _ref(oracle_mod, E, qpos, qvel, ctrl)["f32"]
+    npyr, K = npyr_of(E), E.dims.ncon_max
     geom_root = A["body_rootid"][A["geom_bodyid"]]
     fails, total = [], 0
     for rb, d in sorted(free.items()):
@@ -282,7 +162,7 @@ def test_contact_forces_close_on_the_free_joint(oracle_mod, kind):
             F, _, on, root = ref_wrench(ref32[e], A, npyr, K)
             per = (F[:, 1] * (on[:, 1] & (root[:, 1] == rb))[:, None] + F[:, 0] * (on[:, 0] & (root[:, 0] == rb))[:, None]).astype(np.float32)
             spread[e] = closure_residual(per.sum(0, dtype=np.float32)[None], ref32[e]["qfrc_constraint"][None, d:d + 3].astype(np.float32))[0]
-        _rule(kind, f"closure on dofs {d}..{d + 2}", err, spread, fails)
+        rule(kind, f"closure on dofs {d}..{d + 2}", err, spread, fails)
     print(kind, "contacts on free-jointed trees:", total)
     assert total > (0 if kind == "go2rough" else N // 4), f"{kind}: only {total} contacts on free-jointed trees"
     assert not fails, fails
@@ -313,7 +193,7 @@ def test_qacc_follows_from_the_dynamics_terms_and_qfrc_constraint(oracle_mod, ki
     identity with forward() and the oracle parity of qacc and qfrc_constraint are what hold the Go2 kernels."""
     import torch
     from rsr_mjx_amd.model import pack_blob, unpack_blob
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind, zero_floss=True)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind, zero_floss=True)
     nv = E.dims.nv
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.qacc_warmstart.zero_()
@@ -325,18 +205,13 @@ def test_qacc_follows_from_the_dynamics_terms_and_qfrc_constraint(oracle_mod, ki
     rhs = g(phys.qfrc_passive) - g(phys.qfrc_bias) + g(phys.qfrc_actuator) + g(phys.qfrc_constraint)
     fields = dict(unpack_blob(E.blob))
     fields["dof_frictionloss"] = np.zeros_like(fields["dof_frictionloss"])
-    ref32 = _ref(oracle_mod, kind, E, qpos, qvel, ctrl, blob=pack_blob(fields), tag="nofloss")["f32"]
+    ref32 = _ref(oracle_mod, E, qpos, qvel, ctrl, blob=pack_blob(fields))["f32"]
     o_lhs = np.stack([r["M"] @ r["qacc"] for r in ref32])
     o_rhs = np.stack([r["qfrc_smooth"] + r["qfrc_constraint"] for r in ref32])
     fails = []
-    _rule(kind, "M qacc = qfrc_smooth + qfrc_constraint", _rel(lhs, rhs), _rel(o_lhs, o_rhs), fails)
+    rule(kind, "M qacc = qfrc_smooth + qfrc_constraint", rel(lhs, rhs), rel(o_lhs, o_rhs), fails)
     assert np.abs(g(phys.qfrc_constraint)).max() > 1.0
     assert not fails, fails
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int32)
 
 
 @pytest.mark.gpu
@@ -347,7 +222,7 @@ def test_it_is_the_forward_pass(kind, applied):
     views are phys.contacts(), bit for bit; plain, and with applied forces on (non-zero qfrc and xfrc), where qfrc_constraint also
     differs from the plain run."""
     import torch
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.step(None, 2)                                             # a warm start that is neither zero nor this pass's qacc
     phys.constraint_forces()
@@ -361,17 +236,18 @@ def test_it_is_the_forward_pass(kind, applied):
         phys.set_applied(x, q)
         phys.constraint_forces()
         torch.cuda.synchronize()
-        assert not torch.equal(_bits(phys.qfrc_constraint), _bits(plain))
+        assert not torch.equal(bits(phys.qfrc_constraint), bits(plain))
         assert float((phys.qfrc_constraint - plain).abs().max()) > 1e-3
     cq = phys.constraint_qacc.clone()
-    cv = {k: v.clone() for k, v in phys._con_views().items()}
+    cv = handle_snapshot(phys, ("constraint",))
     phys.forward()
     torch.cuda.synchronize()
-    bad = (_bits(cq) != _bits(phys.qacc)).any(1)
+    bad = (bits(cq) != bits(phys.qacc)).any(1)
     assert not bool(bad.any()), f"{kind}: qacc differs in {int(bad.sum())} envs, max |d| {float((cq - phys.qacc).abs().max()):.3e}"
-    assert torch.equal(_bits(cv["contact"]), _bits(phys._side["contact"]))
-    assert torch.equal(_bits(cv["ncon"]), _bits(phys._side["ncon"]))
-    assert float(cv["ncon"].sum()) > 0
+    side = handle_views(phys, "side")
+    assert torch.equal(bits(cv["con_contact"]), bits(side["contact"]))
+    assert torch.equal(bits(cv["con_ncon"]), bits(side["ncon"]))
+    assert float(cv["con_ncon"].sum()) > 0
 
 
 @pytest.mark.gpu
@@ -379,8 +255,8 @@ def test_it_is_the_forward_pass(kind, applied):
 def test_constraint_forces_has_no_side_effects(kind):
     import torch
     from rsr_mjx_amd.physics import Physics
-    envdef, E, _, scale = _make(kind, N, kind != "tshape")
-    _, F, _, _ = _make(kind, N, kind != "tshape")
+    envdef, E, _, scale = make(kind, N, kind != "tshape")
+    _, F, _, _ = make(kind, N, kind != "tshape")
     E.reset(prng.split(prng.PRNGKey(4), N))
     F.reset(prng.split(prng.PRNGKey(4), N))
     rng = np.random.default_rng(0)
@@ -392,18 +268,13 @@ def test_constraint_forces_has_no_side_effects(kind):
     phys.step(None, 1)
     phys.dynamics()
     torch.cuda.synchronize()
-    dyn = ("qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator")
-    rec0, side0 = E.record.clone(), {k: v.clone() for k, v in phys._side.items()}
-    dyn0 = {f: getattr(phys, f).clone() for f in dyn}
+    before = handle_snapshot(phys, all_but("constraint"))
+    rec0 = before["record"]
     phys.constraint_forces()
-    torch.cuda.synchronize()
-    # the record (the warm start included), the side buffer, sensordata and the dynamics buffer are bitwise as before
-    assert torch.equal(_bits(E.record), _bits(rec0))
-    for k in side0:
-        assert torch.equal(_bits(phys._side[k]), _bits(side0[k])), k
-    for f in dyn:
-        assert torch.equal(_bits(getattr(phys, f)), _bits(dyn0[f])), f
-    views = phys._con_views()
+    # the record (the warm start included), the side buffer, sensordata, the dynamics buffer and every other buffer of the handle
+    # are bitwise as before
+    assert_unchanged(before, handle_snapshot(phys, all_but("constraint")))
+    views = handle_views(phys, "constraint")
     first = {k: v.clone() for k, v in views.items()}
     assert all(float(first[k].abs().max()) > 0 for k in ("qfrc_constraint", "qacc", "efc_counts", "efc_force"))
     # env_ids: the other envs' rows keep a sentinel, the listed rows get the full call's values
@@ -415,7 +286,7 @@ def test_constraint_forces_has_no_side_effects(kind):
     others = np.setdiff1d(np.arange(N), ids)
     for k, v in views.items():
         assert bool((v[others] == 7.25).all()), k
-        assert torch.equal(_bits(v[ids]), _bits(first[k][ids])), k
+        assert torch.equal(bits(v[ids]), bits(first[k][ids])), k
     with pytest.raises(ValueError):
         phys.constraint_forces(env_ids=[N])
     with pytest.raises(ValueError):
@@ -427,7 +298,7 @@ def test_constraint_forces_has_no_side_effects(kind):
     ptr, shape, stride = C.c_void_p(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
     for fid in (-1, len(_lib.CONSTRAINT_FIELDS)):
         assert _lib.lib().rsr_physics_constraint_view(phys._h, fid, C.byref(ptr), shape, stride) == -1
-    assert torch.equal(_bits(E.record), _bits(rec0))
+    assert torch.equal(bits(E.record), bits(rec0))
     # an env.step after constraint_forces() equals the same step without it (F: the same history, no physics handle)
     F.record.copy_(rec0)
     a1 = act()
@@ -435,7 +306,7 @@ def test_constraint_forces_has_no_side_effects(kind):
     F.step(None, a1)
     torch.cuda.synchronize()
     for k in PIPE + ("obs", "reward", "done"):
-        assert torch.equal(_bits(E.view(k)), _bits(F.view(k))), k
+        assert torch.equal(bits(E.view(k)), bits(F.view(k))), k
 
 
 @pytest.mark.gpu
@@ -449,7 +320,7 @@ def test_go2_constraint_forces_read_the_warm_start_and_leave_it(kind):
     differ.  On the CPU oracle, these states after two steps: 255 of 256 (flat), 251 of 256 (footstand) and 58 of the 59 envs
     with a contact (rough terrain, where the robots spawn clear of the ground; none of the other 197 differs)."""
     import torch
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.step(None, 2)
     torch.cuda.synchronize()
@@ -457,17 +328,15 @@ def test_go2_constraint_forces_read_the_warm_start_and_leave_it(kind):
     assert float(warm0.abs().max()) > 0
     phys.constraint_forces()
     torch.cuda.synchronize()
-    first = {k: v.clone() for k, v in phys._con_views().items()}
-    assert torch.equal(_bits(phys.qacc_warmstart), _bits(warm0))
+    first = handle_snapshot(phys, ("constraint",))
+    assert torch.equal(bits(phys.qacc_warmstart), bits(warm0))
     phys.constraint_forces()
-    torch.cuda.synchronize()
-    for k, v in phys._con_views().items():
-        assert torch.equal(_bits(v), _bits(first[k])), k
+    assert_unchanged(first, handle_snapshot(phys, ("constraint",)))
     phys.qacc_warmstart.zero_()
     phys.constraint_forces()
     torch.cuda.synchronize()
-    differ = (_bits(phys.constraint_qacc) != _bits(first["qacc"])).any(1)
-    touching = first["ncon"].reshape(N) > 0
+    differ = (bits(phys.constraint_qacc) != bits(first["con_qacc"])).any(1)
+    touching = first["con_ncon"].reshape(N) > 0
     print(kind, "constraint_qacc depends on the warm start in %d of %d envs, %d of the %d with a contact"
           % (int(differ.sum()), N, int((differ & touching).sum()), int(touching.sum())))
     assert int(touching.sum()) > 0

@@ -10,7 +10,7 @@ with dist in (-r, 0.5 r), centres on grid lines and vertices, exactly on the sur
 the border and one nextafter outside it, and the 81 waves whose four pairs take the states (no contact, below, search) in every
 arrangement.
 
-Rule (set before measuring, _rule of test_dynamics_gpu): p99 <= 1e-5 or <= 3 x the p99 of the spread, every input within
+Rule (set before measuring, rule of tests/physics_support.py): p99 <= 1e-5 or <= 3 x the p99 of the spread, every input within
 max(1e-4, 20 x the largest spread); the spread is the distance of the F32 ORACLE's hfield_sphere from the same reference on the
 same inputs.  dist is checked on every touching input (reference dist < 0) -- it is a minimum distance, 1-Lipschitz in the
 centre, so no facet tie can excuse it -- except below the surface within 1e-4 (u, v units) of a cell edge or the diagonal, where
@@ -48,9 +48,9 @@ import numpy as np
 import pytest
 
 import device_harness as DH
+from physics_support import rule
 from test_device_hfield import (FIELDS, P_BORDER, P_GRID, P_MIXED, P_OUTSIDE, P_RANDOM, P_SURFACE, POSES, case, checked_sets,
                                 closest_tri, oracle_hfield)
-from test_dynamics_gpu import _rule
 
 pytestmark = pytest.mark.gpu
 
@@ -107,7 +107,7 @@ def test_flag_and_dist_match_fp64(oracle_mod, name):
         assert (touch & ~dist_ok).sum() <= 0.02 * touch.sum()
         sel = dist_ok & (k.flag == 1) & (f32 == 1)
         assert sel.sum() >= 0.95 * touch.sum()
-        _rule(f"{name}/{which}", "dist", np.abs(k.dist - ref["dist"])[sel], np.abs(d32 - ref["dist"])[sel], fails)
+        rule(f"{name}/{which}", "dist", np.abs(k.dist - ref["dist"])[sel], np.abs(d32 - ref["dist"])[sel], fails)
         cap = max(1e-4, 20.0 * float(np.abs(d32 - ref["dist"])[sel].max()))
         above = (k.flag == 1) & ref["flag"] & ~ref["below"] & (k.state == 2)
         assert (k.dist[above] >= ref["dist"][above] - cap).all(), (name, which)
@@ -127,8 +127,8 @@ def test_pos_and_normal_match_fp64(oracle_mod, name):
         print(name, which, "random placements left out of pos / nrm: %d of %d" % ((rnd & touch & ~geom_ok).sum(), rnd.sum()))
         assert (rnd & touch & ~geom_ok).sum() <= 0.05 * rnd.sum()
         sel = geom_ok & (k.flag == 1) & (f32 == 1)
-        _rule(f"{name}/{which}", "pos", _vec_err(k.pos, ref["pos"])[sel], _vec_err(p32, ref["pos"])[sel], fails)
-        _rule(f"{name}/{which}", "nrm", _vec_err(k.nrm, ref["nrm"])[sel], _vec_err(n32, ref["nrm"])[sel], fails)
+        rule(f"{name}/{which}", "pos", _vec_err(k.pos, ref["pos"])[sel], _vec_err(p32, ref["pos"])[sel], fails)
+        rule(f"{name}/{which}", "nrm", _vec_err(k.nrm, ref["nrm"])[sel], _vec_err(n32, ref["nrm"])[sel], fails)
         hit = k.flag == 1
         assert np.abs(np.linalg.norm(k.nrm.astype(np.float64), axis=1) - 1.0)[hit].max() <= 1e-6, (name, which)
         # the job in the field frame: n is unit, and the reported pos / nrm are hpos + R (q + n dist / 2), R n
@@ -158,7 +158,7 @@ def test_ties_report_the_shared_point(oracle_mod, name):
         assert sel.sum() >= 24, (name, which, sel.sum())
         R = c["hmat"].astype(np.float64)
         q32 = np.einsum("mkc,mk->mc", R, p32 - n32 * (0.5 * d32)[:, None] - c["hpos"])
-        _rule(f"{name}/{which}", "tied q", _vec_err(k.q, ref["q"])[sel], _vec_err(q32, ref["q"])[sel], fails)
+        rule(f"{name}/{which}", "tied q", _vec_err(k.q, ref["q"])[sel], _vec_err(q32, ref["q"])[sel], fails)
         if which == "identity" and name != "shipped":
             on = (c["place"] == P_SURFACE) & (k.state == 2)
             assert on.sum() >= 12
@@ -229,9 +229,9 @@ def test_rigid_motion_moves_the_answer(oracle_mod, name):
     geo = both & checked_sets(c0)[2] & checked_sets(c1)[2]
     assert sel.sum() > 400 and geo.sum() > 300
     fails = []
-    _rule(name, "moved dist", np.abs(k1.dist - k0.dist.astype(np.float64))[sel], np.abs(o1[1] - o0[1])[sel], fails)
-    _rule(name, "moved pos", _vec_err(k1.pos, move(k0.pos.astype(np.float64)))[geo], _vec_err(o1[2], move(o0[2]))[geo], fails)
-    _rule(name, "moved nrm", _vec_err(k1.nrm, rot(k0.nrm.astype(np.float64)))[geo], _vec_err(o1[3], rot(o0[3]))[geo], fails)
+    rule(name, "moved dist", np.abs(k1.dist - k0.dist.astype(np.float64))[sel], np.abs(o1[1] - o0[1])[sel], fails)
+    rule(name, "moved pos", _vec_err(k1.pos, move(k0.pos.astype(np.float64)))[geo], _vec_err(o1[2], move(o0[2]))[geo], fails)
+    rule(name, "moved nrm", _vec_err(k1.nrm, rot(k0.nrm.astype(np.float64)))[geo], _vec_err(o1[3], rot(o0[3]))[geo], fails)
     assert not fails, fails
 
 
@@ -317,11 +317,11 @@ def test_closest_on_triangle_matches_fp64():
     q32 = _tri32(p, a, b, c)
     d_32 = np.linalg.norm(p.astype(np.float64) - q32, axis=1)
     fails = []
-    _rule("triangle", "distance", np.abs(d_k - d_ref)[keep], np.abs(d_32 - d_ref)[keep], fails)
-    _rule("triangle", "point", _vec_err(q, ref)[keep], _vec_err(q32.astype(np.float64), ref)[keep], fails)
+    rule("triangle", "distance", np.abs(d_k - d_ref)[keep], np.abs(d_32 - d_ref)[keep], fails)
+    rule("triangle", "point", _vec_err(q, ref)[keep], _vec_err(q32.astype(np.float64), ref)[keep], fails)
     for g in range(10):                                     # (7, 8, 9: p on a vertex, on an edge, in the plane)
         s = (region == g) & keep
-        _rule("triangle", f"region {g} distance", np.abs(d_k - d_ref)[s], np.abs(d_32 - d_ref)[s], fails)
+        rule("triangle", f"region {g} distance", np.abs(d_k - d_ref)[s], np.abs(d_32 - d_ref)[s], fails)
     # the regions were hit: the fp64 closest point is the vertex / on the edge / strictly inside
     V = [a.astype(np.float64), b.astype(np.float64), c.astype(np.float64)]
     for g in range(3):

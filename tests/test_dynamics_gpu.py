@@ -2,15 +2,13 @@
 qfrc_actuator against the CPU oracle, qM under domain randomisation, the site Jacobians against fp64 kinematics, consistency with
 the site velocity sensors and with qacc of a forward pass, no side effects, and gravity compensation end to end.
 
-Errors are relative as in tests/test_physics_gpu.py: |hip - ref| / max(1, |ref|_inf of that env's field).  The bound on a dynamic
-field is that file's rule: p99 <= 1e-5, or <= 3 x the fp32 oracle's own p99 distance from the fp64 oracle where that is larger,
-and every env within max(1e-4, 20 x the largest f32-to-f64 distance).  None of the fields here depends on contacts, so no env is
-excluded."""
+Errors, the rule and its spread: tests/physics_support.py.  None of the fields here depends on contacts, so no env is excluded."""
 import numpy as np
 import pytest
 
+from physics_support import (FAMILIES, PIPE, all_but, assert_unchanged, bits, free_states, handle_snapshot, make, oracle_pass, random_states,
+                             rel, rule, stacked)
 from rsr_mjx_amd import prng
-from test_physics_gpu import FAMILIES, PIPE, _make, _random_states, _rel
 
 N = 256
 JAC_SITES = {"cube": ["endpoint"], "tshape": ["endpoint", "T_tail", "T_target_tail"],
@@ -20,60 +18,10 @@ DYN = ("qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator")
 ORACLE_NAME = dict(qM="M", qfrc_bias="qfrc_bias", qfrc_passive="qfrc_passive", qfrc_actuator="qfrc_actuator")
 
 
-def _rule(kind, what, err, spread, fails):
-    """The project's bound on a dynamic field (see the module docstring); prints p99 / max, appends to `fails`."""
-    p99, mx = float(np.quantile(err, 0.99)), float(err.max())
-    sp99, smx = float(np.quantile(spread, 0.99)), float(spread.max())
-    print(kind, what, "p99 %.2e max %.2e f32-f64 p99 %.2e max %.2e" % (p99, mx, sp99, smx))
-    if not (p99 <= 1e-5 or p99 <= 3.0 * sp99):
-        fails.append(f"{kind} {what}: p99 {p99:.2e}")
-    cap = max(1e-4, 20.0 * smx)
-    if not (err <= cap).all():
-        fails.append(f"{kind} {what}: {(err > cap).sum()} envs beyond the cap {cap:.2e}, max {mx:.2e}")
-
-
-def _free_states(envdef, kind, n, seed, zero_vel=False):
-    """_random_states moved clear of every contact and joint limit: free bodies (the Airbot's cube / target / T block) parked
-    apart in the air or the Go2 trunk lifted to 1 m, limited joints kept 0.02 inside their range (the middle of a range narrower
-    than 0.1: the Airbot's link4 and fingers).  The Airbot's shoulder (its second joint) is raised by 0.3 rad: the reset pose
-    holds the fingers a centimetre above the table, and the perturbation of _random_states puts them into it in 12 of 256
-    T-shape envs (CPU oracle)."""
-    qpos, qvel, ctrl = _random_states(envdef, kind, n, seed)
-    A = envdef.sys.arrays
-    if kind in ("cube", "tshape"):
-        qpos[:, int(A["jnt_qposadr"][1])] += 0.3
-    for j in range(len(A["jnt_type"])):
-        jt, qa = int(A["jnt_type"][j]), int(A["jnt_qposadr"][j])
-        if jt == 0:
-            qpos[:, qa:qa + 3] = [0.0, 0.0, 1.0] if kind not in ("cube", "tshape") else [3.0 + j, 3.0, 2.0]
-        elif A["jnt_limited"][j]:
-            lo, hi = float(A["jnt_range"][j, 0]), float(A["jnt_range"][j, 1])
-            qpos[:, qa] = 0.5 * (lo + hi) if hi - lo < 0.1 else np.clip(qpos[:, qa], lo + 0.02, hi - 0.02)
-    if zero_vel:
-        qvel[:] = 0.0
-    return qpos, qvel, ctrl
-
-
-_REF = {}
-
-
-def _oracle_ref(oracle_mod, E, key, qpos, qvel, ctrl, names, blob=None):
-    """{precision: {name: [n, w]}} of Oracle.forward(qpos, qvel, ctrl, zeros) per env, plus counts; cached per `key`."""
-    if key in _REF:
-        return _REF[key]
-    n = len(qpos)
-    ref = {}
-    for p in ("f32", "f64"):
-        o = oracle_mod.Oracle(blob or E.blob, p)
-        o.set_ncon_cap(E.dims.ncon_max)
-        rows = {k: [] for k in names + ("counts",)}
-        for e in range(n):
-            o.forward(qpos[e].astype(np.float64), qvel[e].astype(np.float64), ctrl[e], np.zeros(E.dims.nv), step=False)
-            for k in rows:
-                rows[k].append(o.get(k))
-        ref[p] = {k: np.asarray(v) for k, v in rows.items()}
-    _REF[key] = ref
-    return ref
+def _oracle_ref(oracle_mod, E, qpos, qvel, ctrl, names, blob=None):
+    """{precision: {name: [n, w]}} of the oracle's pass from a zero warm start"""
+    ref = oracle_pass(oracle_mod, blob or E.blob, E.dims, qpos, qvel, ctrl)
+    return {p: stacked(rows, names) for p, rows in ref.items()}
 
 
 def _dyn_fields(phys):
@@ -87,9 +35,9 @@ def test_dynamics_terms_match_the_oracle(oracle_mod, kind):
     non-zero qvel; the bound is the module's rule with the f32 oracle's own distance, no env excluded."""
     import torch
     from rsr_mjx_amd.physics import Physics
-    envdef, E, _, _ = _make(kind, N, False)
+    envdef, E, _, _ = make(kind, N, False)
     E.reset(prng.split(prng.PRNGKey(1), N))
-    qpos, qvel, ctrl = _random_states(envdef, kind, N, 21)
+    qpos, qvel, ctrl = random_states(envdef, kind, N, 21)
     assert np.abs(qvel).max() > 0.1
     phys = Physics(E)
     assert float(phys.qM.abs().max()) == 0.0 and phys.jacp.shape == (N, 0, 3, E.dims.nv)      # zeros until the first call
@@ -99,11 +47,11 @@ def test_dynamics_terms_match_the_oracle(oracle_mod, kind):
     hip = _dyn_fields(phys)
     assert phys.qM.shape == (N, E.dims.nv, E.dims.nv)
     np.testing.assert_array_equal(phys.qM.cpu().numpy(), phys.qM.cpu().numpy().transpose(0, 2, 1))      # symmetric, bitwise
-    ref = _oracle_ref(oracle_mod, E, (kind, 21), qpos, qvel, ctrl, tuple(ORACLE_NAME.values()))
+    ref = _oracle_ref(oracle_mod, E, qpos, qvel, ctrl, tuple(ORACLE_NAME.values()))
     fails = []
     for f in DYN:
         r64, r32 = ref["f64"][ORACLE_NAME[f]], ref["f32"][ORACLE_NAME[f]]
-        _rule(kind, f, _rel(hip[f], r64), _rel(r32, r64), fails)
+        rule(kind, f, rel(hip[f], r64), rel(r32, r64), fails)
     assert not fails, fails
 
 
@@ -118,9 +66,9 @@ def test_qM_honours_the_per_env_leaves(oracle_mod, kind):
     from rsr_mjx_amd import mjcf
     from rsr_mjx_amd.model import pack_blob, unpack_blob
     from rsr_mjx_amd.physics import Physics
-    envdef, E, dr, _ = _make(kind, N, True)
+    envdef, E, dr, _ = make(kind, N, True)
     E.reset(prng.split(prng.PRNGKey(1), N))
-    qpos, qvel, ctrl = _random_states(envdef, kind, N, 22)
+    qpos, qvel, ctrl = random_states(envdef, kind, N, 22)
     phys = Physics(E)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.dynamics()
@@ -146,9 +94,9 @@ def test_qM_honours_the_per_env_leaves(oracle_mod, kind):
         o_nom.forward(qpos[e].astype(np.float64), qvel[e].astype(np.float64), ctrl[e], np.zeros(nv))
         nominal[e] = o_nom.get("M")
     fails = []
-    _rule(kind, "qM (DR)", _rel(hip, r64), _rel(r32, r64), fails)
+    rule(kind, "qM (DR)", rel(hip, r64), rel(r32, r64), fails)
     assert not fails, fails
-    assert np.quantile(_rel(nominal, r64), 0.5) > 1e-3, "the randomisation does not move qM: the test shows nothing"
+    assert np.quantile(rel(nominal, r64), 0.5) > 1e-3, "the randomisation does not move qM: the test shows nothing"
 
 
 @pytest.mark.gpu
@@ -160,9 +108,9 @@ def test_site_jacobians_match_fp64_kinematics(kind):
     import torch
     from rsr_mjx_amd import mjcf
     from rsr_mjx_amd.physics import Physics
-    envdef, E, _, _ = _make(kind, N, False)
+    envdef, E, _, _ = make(kind, N, False)
     E.reset(prng.split(prng.PRNGKey(1), N))
-    qpos, qvel, ctrl = _random_states(envdef, kind, N, 21)
+    qpos, qvel, ctrl = random_states(envdef, kind, N, 21)
     sys_, A = envdef.sys, envdef.sys.arrays
     names = JAC_SITES[kind]
     sids = [sys_.id("site", s) for s in names]
@@ -221,9 +169,9 @@ def test_jacobians_times_qvel_are_the_site_velocity_sensors(kind):
     on the same state (product in fp64 on the host): within 1e-5 relative."""
     import torch
     from rsr_mjx_amd.physics import Physics
-    envdef, E, _, _ = _make(kind, N, False)
+    envdef, E, _, _ = make(kind, N, False)
     E.reset(prng.split(prng.PRNGKey(1), N))
-    qpos, qvel, ctrl = _random_states(envdef, kind, N, 21)
+    qpos, qvel, ctrl = random_states(envdef, kind, N, 21)
     names = JAC_SITES[kind]
     spec = [(f"lin_{s}", "framelinvel", s) for s in names] + [(f"ang_{s}", "frameangvel", s) for s in names]
     phys = Physics(E, sensors=spec)
@@ -237,7 +185,7 @@ def test_jacobians_times_qvel_are_the_site_velocity_sensors(kind):
     for k, s in enumerate(names):
         for name, J in ((f"lin_{s}", jp), (f"ang_{s}", jr)):
             sens = phys.sensor(name).cpu().numpy()
-            err = _rel(np.einsum("nij,nj->ni", J[:, k], v), sens)
+            err = rel(np.einsum("nij,nj->ni", J[:, k], v), sens)
             print(kind, name, "p99 %.2e max %.2e" % (np.quantile(err, 0.99), err.max()))
             worst = max(worst, float(err.max()))
     assert worst <= 1e-5, worst
@@ -258,19 +206,19 @@ def test_qacc_of_a_forward_pass_follows_from_the_dynamics_terms(oracle_mod, kind
     import torch
     from rsr_mjx_amd.model import pack_blob, unpack_blob
     from rsr_mjx_amd.physics import Physics
-    envdef, E, _, _ = _make(kind, N, False)
+    envdef, E, _, _ = make(kind, N, False)
     nv = E.dims.nv
     E.set_randomization({"dof_frictionloss": np.zeros((N, nv), np.float32)})
     E.reset(prng.split(prng.PRNGKey(1), N))
-    qpos, qvel, ctrl = _free_states(envdef, kind, N, 23)
+    qpos, qvel, ctrl = free_states(envdef, kind, N, 23)
     phys = Physics(E)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.dynamics()
     torch.cuda.synchronize()
     fields = dict(unpack_blob(E.blob))
     fields["dof_frictionloss"] = np.zeros_like(fields["dof_frictionloss"])
-    ref = _oracle_ref(oracle_mod, E, (kind, "free", 23), qpos, qvel, ctrl, ("qacc", "qfrc_constraint"), blob=pack_blob(fields))
-    counts = ref["f64"]["counts"]                              # nefc, ne, nf, ncon, ...
+    ref = _oracle_ref(oracle_mod, E, qpos, qvel, ctrl, ("qacc", "qfrc_constraint", "nefc", "ne", "nf", "ncon"), blob=pack_blob(fields))
+    counts = np.concatenate([ref["f64"][k] for k in ("nefc", "ne", "nf", "ncon")], 1)
     assert (counts[:, 3] == 0).all(), f"{kind}: contacts in {(counts[:, 3] != 0).sum()} envs"
     assert (counts[:, 0] == counts[:, 1] + counts[:, 2]).all(), f"{kind}: active limits in {(counts[:, 0] != counts[:, 1] + counts[:, 2]).sum()} envs"
     assert (phys.contacts()["ncon"] == 0).all()
@@ -283,7 +231,7 @@ def test_qacc_of_a_forward_pass_follows_from_the_dynamics_terms(oracle_mod, kind
         assert (counts[:, 1] == 0).all() and np.abs(ref["f64"]["qfrc_constraint"]).max() == 0.0
     a = np.stack([np.linalg.solve(d["qM"][e].reshape(nv, nv), rhs[e]) for e in range(N)])
     fails = []
-    _rule(kind, "qacc from qM and the forces", _rel(a, phys.qacc.cpu().numpy()), _rel(ref["f32"]["qacc"], ref["f64"]["qacc"]), fails)
+    rule(kind, "qacc from qM and the forces", rel(a, phys.qacc.cpu().numpy()), rel(ref["f32"]["qacc"], ref["f64"]["qacc"]), fails)
     assert not fails, fails
 
 
@@ -292,8 +240,8 @@ def test_qacc_of_a_forward_pass_follows_from_the_dynamics_terms(oracle_mod, kind
 def test_dynamics_has_no_side_effects(kind):
     import torch
     from rsr_mjx_amd.physics import Physics
-    envdef, E, _, scale = _make(kind, N, kind != "tshape")
-    _, F, _, _ = _make(kind, N, kind != "tshape")
+    envdef, E, _, scale = make(kind, N, kind != "tshape")
+    _, F, _, _ = make(kind, N, kind != "tshape")
     E.reset(prng.split(prng.PRNGKey(4), N))
     F.reset(prng.split(prng.PRNGKey(4), N))
     rng = np.random.default_rng(0)
@@ -306,14 +254,11 @@ def test_dynamics_has_no_side_effects(kind):
     phys.set_jac_sites(names)
     phys.step(None, 1)
     torch.cuda.synchronize()
-    bits = lambda t: t.contiguous().view(torch.int32)          # (bitwise: Go2 records hold PRNG key words, some of them NaN patterns)
-    rec0, side0 = E.record.clone(), {k: v.clone() for k, v in phys._side.items()}
+    before = handle_snapshot(phys, all_but("dynamics"))
+    rec0 = before["record"]
     phys.dynamics()
-    torch.cuda.synchronize()
-    # the record, the side buffer and sensordata are bitwise as before
-    assert torch.equal(bits(E.record), bits(rec0))
-    for k in side0:
-        assert torch.equal(bits(phys._side[k]), bits(side0[k])), k
+    # the record, the side buffer, sensordata and every other buffer of the handle are bitwise as before
+    assert_unchanged(before, handle_snapshot(phys, all_but("dynamics")))
     outs = ("qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "jacp", "jacr", "jac_site_xpos")
     first = {f: getattr(phys, f).clone() for f in outs}
     assert all(float(first[f].abs().max()) > 0 for f in outs)
@@ -365,9 +310,9 @@ def test_gravity_compensation_holds_the_airbot_arm(oracle_mod):
     import torch
     from rsr_mjx_amd.physics import Physics
     kind, arm = "cube", slice(0, 6)
-    envdef, E, _, _ = _make(kind, N, False)
+    envdef, E, _, _ = make(kind, N, False)
     E.reset(prng.split(prng.PRNGKey(1), N))
-    qpos, qvel, ctrl = _free_states(envdef, kind, N, 24, zero_vel=True)
+    qpos, qvel, ctrl = free_states(envdef, kind, N, 24, zero_vel=True)
     phys = Physics(E)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     torch.cuda.synchronize()
@@ -377,7 +322,7 @@ def test_gravity_compensation_holds_the_airbot_arm(oracle_mod):
     phys.forward()
     torch.cuda.synchronize()
     held = np.abs(phys.qacc.cpu().numpy()[:, arm]).max(1)
-    ref = _oracle_ref(oracle_mod, E, (kind, "free0", 24), qpos, qvel, ctrl, ("M", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "qfrc_smooth"))
+    ref = _oracle_ref(oracle_mod, E, qpos, qvel, ctrl, ("M", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "qfrc_smooth"))
     r = ref["f32"]
     nv = E.dims.nv
     f32 = np.float32

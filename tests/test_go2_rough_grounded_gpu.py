@@ -7,23 +7,19 @@ On the CPU the f64 oracle lists >= 3 contacts in 256 of the 256 envs (815 contac
 (ne, nf, nl, ncon) in 0 of them; every one of the 815 contacts carries a normal force > 0 in the f64 oracle (the generator sees to
 that; on the device the smallest force along its normal is 2.29 N).
 
-Errors, rule and exclusion are test_constraint_gpu's: |hip - ref| / max(1, |ref|_inf of the env's field), p99 <= 1e-5 or <= 3 x the
-f32 oracle's p99 distance from the f64 oracle, every env within max(1e-4, 20 x the largest such distance); an env whose row counts
-differ between the kernel, the f64 oracle and the f32 oracle is left out, at most 2 % of them."""
+Errors, rule and exclusion: tests/physics_support.py, as in test_constraint_gpu."""
 import os
 
 import numpy as np
 import pytest
 
+from physics_support import closure_residual, keep_constraint, make, npyr, oracle_pass, ref_wrench, rel, rule, wrench_on_root
 from rsr_mjx_amd import prng
-from test_constraint_gpu import N, _keep, _npyr, closure_residual, oracle_rows, ref_wrench, wrench_on_root
-from test_dynamics_gpu import _rule
-from test_physics_gpu import _make, _rel
 
 pytestmark = pytest.mark.gpu
 
 KIND = "go2rough"
-_REF = {}
+N = 256
 
 
 def _states():
@@ -34,15 +30,13 @@ def _states():
 
 def _setup():
     from rsr_mjx_amd.physics import Physics
-    envdef, E, _, _ = _make(KIND, N, False)
+    envdef, E, _, _ = make(KIND, N, False)
     E.reset(prng.split(prng.PRNGKey(1), N))
     return (envdef, E, Physics(E)) + _states()
 
 
 def _ref(oracle_mod, E, qpos, qvel, ctrl):
-    if "rows" not in _REF:
-        _REF["rows"] = oracle_rows(oracle_mod, E.blob, E.dims.nv, E.dims.ncon_max, E.dims.nefc_max, qpos, qvel, ctrl)
-    return _REF["rows"]
+    return oracle_pass(oracle_mod, E.blob, E.dims, qpos, qvel, ctrl)
 
 
 def test_contacts_on_grounded_states(oracle_mod):
@@ -55,10 +49,10 @@ def test_contacts_on_grounded_states(oracle_mod):
     torch.cuda.synchronize()
     c = {k: v.cpu().numpy() for k, v in phys.contacts().items()}
     phys.qacc_warmstart.zero_()
-    phys.constraint_forces()                                   # (for _keep: the row counts; it leaves the contacts of the pass alone)
+    phys.constraint_forces()                                   # (for keep_constraint: the row counts; it leaves the contacts of the pass alone)
     torch.cuda.synchronize()
     ref = _ref(oracle_mod, E, qpos, qvel, ctrl)
-    keep = _keep(KIND, phys, ref, _npyr(E))
+    keep = keep_constraint(KIND, phys, ref, npyr(E))
     K = E.dims.ncon_max
     pad = {p: {f: np.zeros((N, K, w)) for f, w in (("dist", 1), ("pos", 3), ("normal", 3))} for p in ("f32", "f64")}
     for e in np.nonzero(keep)[0]:
@@ -75,7 +69,7 @@ def test_contacts_on_grounded_states(oracle_mod):
     assert total > 3 * N * 0.8
     fails = []
     for f in ("dist", "pos", "normal"):
-        _rule(KIND, "contact " + f, _rel(c[f].reshape(N, -1), pad["f64"][f])[keep], _rel(pad["f32"][f], pad["f64"][f])[keep], fails)
+        rule(KIND, "contact " + f, rel(c[f].reshape(N, -1), pad["f64"][f])[keep], rel(pad["f32"][f], pad["f64"][f])[keep], fails)
     assert not fails, fails
 
 
@@ -92,20 +86,20 @@ def test_forces_on_grounded_states(oracle_mod):
     phys.constraint_forces()
     torch.cuda.synchronize()
     ref = _ref(oracle_mod, E, qpos, qvel, ctrl)
-    npyr, K = _npyr(E), E.dims.ncon_max
-    keep = _keep(KIND, phys, ref, npyr)
+    edges, K = npyr(E), E.dims.ncon_max
+    keep = keep_constraint(KIND, phys, ref, edges)
     fails = []
     for f, t in dict(efc_force=phys.efc_force, qfrc_constraint=phys.qfrc_constraint, qacc=phys.constraint_qacc).items():
         h = t.cpu().numpy().astype(np.float64)
         r64, r32 = (np.stack([r[f] for r in ref[p]]) for p in ("f64", "f32"))
-        _rule(KIND, f, _rel(h, r64)[keep], _rel(r32, r64)[keep], fails)
+        rule(KIND, f, rel(h, r64)[keep], rel(r32, r64)[keep], fails)
     cf = {k: v.cpu().numpy() for k, v in phys.contact_forces().items()}
     refF, refT = ({p: np.zeros((N, K, 2, 3)) for p in ("f32", "f64")} for _ in range(2))
     hipF, hipT = np.zeros((N, K, 2, 3)), np.zeros((N, K, 2, 3))
     seen = 0
     for e in np.nonzero(keep)[0]:
         for p in ("f32", "f64"):
-            refF[p][e], refT[p][e], on, root = ref_wrench(ref[p][e], A, npyr, K)
+            refF[p][e], refT[p][e], on, root = ref_wrench(ref[p][e], A, edges, K)
         for cc, side in zip(*np.nonzero(on)):
             sign = 1.0 if side == 1 else -1.0
             hipF[e, cc, side] = sign * cf["force"][e, cc]
@@ -113,8 +107,8 @@ def test_forces_on_grounded_states(oracle_mod):
             seen += 1
     print(KIND, "grounded: contacts on the trunk's tree:", seen)
     assert seen > N
-    _rule(KIND, "contact force", _rel(hipF, refF["f64"])[keep], _rel(refF["f32"], refF["f64"])[keep], fails)
-    _rule(KIND, "contact torque on the root", _rel(hipT, refT["f64"])[keep], _rel(refT["f32"], refT["f64"])[keep], fails)
+    rule(KIND, "contact force", rel(hipF, refF["f64"])[keep], rel(refF["f32"], refF["f64"])[keep], fails)
+    rule(KIND, "contact torque on the root", rel(hipT, refT["f64"])[keep], rel(refT["f32"], refT["f64"])[keep], fails)
     # closure on dofs 0..2: the field is geom1 of every pair, so the sum of the contact forces is qfrc_constraint[0:3]
     live = np.arange(K)[None, :] < cf["ncon"][:, None]
     assert (A["geom_bodyid"][cf["geom1"][live]] == 0).all()
@@ -122,10 +116,10 @@ def test_forces_on_grounded_states(oracle_mod):
     qfc = phys.qfrc_constraint.cpu().numpy()
     spread = np.zeros(N)
     for e in range(N):
-        F, _, on, _ = ref_wrench(ref["f32"][e], A, npyr, K)
+        F, _, on, _ = ref_wrench(ref["f32"][e], A, edges, K)
         per = (F[:, 1] * on[:, 1][:, None]).astype(np.float32)
         spread[e] = closure_residual(per.sum(0, dtype=np.float32)[None], ref["f32"][e]["qfrc_constraint"][None, 0:3].astype(np.float32))[0]
-    _rule(KIND, "closure on dofs 0..2", closure_residual(Fsum, qfc[:, 0:3]), spread, fails)
+    rule(KIND, "closure on dofs 0..2", closure_residual(Fsum, qfc[:, 0:3]), spread, fails)
     along = np.einsum("nkc,nkc->nk", cf["force"], cf["normal"])
     print(KIND, "grounded: smallest contact force along its normal %.3e" % along[live].min())
     assert (along[live] > 0).all(), f"{(along[live] <= 0).sum()} contacts without a force along their normal"
@@ -163,5 +157,5 @@ def test_step_from_grounded_states(oracle_mod):
     assert flips.mean() <= 0.02
     fails = []
     for f in fields:
-        _rule(KIND, "stepN " + f, _rel(hip[f], ref["f64"][f])[~flips], _rel(ref["f32"][f], ref["f64"][f])[~flips], fails)
+        rule(KIND, "stepN " + f, rel(hip[f], ref["f64"][f])[~flips], rel(ref["f32"][f], ref["f64"][f])[~flips], fails)
     assert not fails, fails

@@ -2,17 +2,15 @@
 qfrc_actuator and qfrc_inverse at given accelerations against the CPU oracle's terms, bit identity with constraint_forces() at its
 own qacc, the discrete-time conversion, no side effects, env subsets and applied forces.
 
-States: _random_states(envdef, kind, 256, 11), the states of test_constraint_gpu, DR off.  Errors are relative as there,
-|hip - ref| / max(1, |ref|_inf of that env's field), and the bound is the project's rule (_rule of test_dynamics_gpu): p99 <= 1e-5
-or <= 3 x the fp32 oracle's own p99 distance from the fp64 oracle, and every env within max(1e-4, 20 x the largest such distance).
+States: random_states(envdef, kind, 256, 11), the states of test_constraint_gpu, DR off.  Errors, the rule and the exclusion of envs
+whose row counts flip: tests/physics_support.py.
 
 The reference: per env Oracle.forward(q, v, ctrl, zeros) in f64 and in f32 gives M, qfrc_bias, qfrc_passive, qfrc_actuator and
 the rows efc_J, efc_aref, efc_D, efc_R, efc_floss with their counts; row_forces() below applies the row law at the given
 acceleration (the law oracle_debug_cost states as a cost), then J^T f and M a + bias - passive - J^T f.  The f64 oracle's terms in
-float64 are the reference, the f32 oracle's terms in float32 the spread.  An env whose (ne, nf, nl, ncon) differ between the kernel
-and the f64 oracle, or between the f32 and f64 oracles, is excluded (a contact or limit mode flip); at most 2 % may be.  On the
-CPU, with the oracle's own reset states for seed 11 and the same perturbation, the f32-vs-f64 part of that excludes 0 of 256 envs
-on all five families (re-checked for this module), so seed 11 stays.
+float64 are the reference, the f32 oracle's terms in float32 the spread.  On the CPU, with the oracle's own reset states for seed 11
+and the same perturbation, the f32-vs-f64 part of the exclusion leaves out 0 of 256 envs on all five families (re-checked for this
+module), so seed 11 stays.
 
 Integrators, from the models: the Airbot cube and T-shape run implicitfast, so their discrete accelerations are converted
 (a = qacc + h M^-1 (damp * qacc)); the three Go2 models run Euler with eulerdamp disabled, so theirs pass through bit for bit."""
@@ -21,32 +19,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from physics_support import (FAMILIES, IMPLICIT, PIPE, all_but, assert_unchanged, bits, handle_snapshot, handle_views, make, oracle_pass,
+                             rel, rule, setup)
+from physics_support import keep as keep_rows, npyr as npyr_of
 from rsr_mjx_amd import prng
-from test_dynamics_gpu import _rule
-from test_physics_gpu import FAMILIES, PIPE, _make, _random_states, _rel
 
 N = 256
 SEED = 11
-IMPLICIT = ("cube", "tshape")
 OUT = ("efc_force", "qfrc_constraint", "qfrc_actuator", "qfrc_inverse")
-
-
-def oracle_terms(oracle_mod, blob, nv, ncon_max, qpos, qvel, ctrl, precisions=("f32", "f64")):
-    """{precision: per-env list of dicts} of Oracle.forward(qpos, qvel, ctrl, zeros): the dynamics terms, the constraint rows and
-    their counts, and the oracle's own qacc"""
-    out = {}
-    for p in precisions:
-        o = oracle_mod.Oracle(blob, p)
-        o.set_ncon_cap(ncon_max)
-        rows = []
-        for e in range(len(qpos)):
-            o.forward(qpos[e].astype(np.float64), qvel[e].astype(np.float64), ctrl[e], np.zeros(nv), step=False)
-            nefc, ne, nf, ncon = (int(x) for x in o.get("counts")[:4])
-            r = {k: o.get(k) for k in ("qfrc_bias", "qfrc_passive", "qfrc_actuator", "efc_aref", "efc_D", "efc_R", "efc_floss", "qacc")}
-            r.update(M=o.get("M").reshape(nv, nv), efc_J=o.get("efc_J").reshape(nefc, nv), nefc=nefc, ne=ne, nf=nf, ncon=ncon)
-            rows.append(r)
-        out[p] = rows
-    return out
 
 
 def row_forces(r, a, dt):
@@ -80,44 +60,16 @@ def to_continuous(r, a, h, damp, dt):
     return (a + dt(h) * np.linalg.solve(r["M"].astype(dt), (damp.astype(dt) * a))).astype(dt)
 
 
-def _setup(kind, sensors=None):
-    from rsr_mjx_amd.physics import Physics
-    envdef, E, _, _ = _make(kind, N, False)
-    E.reset(prng.split(prng.PRNGKey(1), N))
-    qpos, qvel, ctrl = _random_states(envdef, kind, N, SEED)
-    return envdef, E, Physics(E, sensors=sensors), qpos, qvel, ctrl
-
-
-_REF = {}
-
-
-def _ref(oracle_mod, kind, E, qpos, qvel, ctrl):
-    if kind not in _REF:
-        _REF[kind] = oracle_terms(oracle_mod, E.blob, E.dims.nv, E.dims.ncon_max, qpos, qvel, ctrl)
-    return _REF[kind]
-
-
-def _npyr(E):
-    condim = np.unique(E.sys.arrays["pair_condim"])
-    assert len(condim) == 1
-    return 2 * (int(condim[0]) - 1)
-
-
-def _counts(rows, npyr):
-    return np.array([[r["ne"], r["nf"], r["nefc"] - r["ne"] - r["nf"] - npyr * r["ncon"], r["ncon"]] for r in rows])
+def _ref(oracle_mod, E, qpos, qvel, ctrl):
+    return oracle_pass(oracle_mod, E.blob, E.dims, qpos, qvel, ctrl)
 
 
 def _keep(kind, phys, ref, npyr):
-    """envs whose (ne, nf, nl, ncon) agree between the kernel, the f64 oracle and the f32 oracle; asserts the 2 % condition"""
+    """keep on the counts of the last inverse()"""
     hc = phys.inverse_efc_counts.cpu().numpy().astype(int)
     ncon = hc[:, 0] - hc[:, 1] - hc[:, 2] - hc[:, 3]
     assert (ncon % npyr == 0).all() and (ncon >= 0).all()
-    hip = np.stack([hc[:, 1], hc[:, 2], hc[:, 3], ncon // npyr], 1)
-    c64, c32 = _counts(ref["f64"], npyr), _counts(ref["f32"], npyr)
-    flips = (hip != c64).any(1) | (c32 != c64).any(1)
-    print(kind, "excluded envs: %d of %d (kernel vs f64 %d, f32 vs f64 %d)" % (flips.sum(), N, (hip != c64).any(1).sum(), (c32 != c64).any(1).sum()))
-    assert flips.mean() <= 0.02, f"{kind}: row counts differ in {flips.sum()} of {N} envs"
-    return ~flips
+    return keep_rows(kind, np.stack([hc[:, 1], hc[:, 2], hc[:, 3], ncon // npyr], 1), ref, npyr)
 
 
 def _inputs(ref64):
@@ -128,11 +80,6 @@ def _inputs(ref64):
     scale = 0.3 * np.maximum(1.0, np.abs(own).max(1, keepdims=True))
     noisy = (own + scale * rng.normal(size=own.shape)).astype(np.float32)
     return dict(own=own, noisy=noisy, zeros=np.zeros_like(own))
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int32)
 
 
 def _dev(x, phys):
@@ -146,13 +93,13 @@ def test_inverse_matches_the_oracle_at_arbitrary_accelerations(oracle_mod, kind)
     """inverse_efc_force, inverse_qfrc_constraint, inverse_qfrc_actuator and qfrc_inverse after set_state + inverse(a) for the three
     accelerations of _inputs, against the numpy restatement on the f64 oracle's terms, under the module's rule and exclusion."""
     import torch
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind)
     d = E.dims
     assert float(phys.qfrc_inverse.abs().max()) == 0.0 and float(phys.inverse_efc_force.abs().max()) == 0.0      # zeros until the first call
     assert phys.qfrc_inverse.shape == (N, d.nv) and phys.inverse_efc_force.shape == (N, d.nefc_max) and phys.inverse_efc_counts.shape == (N, 4)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
-    ref = _ref(oracle_mod, kind, E, qpos, qvel, ctrl)
-    npyr = _npyr(E)
+    ref = _ref(oracle_mod, E, qpos, qvel, ctrl)
+    npyr = npyr_of(E)
     fails, keep, biggest = [], None, 0.0
     for name, a in _inputs(ref["f64"]).items():
         phys.inverse(_dev(a, phys))
@@ -167,7 +114,7 @@ def test_inverse_matches_the_oracle_at_arbitrary_accelerations(oracle_mod, kind)
         for f in OUT:
             h = views[f].cpu().numpy().astype(np.float64)
             s64, s32 = np.stack([r[f] for r in r64]), np.stack([r[f] for r in r32])
-            _rule(kind, f"{f} at {name}", _rel(h, s64)[keep], _rel(s32, s64)[keep], fails)
+            rule(kind, f"{f} at {name}", rel(h, s64)[keep], rel(s32, s64)[keep], fails)
         nefc = phys.inverse_efc_counts[:, 0].cpu().numpy().astype(int)
         ef = phys.inverse_efc_force.cpu().numpy()
         assert all((ef[e, nefc[e]:] == 0).all() for e in range(N))
@@ -188,7 +135,7 @@ def test_it_is_the_constraint_pass(oracle_mod, kind):
     formed in fp64 on the host from dynamics() and constraint_forces(), under the module's rule; the spread is the f32 oracle's
     residual of the same expression at the same state and acceleration: its terms combined in fp32 against the same terms in fp64."""
     import torch
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.step(None, 2)
     phys.constraint_forces()
@@ -198,22 +145,22 @@ def test_it_is_the_constraint_pass(oracle_mod, kind):
     torch.cuda.synchronize()
     for f, got, want in (("efc_counts", phys.inverse_efc_counts, phys.efc_counts), ("efc_force", phys.inverse_efc_force, phys.efc_force),
                          ("qfrc_constraint", phys.inverse_qfrc_constraint, phys.qfrc_constraint)):
-        bad = (_bits(got) != _bits(want)).any(1)
+        bad = (bits(got) != bits(want)).any(1)
         assert not bool(bad.any()), f"{kind} {f}: {int(bad.sum())} envs differ, max |d| {float((got - want).abs().max()):.3e}"
     assert float(phys.efc_force.abs().max()) > 1.0
-    assert torch.equal(_bits(phys.inverse_qfrc_actuator), _bits(phys.qfrc_actuator))
+    assert torch.equal(bits(phys.inverse_qfrc_actuator), bits(phys.qfrc_actuator))
     g = lambda t: t.cpu().numpy().astype(np.float64)
     host = np.einsum("nij,nj->ni", g(phys.qM), g(a)) - (g(phys.qfrc_passive) - g(phys.qfrc_bias) + g(phys.qfrc_actuator)) - g(phys.qfrc_constraint)
     hip = g(phys.qfrc_inverse) - g(phys.inverse_qfrc_actuator)
     q1, v1, c1, an = g(phys.qpos), g(phys.qvel), phys.ctrl.cpu().numpy(), a.cpu().numpy()
-    r32 = oracle_terms(oracle_mod, E.blob, E.dims.nv, E.dims.ncon_max, q1, v1, c1, precisions=("f32",))["f32"]
+    r32 = oracle_pass(oracle_mod, E.blob, E.dims, q1, v1, c1, precisions=("f32",))["f32"]
     lo, hi = [], []
     for e in range(N):
         x32, x64 = inverse_ref(r32[e], an[e], np.float32, E.dims.nefc_max), inverse_ref(r32[e], an[e], np.float64, E.dims.nefc_max)
         lo.append(x32["qfrc_inverse"] - x32["qfrc_actuator"])
         hi.append(x64["qfrc_inverse"] - x64["qfrc_actuator"])
     fails = []
-    _rule(kind, "qfrc_inverse - qfrc_actuator", _rel(hip, host), _rel(np.stack(lo), np.stack(hi)), fails)
+    rule(kind, "qfrc_inverse - qfrc_actuator", rel(hip, host), rel(np.stack(lo), np.stack(hi)), fails)
     assert not fails, fails
 
 
@@ -235,11 +182,11 @@ def test_discrete_accelerations(oracle_mod, kind):
     (cube) and 2.8e-3 (tshape, one env of 256 unexplained) of it.  On the Go2 models the gap is rounding and that figure says
     nothing."""
     import torch
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind)
     h = float(envdef.sys.arrays["opt_timestep"][0])
     damp = np.asarray(envdef.sys.arrays["dof_damping"], np.float64)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
-    ref = _ref(oracle_mod, kind, E, qpos, qvel, ctrl)
+    ref = _ref(oracle_mod, E, qpos, qvel, ctrl)
     a = _inputs(ref["f64"])["noisy"]
     phys.inverse(_dev(a, phys), discrete=True)
     torch.cuda.synchronize()
@@ -249,7 +196,7 @@ def test_discrete_accelerations(oracle_mod, kind):
         c32 = np.stack([to_continuous(ref["f32"][e], a[e], h, damp, np.float32) for e in range(N)])
         assert np.abs(c64 - a).max() > 1e-3                   # the conversion moves the input: the test shows something
         fails = []
-        _rule(kind, "inverse_qacc (discrete)", _rel(got, c64), _rel(c32, c64), fails)
+        rule(kind, "inverse_qacc (discrete)", rel(got, c64), rel(c32, c64), fails)
         assert not fails, fails
     else:
         assert (got.view(np.int32) == a.view(np.int32)).all()
@@ -258,7 +205,7 @@ def test_discrete_accelerations(oracle_mod, kind):
     phys.inverse(phys.inverse_qacc.clone().contiguous())
     torch.cuda.synchronize()
     for f, v in plain.items():
-        assert torch.equal(_bits(getattr(phys, f)), _bits(v)), f
+        assert torch.equal(bits(getattr(phys, f)), bits(v)), f
     # (b)
     rec0, v0 = E.record.clone(), phys.qvel.clone()
     phys.step(None, 1)
@@ -270,7 +217,7 @@ def test_discrete_accelerations(oracle_mod, kind):
     torch.cuda.synchronize()
     got, dqn = phys.inverse_qacc.cpu().numpy(), dq.cpu().numpy()
     host = np.stack([to_continuous(ref["f64"][e], dqn[e], h, damp, np.float64) for e in range(N)]) if kind in IMPLICIT else dqn.astype(np.float64)
-    err, base = _rel(got, side), _rel(host, side)
+    err, base = rel(got, side), rel(host, side)
     print(kind, "round trip: kernel p99 %.2e max %.2e | fp64 conversion of the same difference p99 %.2e max %.2e"
           % (np.quantile(err, 0.99), err.max(), np.quantile(base, 0.99), base.max()))
     # where the gap comes from, measured (the record is the one the step started from, so constraint_forces() repeats the step's
@@ -280,12 +227,12 @@ def test_discrete_accelerations(oracle_mod, kind):
     phys.constraint_forces()
     torch.cuda.synchronize()
     g = lambda t: t.cpu().numpy().astype(np.float64)
-    assert torch.equal(_bits(phys.constraint_qacc), _bits(phys.qacc))
+    assert torch.equal(bits(phys.constraint_qacc), bits(phys.qacc))
     M, qa = g(phys.qM), g(phys.constraint_qacc)
     resid = g(phys.qfrc_passive) - g(phys.qfrc_bias) + g(phys.qfrc_actuator) + g(phys.qfrc_constraint) - np.einsum("nij,nj->ni", M, qa)
     pred = np.linalg.solve(M, resid[:, :, None])[:, :, 0]
     gap = got.astype(np.float64) - side
-    left = _rel(gap, pred)
+    left = rel(gap, pred)
     print(kind, "round trip gap against M^-1 (solver residual): |gap|_inf p99 %.2e max %.2e, |gap - M^-1 r| / max(1, |M^-1 r|_inf) p99 %.2e max %.2e"
           % (np.quantile(np.abs(gap).max(1), 0.99), np.abs(gap).max(), np.quantile(left, 0.99), left.max()))
     bad = err > np.maximum(3.0 * base, 1e-5)
@@ -303,8 +250,8 @@ def test_inverse_has_no_side_effects_and_ignores_applied_forces(kind):
     from rsr_mjx_amd import _lib
     from rsr_mjx_amd.physics import Physics
     site = "endpoint" if kind in ("cube", "tshape") else "imu"
-    envdef, E, phys, qpos, qvel, ctrl = _setup(kind, sensors=[("lin", "framelinvel", site)])
-    _, F, _, _ = _make(kind, N, False)
+    envdef, E, phys, qpos, qvel, ctrl = setup(kind, sensors=[("lin", "framelinvel", site)])
+    _, F, _, _ = make(kind, N, False)
     F.reset(prng.split(prng.PRNGKey(1), N))
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.step(None, 1)
@@ -314,20 +261,14 @@ def test_inverse_has_no_side_effects_and_ignores_applied_forces(kind):
     torch.cuda.synchronize()
     g = torch.Generator(device="cpu").manual_seed(5)
     a = (phys.qacc.cpu() + 0.3 * torch.randn((N, E.dims.nv), generator=g)).to(phys.device).contiguous()
-    snap = lambda: dict(record=E.record.clone(), **{"side_" + k: v.clone() for k, v in phys._side.items()},
-                        **{"dyn_" + f: getattr(phys, f).clone() for f in ("qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator")},
-                        **{"con_" + k: v.clone() for k, v in phys._con_views().items()}, fd=phys._fd_view("columns").clone())
-    before = snap()
-    assert all(float(before[k].abs().max()) > 0 for k in ("side_sensordata", "dyn_qM", "con_efc_force", "fd"))
+    before = handle_snapshot(phys, all_but("inverse"))
+    assert all(float(before[k].abs().max()) > 0 for k in ("side_sensordata", "dyn_qM", "con_efc_force", "fd_columns"))
     ids = np.array([3, 250, 7, N + 5, 100], np.int32)
     ids_dev = torch.as_tensor(ids, device=phys.device)
     for flags in (0, _lib.INV_DISCRETE):
         _lib.check(_lib.lib().rsr_physics_inverse(phys._h, C.c_void_p(a.data_ptr()), C.c_void_p(ids_dev.data_ptr()), len(ids), flags, phys._stream()))
-    torch.cuda.synchronize()
-    after = snap()
-    for k in before:
-        assert torch.equal(_bits(after[k]), _bits(before[k])), k
-    views = phys._inv_views()
+    assert_unchanged(before, handle_snapshot(phys, all_but("inverse")))
+    views = handle_views(phys, "inverse")
     listed = np.array([3, 250, 7, 100])
     others = np.setdiff1d(np.arange(N), listed)
     subset = {k: v.clone() for k, v in views.items()}
@@ -338,7 +279,7 @@ def test_inverse_has_no_side_effects_and_ignores_applied_forces(kind):
     torch.cuda.synchronize()
     full = {k: v.clone() for k, v in views.items()}
     for k in views:
-        assert torch.equal(_bits(full[k][listed]), _bits(subset[k][listed])), k
+        assert torch.equal(bits(full[k][listed]), bits(subset[k][listed])), k
         assert float(full[k][others].abs().max()) > 0.0, k
     with pytest.raises(ValueError):
         phys.inverse(a, env_ids=[N])
@@ -361,9 +302,9 @@ def test_inverse_has_no_side_effects_and_ignores_applied_forces(kind):
     phys.inverse(a, discrete=True)
     torch.cuda.synchronize()
     for k in views:
-        assert torch.equal(_bits(views[k]), _bits(full[k])), k
+        assert torch.equal(bits(views[k]), bits(full[k])), k
     phys.clear_applied()
-    assert torch.equal(_bits(E.record), _bits(before["record"]))
+    assert torch.equal(bits(E.record), bits(before["record"]))
     # a step after inverse() equals the same step without it (F: the same record, a handle that never ran inverse)
     F.record.copy_(before["record"])
     physF = Physics(F)
@@ -371,5 +312,5 @@ def test_inverse_has_no_side_effects_and_ignores_applied_forces(kind):
     physF.step(None, 1)
     torch.cuda.synchronize()
     for k in PIPE:
-        assert torch.equal(_bits(E.view(k)), _bits(F.view(k))), k
-    assert torch.equal(_bits(phys.qacc), _bits(physF.qacc))
+        assert torch.equal(bits(E.view(k)), bits(F.view(k))), k
+    assert torch.equal(bits(phys.qacc), bits(physF.qacc))

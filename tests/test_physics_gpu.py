@@ -3,25 +3,8 @@ bit-identity with the fused env step, parity with the CPU oracle's forward / ste
 import numpy as np
 import pytest
 
+from physics_support import FAMILIES, PIPE, assert_unchanged, bits, handle_snapshot, make, random_states, rel, rule
 from rsr_mjx_amd import prng
-
-FAMILIES = ["cube", "tshape", "go2flat", "go2rough", "footstand"]
-
-
-def _make(kind, n, dr_on):
-    """(envdef, batched env, dr dict or None, action scale); no Episode / AutoReset wrappers, no Go2 kicks."""
-    from rsr_mjx_amd.envs import airbot, go2
-    if kind in ("cube", "tshape"):
-        envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-        dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n)) if dr_on else None
-        return envdef, envdef.batched(n, randomization=dr), dr, 1.0
-    name = {"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind]
-    envdef = go2.load(name)
-    dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n)) if dr_on else None
-    return envdef, envdef.batched(n, randomization=dr), dr, 0.5
-
-
-PIPE = ("qpos", "qvel", "ctrl", "qacc_warmstart", "time", "xpos", "site_xpos")
 
 
 @pytest.mark.gpu
@@ -33,8 +16,8 @@ def test_physics_step_is_bit_identical_to_env_step(kind):
     from rsr_mjx_amd.physics import Physics
     n = 1024
     dr_on = kind != "tshape"                 # (the Airbot randomisation of domain_randomize.py is the cube scene's)
-    _, A, dr, scale = _make(kind, n, dr_on)
-    _, B, _, _ = _make(kind, n, dr_on)
+    _, A, dr, scale = make(kind, n, dr_on)
+    _, B, _, _ = make(kind, n, dr_on)
     rng = np.random.default_rng(3)
     nu = A.dims.nu
     act = lambda: np.clip(rng.normal(size=(n, nu)) * scale, -1, 1).astype(np.float32)
@@ -62,51 +45,26 @@ def test_physics_step_is_bit_identical_to_env_step(kind):
     np.testing.assert_array_equal(phys.qacc.cpu().numpy(), B.view("qacc_warmstart").cpu().numpy())
 
 
-def _random_states(envdef, kind, n, seed):
-    """Reset distribution of the env plus a perturbation of qpos / qvel, and a random ctrl inside the control range."""
-    import torch
-    _, E, _, _ = _make(kind, n, False)
-    E.reset(prng.split(prng.PRNGKey(seed), n))
-    torch.cuda.synchronize()
-    rng = np.random.default_rng(seed)
-    qpos = E.view("qpos").cpu().numpy().astype(np.float64)
-    qvel = E.view("qvel").cpu().numpy().astype(np.float64)
-    A = envdef.sys.arrays
-    jt, qa = A["jnt_type"], A["jnt_qposadr"]
-    for j in range(len(jt)):
-        if jt[j] in (2, 3):                               # hinge / slide: perturb the angle
-            qpos[:, qa[j]] += rng.normal(scale=0.05, size=n)
-    qvel += rng.normal(scale=0.2, size=qvel.shape)
-    lo, hi = A["actuator_ctrlrange"][:, 0], A["actuator_ctrlrange"][:, 1]
-    ctrl = lo + (hi - lo) * rng.uniform(size=(n, len(lo)))
-    return qpos.astype(np.float32), qvel.astype(np.float32), ctrl.astype(np.float32)
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64).reshape(len(a), -1), np.asarray(b, np.float64).reshape(len(b), -1)
-    return (np.abs(a - b) / np.maximum(1.0, np.abs(b).max(1, keepdims=True))).max(1)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", FAMILIES)
 def test_physics_oracle_parity(oracle_mod, kind):
     """forward and step (nsteps 1 and n_frames) against the oracle's debug forward / step, per env, DR off.  Kinematic fields
-    (xpos, xquat, site_xpos) within 1e-5 everywhere; dynamic fields (qacc, qvel, actuator_force, and qpos after n_frames) with
-    p99 <= 1e-5, or 3 x the fp32 oracle's own p99 distance from the fp64 oracle where that is larger (acceleration-level fields of
-    the ill-conditioned Airbot solves), and every env within max(1e-4, 20 x the largest f32-to-f64 oracle distance of the field).  An env whose active
-    contact set differs from the f64 oracle's (a contact mode flip) is counted, and the count is bounded, not the error."""
+    (xpos, xquat, site_xpos) within 1e-5 everywhere; dynamic fields (qacc, qvel, actuator_force, and qpos after n_frames) under
+    the rule of tests/physics_support.py (its 3 x arm is met by the acceleration-level fields of the ill-conditioned Airbot solves).
+    An env whose active contact set differs from the f64 oracle's (a contact mode flip) is counted, and the count is bounded (2 %),
+    not the error."""
     import torch
     from rsr_mjx_amd.physics import Physics
     n = 256
-    envdef, E, _, _ = _make(kind, n, False)
+    envdef, E, _, _ = make(kind, n, False)
     E.reset(prng.split(prng.PRNGKey(1), n))
-    qpos, qvel, ctrl = _random_states(envdef, kind, n, 11)
+    qpos, qvel, ctrl = random_states(envdef, kind, n, 11)
     phys = Physics(E)
     nf = phys.n_substeps
     o32 = oracle_mod.Oracle(E.blob); o32.set_ncon_cap(E.dims.ncon_max)
     o64 = oracle_mod.Oracle(E.blob, "f64"); o64.set_ncon_cap(E.dims.ncon_max)
     fields = ("qpos", "qvel", "qacc", "actuator_force", "xpos", "xquat", "site_xpos")
-    report, fails = {}, []
+    fails = []
     for mode, nsteps in (("forward", 0), ("step1", 1), ("stepN", nf)):
         phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
         if nsteps:
@@ -130,26 +88,19 @@ def test_physics_oracle_parity(oracle_mod, kind):
                 ncon[p][e] = int(o.get("counts")[3])
         hip_ncon = phys.contacts()["ncon"].cpu().numpy()
         flips = (hip_ncon != ncon["f64"]) | (ncon["f32"] != ncon["f64"])
-        report[(mode, "flips")] = (float(flips.sum()), float(n), 0.0)
+        print(kind, mode, "contact-mode flips in %d of %d envs" % (flips.sum(), n))
         if flips.mean() > 0.02:
             fails.append(f"{kind} {mode}: contact-mode flips in {flips.sum()} of {n} envs")
         keep = ~flips
         for f in fields:
-            err = _rel(hip[f], ref["f64"][f])[keep]
-            spread = _rel(ref["f32"][f], ref["f64"][f])[keep]
-            p99, mx = float(np.quantile(err, 0.99)), float(err.max())
-            report[(mode, f)] = (p99, mx, float(spread.max()))
+            err = rel(hip[f], ref["f64"][f])[keep]
+            spread = rel(ref["f32"][f], ref["f64"][f])[keep]
             if f in ("xpos", "xquat", "site_xpos") and mode == "forward":
-                if mx > 1e-5:
-                    fails.append(f"{kind} {mode} {f}: max {mx:.2e}")
+                print(kind, mode, f, "max %.2e" % err.max())
+                if err.max() > 1e-5:
+                    fails.append(f"{kind} {mode} {f}: max {err.max():.2e}")
             else:
-                if not (p99 <= 1e-5 or p99 <= 3.0 * float(np.quantile(spread, 0.99))):
-                    fails.append(f"{kind} {mode} {f}: p99 {p99:.2e}")
-                cap = max(1e-4, 20.0 * float(spread.max()))
-                if not (err <= cap).all():
-                    fails.append(f"{kind} {mode} {f}: {(err > cap).sum()} envs beyond the cap, max {mx:.2e}")
-    for k, v in sorted(report.items()):
-        print(kind, *k, "p99 %.2e max %.2e f32-f64 max %.2e" % v)
+                rule(kind, f"{mode} {f}", err, spread, fails)
     assert not fails, fails
 
 
@@ -161,9 +112,9 @@ def test_physics_contacts_view(oracle_mod, kind):
     import torch
     from rsr_mjx_amd.physics import Physics
     n = 256
-    envdef, E, _, _ = _make(kind, n, False)
+    envdef, E, _, _ = make(kind, n, False)
     E.reset(prng.split(prng.PRNGKey(2), n))
-    qpos, qvel, ctrl = _random_states(envdef, kind, n, 12)
+    qpos, qvel, ctrl = random_states(envdef, kind, n, 12)
     if kind == "footstand":                          # lower the trunk onto the floor: capsule / cylinder contacts, over the cap
         qpos[: n // 2, 2] = 0.08
     phys = Physics(E)
@@ -207,24 +158,21 @@ def test_set_state_semantics(oracle_mod, kind):
     from rsr_mjx_amd import _lib, mjcf
     from rsr_mjx_amd.physics import Physics
     n = 128
-    envdef, E, _, scale = _make(kind, n, False)
+    envdef, E, _, scale = make(kind, n, False)
     E.reset(prng.split(prng.PRNGKey(4), n))
     rng = np.random.default_rng(0)
     E.step(None, np.clip(rng.normal(size=(n, E.dims.nu)) * scale, -1, 1).astype(np.float32))
     phys = Physics(E)
     phys.forward()
     torch.cuda.synchronize()
-    qpos, qvel, ctrl = _random_states(envdef, kind, n, 13)
+    qpos, qvel, ctrl = random_states(envdef, kind, n, 13)
     # subset write: the other envs' record and physics outputs are bit-unchanged
-    rec0, side0 = E.record.clone(), {k: v.clone() for k, v in phys._side.items()}
+    before = handle_snapshot(phys, ("record", "side"))
     ids = np.array([3, 17, 64, 100])
     phys.set_state(qpos=qpos[ids], qvel=qvel[ids], ctrl=ctrl[ids], env_ids=ids)
-    torch.cuda.synchronize()
     others = np.setdiff1d(np.arange(n), ids)
-    bits = lambda t: t.contiguous().view(torch.int32)          # (bitwise: Go2 records hold PRNG key words, some of them NaN patterns)
-    assert torch.equal(bits(E.record[others]), bits(rec0[others]))
-    for k in side0:
-        assert torch.equal(bits(phys._side[k][others]), bits(side0[k][others])), k
+    rows = lambda snap: {k: v[others] for k, v in snap.items()}
+    assert_unchanged(rows(before), rows(handle_snapshot(phys, ("record", "side"))))
     np.testing.assert_array_equal(phys.qpos[ids].cpu().numpy(), qpos[ids])
     np.testing.assert_array_equal(phys.qacc_warmstart[ids].cpu().numpy(), phys.qacc[ids].cpu().numpy())
     # every env: kinematics consistent with the state that was set (fp64 forward kinematics, oracle site positions)
@@ -240,7 +188,7 @@ def test_set_state_semantics(oracle_mod, kind):
         o.forward(qpos[e], qvel[e], ctrl[e], None)
         np.testing.assert_allclose(sx[e].ravel(), o.get("site_xpos"), atol=1e-5)
     # set_state then env.step == the fused step from the same pipeline state written directly into another batch
-    _, F, _, _ = _make(kind, n, False)
+    _, F, _, _ = make(kind, n, False)
     F.reset(prng.split(prng.PRNGKey(9), n))
     for k in PIPE:
         F.view(k).copy_(E.view(k))

@@ -6,69 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from physics_support import ALL, FAMILIES, GO2_EXTRA, PIPE, assert_bitwise, handle_views, make, pair, sensor_spec
 from rsr_mjx_amd import prng
-
-FAMILIES = ["cube", "tshape", "go2flat", "go2rough", "footstand"]
-PIPE = ("qpos", "qvel", "ctrl", "qacc_warmstart", "time", "xpos", "site_xpos")
-ALL = ("qpos", "qvel", "time", "actuator_force", "ncon", "sensordata")
-
-# every supported type on the Airbot endpoint (and on the T-shape's tail sites, framepos with a ref site)
-AIRBOT_SPEC = [("pos", "framepos", "endpoint"), ("linvel", "framelinvel", "endpoint"), ("angvel", "frameangvel", "endpoint"),
-               ("gyro", "gyro", "endpoint"), ("vel", "velocimeter", "endpoint"), ("quat", "framequat", "endpoint"),
-               ("xaxis", "framexaxis", "endpoint"), ("zaxis", "framezaxis", "endpoint")]
-TSHAPE_SPEC = AIRBOT_SPEC + [("tail_in_ee", "framepos", "T_tail", "endpoint")]
-GO2_EXTRA = [("FR_vel", "velocimeter", "FR"), ("FR_quat", "framequat", "FR")]          # (55 + 7 floats: within the 64 cap)
-
-
-def _make(kind, n, dr_on):
-    """(envdef, batched env, action scale); no Episode / AutoReset wrappers, no Go2 kicks (as tests/test_physics_gpu.py)."""
-    from rsr_mjx_amd.envs import airbot, go2
-    if kind in ("cube", "tshape"):
-        envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-        dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n)) if dr_on else None
-        return envdef, envdef.batched(n, randomization=dr), 1.0
-    name = {"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind]
-    envdef = go2.load(name)
-    dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n)) if dr_on else None
-    return envdef, envdef.batched(n, randomization=dr), 0.5
-
-
-def _spec(kind, envdef):
-    if kind == "cube":
-        return AIRBOT_SPEC
-    if kind == "tshape":
-        return TSHAPE_SPEC
-    return envdef.sensors + GO2_EXTRA
-
-
-def _pair(kind, n, seed=3, steps=3):
-    """Two batches in the same state (records equal bit for bit) after a few env steps, same DR."""
-    import torch
-    dr_on = kind != "tshape"                 # (the Airbot randomisation of domain_randomize.py is the cube scene's)
-    envdef, A, scale = _make(kind, n, dr_on)
-    _, B, _ = _make(kind, n, dr_on)
-    rng = np.random.default_rng(seed)
-    A.reset(prng.split(prng.PRNGKey(7), n))
-    B.reset(prng.split(prng.PRNGKey(7), n))
-    for _ in range(steps):
-        A.step(None, np.clip(rng.normal(size=(n, A.dims.nu)) * scale, -1, 1).astype(np.float32))
-    B.record.copy_(A.record)
-    torch.cuda.synchronize()
-    return envdef, A, B, scale, rng
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int32)
-
-
-def _assert_bitwise(name, a, b):
-    import torch
-    a, b = a.contiguous(), b.contiguous()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    if not torch.equal(_bits(a), _bits(b)):
-        d = (a.double() - b.double()).abs()
-        raise AssertionError(f"{name}: {int((_bits(a) != _bits(b)).sum())} elements differ, max |d| {float(d.max()):.3e}")
 
 
 def _ctrl(envdef, A, rng, T):
@@ -83,8 +22,8 @@ def test_rollout_is_repeated_step_bit_for_bit(kind):
     import torch
     from rsr_mjx_amd.physics import Physics
     n, T = 1024, 16
-    envdef, A, B, scale, rng = _pair(kind, n)
-    spec = _spec(kind, envdef)
+    envdef, A, B, scale, rng = pair(kind, n)
+    spec = sensor_spec(kind, envdef)
     pa, pb = Physics(A, sensors=spec), Physics(B, sensors=spec)
     ctrl = torch.as_tensor(_ctrl(envdef, A, rng, T), device=A.device)
     keep = {k: B.view(k).clone() for k in ("obs", "reward", "done", "metrics", "first_qpos", "info_go2", "stats", "privileged_obs")}
@@ -92,26 +31,26 @@ def test_rollout_is_repeated_step_bit_for_bit(kind):
     for t in range(T):
         pa.step(ctrl[:, t], pa.n_substeps)
         ref["qpos"].append(pa.qpos.clone()); ref["qvel"].append(pa.qvel.clone()); ref["time"].append(pa.time[:, None].clone())
-        ref["actuator_force"].append(pa.actuator_force.clone()); ref["ncon"].append(pa._side["ncon"].clone())
+        ref["actuator_force"].append(pa.actuator_force.clone()); ref["ncon"].append(handle_views(pa, "side")["ncon"].clone())
         ref["sensordata"].append(pa.sensordata.clone())
     out = pb.rollout(ctrl, fields=ALL)
     torch.cuda.synchronize()
     assert pb.nsensordata == sum({"framequat": 4}.get(s[1], 3) for s in spec)
     for f in ALL:
-        _assert_bitwise(f"{kind} rollout {f}", out[f], torch.stack(ref[f], 1))
+        assert_bitwise(f"{kind} rollout {f}", out[f], torch.stack(ref[f], 1))
     for k in PIPE:
-        _assert_bitwise(f"{kind} record {k}", B.view(k), A.view(k))
+        assert_bitwise(f"{kind} record {k}", B.view(k), A.view(k))
     for k in ("qacc", "actuator_force", "xquat", "ncon", "contact", "ncon_dropped", "sensordata"):
-        _assert_bitwise(f"{kind} side {k}", pb._side[k], pa._side[k])
+        assert_bitwise(f"{kind} side {k}", handle_views(pb, "side")[k], handle_views(pa, "side")[k])
     for k, v in keep.items():                    # the env's bookkeeping is left alone
-        _assert_bitwise(f"{kind} untouched {k}", B.view(k), v)
-    _assert_bitwise(f"{kind} whole record", B.record, A.record)
+        assert_bitwise(f"{kind} untouched {k}", B.view(k), v)
+    assert_bitwise(f"{kind} whole record", B.record, A.record)
     # env.step continues from the state the rollout left
     act = np.clip(rng.normal(size=(n, A.dims.nu)) * scale, -1, 1).astype(np.float32)
     A.step(None, act)
     B.step(None, act)
     torch.cuda.synchronize()
-    _assert_bitwise(f"{kind} env.step after rollout", B.record, A.record)
+    assert_bitwise(f"{kind} env.step after rollout", B.record, A.record)
 
 
 # privileged_state columns (go2/joystick.py:341-366): gyro, accelerometer, (gravity), local linvel, global angvel, ..., feet
@@ -129,17 +68,17 @@ def test_sensors_are_the_envs_own_values(kind):
     import torch
     from rsr_mjx_amd.physics import Physics
     n = 1024
-    envdef, A, B, scale, rng = _pair(kind, n)
+    envdef, A, B, scale, rng = pair(kind, n)
     A.step(None, np.clip(rng.normal(size=(n, A.dims.nu)) * scale, -1, 1).astype(np.float32))
     ctrl1 = A.view("ctrl").clone()
     phys = Physics(B, sensors=envdef.sensors)
     out = phys.rollout(ctrl1[:, None, :], nsteps=phys.n_substeps, fields=("sensordata", "qpos"))
     torch.cuda.synchronize()
-    _assert_bitwise(f"{kind} qpos", out["qpos"][:, 0], A.view("qpos"))
+    assert_bitwise(f"{kind} qpos", out["qpos"][:, 0], A.view("qpos"))
     priv = A.view("privileged_obs")
     for name, col in _PRIV.items():
-        _assert_bitwise(f"{kind} {name}", phys.sensor(name, out["sensordata"])[:, 0], priv[:, col:col + 3])
-    _assert_bitwise(f"{kind} current sensordata", phys.sensordata, out["sensordata"][:, 0])
+        assert_bitwise(f"{kind} {name}", phys.sensor(name, out["sensordata"])[:, 0], priv[:, col:col + 3])
+    assert_bitwise(f"{kind} current sensordata", phys.sensordata, out["sensordata"][:, 0])
 
 
 def _quat2mat(q):
@@ -203,12 +142,12 @@ def test_frame_sensors_against_fp64(kind):
     import torch
     from rsr_mjx_amd.physics import Physics
     n, T = 1024, 4
-    envdef, A, scale = _make(kind, n, False)
+    envdef, A, _, scale = make(kind, n, False)
     A.reset(prng.split(prng.PRNGKey(21), n))
     rng = np.random.default_rng(21)
     for _ in range(2):
         A.step(None, np.clip(rng.normal(size=(n, A.dims.nu)) * scale, -1, 1).astype(np.float32))
-    spec = [s for s in (envdef.sensors + GO2_EXTRA if kind == "go2flat" else _spec(kind, envdef)) if s[1] != "accelerometer"]
+    spec = [s for s in (envdef.sensors + GO2_EXTRA if kind == "go2flat" else sensor_spec(kind, envdef)) if s[1] != "accelerometer"]
     phys = Physics(A, sensors=spec)
     q0, v0 = phys.qpos.clone(), phys.qvel.clone()
     out = phys.rollout(torch.as_tensor(_ctrl(envdef, A, rng, T), device=A.device), nsteps=1, fields=("qpos", "qvel", "sensordata"))
@@ -236,10 +175,10 @@ def test_masks_and_errors(kind):
     from rsr_mjx_amd import _lib
     from rsr_mjx_amd.physics import Physics
     n, T = 1024, 5
-    envdef, A, B, scale, rng = _pair(kind, n)
-    _, Cb, _ = _make(kind, n, kind != "tshape")
+    envdef, A, B, scale, rng = pair(kind, n)
+    _, Cb, _, _ = make(kind, n, kind != "tshape")
     Cb.record.copy_(A.record)
-    spec = _spec(kind, envdef)
+    spec = sensor_spec(kind, envdef)
     ctrl = torch.as_tensor(_ctrl(envdef, A, rng, T), device=A.device)
     pa, pb, pc = Physics(A, sensors=spec), Physics(B, sensors=spec), Physics(Cb)
     # fields left NULL are not written: sentinels survive; a subset records what recording everything records
@@ -250,20 +189,20 @@ def test_masks_and_errors(kind):
     sub = pb.rollout(ctrl, fields=("qvel", "sensordata"), out={"qvel": sentinel["qvel"], "sensordata": sentinel["sensordata"]})
     torch.cuda.synchronize()
     assert sub["qvel"] is sentinel["qvel"]
-    _assert_bitwise("subset qvel", sub["qvel"], full["qvel"])
-    _assert_bitwise("subset sensordata", sub["sensordata"], full["sensordata"])
+    assert_bitwise("subset qvel", sub["qvel"], full["qvel"])
+    assert_bitwise("subset sensordata", sub["sensordata"], full["sensordata"])
     for f in ("qpos", "time", "actuator_force", "ncon"):
         assert (sentinel[f] == -7.25).all(), f
-    _assert_bitwise("subset record", B.record, A.record)
+    assert_bitwise("subset record", B.record, A.record)
     # with no sensors set, a step leaves exactly what it leaves with sensors set (but for sensordata)
     c1 = ctrl[:, 0]
     Cb.record.copy_(A.record)
     pa.step(c1)
     pc.step(c1)
     torch.cuda.synchronize()
-    _assert_bitwise("no-sensor step record", Cb.record, A.record)
+    assert_bitwise("no-sensor step record", Cb.record, A.record)
     for k in ("qacc", "actuator_force", "xquat", "ncon", "contact", "ncon_dropped"):
-        _assert_bitwise(f"no-sensor step side {k}", pc._side[k], pa._side[k])
+        assert_bitwise(f"no-sensor step side {k}", handle_views(pc, "side")[k], handle_views(pa, "side")[k])
     assert pc.nsensordata == 0 and pc.sensordata.shape == (n, 0)
     # clearing the table
     pb.set_sensors(None)

@@ -9,11 +9,10 @@ import functools
 import numpy as np
 import pytest
 
+from physics_support import ALL, FAMILIES, assert_bitwise, assert_unchanged, handle_snapshot, pair, sensor_spec
 from rsr_mjx_amd import prng
-from test_physics_rollout_gpu import ALL, FAMILIES, _assert_bitwise, _pair, _spec
 
 N, K, T = 64, 5, 4              # K odd, no divisor of N; N * K = 320 workgroups
-SIDE = ("qacc", "actuator_force", "xquat", "ncon", "contact", "ncon_dropped", "sensordata")
 
 
 def _dr(kind, envdef, n):
@@ -52,8 +51,8 @@ def _case(kind, applied=False):
     in the ctrl range, A's sampled rollouts and the replica batch's rollout, each computed once and left unchanged."""
     import torch
     from rsr_mjx_amd.physics import Physics
-    envdef, A, twin, scale, rng = _pair(kind, N)
-    spec = _spec(kind, envdef)
+    envdef, A, twin, scale, rng = pair(kind, N)
+    spec = sensor_spec(kind, envdef)
     pa = Physics(A, sensors=spec)
     R = _replica(kind, envdef, A, K)
     pr = Physics(R, sensors=spec)
@@ -64,10 +63,9 @@ def _case(kind, applied=False):
     rng_c = envdef.sys.arrays["actuator_ctrlrange"]
     lo, hi = rng_c[:, 0], rng_c[:, 1]
     ctrl = torch.as_tensor((lo + (hi - lo) * rng.uniform(size=(N, K, T, A.dims.nu))).astype(np.float32), device=A.device)
-    before = dict(record=A.record.clone(), **{"side " + k: pa._side[k].clone() for k in SIDE})
+    before = handle_snapshot(pa)
     full = pa.sample_rollouts(ctrl, fields=ALL)
-    torch.cuda.synchronize()
-    after = dict(record=A.record.clone(), **{"side " + k: pa._side[k].clone() for k in SIDE})
+    after = handle_snapshot(pa)
     ref = pr.rollout(ctrl.reshape(N * K, T, A.dims.nu), fields=ALL)
     torch.cuda.synchronize()
     del pr, R
@@ -79,11 +77,10 @@ def _check_against_replica(kind, c):
     assert c["pa"].nsensordata > 0
     for f in ALL:
         assert c["full"][f].shape[:3] == (N, K, T)
-        _assert_bitwise(f"{kind} sample {f}", c["full"][f], c["ref"][f].reshape(N, K, T, -1))
+        assert_bitwise(f"{kind} sample {f}", c["full"][f], c["ref"][f].reshape(N, K, T, -1))
         assert torch.isfinite(c["full"][f]).all(), f
     assert (c["full"]["ncon"] > 0).any()                                  # contacts were active
-    for k, v in c["before"].items():                                      # the whole record, the side buffer, sensordata
-        _assert_bitwise(f"{kind} untouched {k}", c["after"][k], v)
+    assert_unchanged(c["before"], c["after"])                             # the whole record and every buffer of the handle
 
 
 @pytest.mark.gpu
@@ -100,7 +97,7 @@ def test_samples_are_the_replica_rollout_bit_for_bit(kind):
     A.step(None, act)
     twin.step(None, act)
     torch.cuda.synchronize()
-    _assert_bitwise(f"{kind} env.step after sample_rollouts", A.record, twin.record)
+    assert_bitwise(f"{kind} env.step after sample_rollouts", A.record, twin.record)
     A.record.copy_(c["before"]["record"])
     torch.cuda.synchronize()
 
@@ -132,9 +129,9 @@ def test_rows_go_by_slot(kind):
     for f in ALL:
         assert out[f].data_ptr() == buf[f].data_ptr()
         for s, e in enumerate(ids):
-            _assert_bitwise(f"{kind} slot {s} (env {e}) {f}", out[f][s], full[f][e])
+            assert_bitwise(f"{kind} slot {s} (env {e}) {f}", out[f][s], full[f][e])
         assert (buf[f][len(ids)] == -7.25).all(), f
-    _assert_bitwise(f"{kind} record", A.record, c["before"]["record"])
+    assert_bitwise(f"{kind} record", A.record, c["before"]["record"])
     # an empty list launches nothing
     empty = pa.sample_rollouts(sub_ctrl[:0], env_ids=[])
     assert {f: tuple(t.shape) for f, t in empty.items()} == dict(qpos=(0, K, T, A.dims.nq), qvel=(0, K, T, A.dims.nv), time=(0, K, T, 1))
@@ -150,10 +147,10 @@ def test_rows_go_by_slot(kind):
     torch.cuda.synchronize()
     assert rc == 0, _lib.lib().rsr_last_error()
     for f in ALL:
-        _assert_bitwise(f"{kind} raw slot 0 {f}", buf[f][0], full[f][41])
-        _assert_bitwise(f"{kind} raw slot 2 {f}", buf[f][2], full[f][17])
+        assert_bitwise(f"{kind} raw slot 0 {f}", buf[f][0], full[f][41])
+        assert_bitwise(f"{kind} raw slot 2 {f}", buf[f][2], full[f][17])
         assert (buf[f][1] == -7.25).all() and (buf[f][3] == -7.25).all(), f
-    _assert_bitwise(f"{kind} record after the raw call", A.record, c["before"]["record"])
+    assert_bitwise(f"{kind} record after the raw call", A.record, c["before"]["record"])
 
 
 @pytest.mark.gpu
@@ -168,17 +165,17 @@ def test_samples_are_indexed_by_k(kind):
     torch.cuda.synchronize()
     for f in ALL:
         for k in range(1, K):
-            _assert_bitwise(f"{kind} same ctrl, sample {k} {f}", same[f][:, k], same[f][:, 0])
-        _assert_bitwise(f"{kind} same ctrl is sample 0 of the distinct ones {f}", same[f][:, 0], c["full"][f][:, 0])
+            assert_bitwise(f"{kind} same ctrl, sample {k} {f}", same[f][:, k], same[f][:, 0])
+        assert_bitwise(f"{kind} same ctrl is sample 0 of the distinct ones {f}", same[f][:, 0], c["full"][f][:, 0])
     assert any(not torch.equal(c["full"]["qpos"][:, k], c["full"]["qpos"][:, 0]) for k in range(1, K))
     # K = 1 is rollout on a copy of the batch
     one = pa.sample_rollouts(ctrl[:, :1].contiguous(), fields=ALL)
     twin.record.copy_(c["before"]["record"])
-    ref = Physics(twin, sensors=_spec(kind, c["envdef"])).rollout(ctrl[:, 0].contiguous(), fields=ALL)
+    ref = Physics(twin, sensors=sensor_spec(kind, c["envdef"])).rollout(ctrl[:, 0].contiguous(), fields=ALL)
     torch.cuda.synchronize()
     for f in ALL:
-        _assert_bitwise(f"{kind} K = 1 {f}", one[f][:, 0], ref[f])
-    _assert_bitwise(f"{kind} record", A.record, c["before"]["record"])
+        assert_bitwise(f"{kind} K = 1 {f}", one[f][:, 0], ref[f])
+    assert_bitwise(f"{kind} record", A.record, c["before"]["record"])
 
 
 @pytest.mark.gpu
@@ -191,8 +188,8 @@ def test_dispatch_ignores_the_handles_other_buffers(kind):
     import torch
     from rsr_mjx_amd.physics import Physics
     n, k, t = 2, 2, 2
-    envdef, A, _, _, rng = _pair(kind, n)
-    spec = _spec(kind, envdef)
+    envdef, A, _, _, rng = pair(kind, n)
+    spec = sensor_spec(kind, envdef)
     lo, hi = envdef.sys.arrays["actuator_ctrlrange"].T
     ctrl = torch.as_tensor((lo + (hi - lo) * rng.uniform(size=(n, k, t, A.dims.nu))).astype(np.float32), device=A.device)
     qacc = (5.0 * torch.randn((n, A.dims.nv), generator=torch.Generator(device="cpu").manual_seed(2))).to(A.device).contiguous()
@@ -202,8 +199,7 @@ def test_dispatch_ignores_the_handles_other_buffers(kind):
         phys.set_state(**state)                                           # the same record for both handles
         out = {"sample " + f: v.clone() for f, v in phys.sample_rollouts(ctrl, nsteps=1, fields=ALL).items()}
         phys.inverse(qacc)
-        out.update({"inverse " + f: v.clone() for f, v in phys._inv_views().items()})
-        torch.cuda.synchronize()
+        out.update(handle_snapshot(phys, ("inverse",)))
         return out
     first = run(Physics(A, sensors=spec))
     second = Physics(A, sensors=spec)
@@ -215,7 +211,7 @@ def test_dispatch_ignores_the_handles_other_buffers(kind):
     again = run(second)
     assert sorted(first) == sorted(again) and len(first) == len(ALL) + 6
     for f, v in first.items():
-        _assert_bitwise(f"{kind} {f}", again[f], v)
+        assert_bitwise(f"{kind} {f}", again[f], v)
 
 
 @pytest.mark.gpu
@@ -248,5 +244,5 @@ def test_refusals_on_the_device():
         assert fn(*args, pa._stream()) == -1, what                       # RSR_ERR_ARG
         assert b"rsr_physics_sample_rollouts" in L.rsr_last_error(), what
     torch.cuda.synchronize()
-    _assert_bitwise("record after the refusals", A.record, before)
+    assert_bitwise("record after the refusals", A.record, before)
     assert (qpos == -7.25).all() and (sd == -7.25).all()

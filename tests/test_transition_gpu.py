@@ -2,13 +2,12 @@
 tangent space of (qpos, qvel), MuJoCo's mjd_transitionFD.  The call is specified as "the differences of the step at the given eps",
 so the tests take it apart: every perturbed run is the stepper's bit for bit, the perturbations are mj_integratePos's, the columns
 are mj_differentiatePos of the runs' end states, and at the same eps the columns agree with the CPU oracle's own finite differences
-as closely as the project's rule for a dynamic field asks (tests/test_dynamics_gpu.py)."""
+as closely as the project's rule for a dynamic field asks (tests/physics_support.py)."""
 import numpy as np
 import pytest
 
+from physics_support import FAMILIES, PIPE, all_but, assert_unchanged, bits, free_states, handle_snapshot, handle_views, make, rel, rule
 from rsr_mjx_amd import prng
-from test_physics_gpu import FAMILIES, PIPE, _make, _random_states, _rel
-from test_dynamics_gpu import _free_states, _rule
 
 N = 64
 EPS = 1e-3
@@ -22,13 +21,9 @@ _ID = lambda c: "%s%s%s%s%s" % (c[0], "-dr" if c[1] else "", "-applied" if c[2] 
 _RUNS = {}
 
 
-def _bits(t):
-    return t.contiguous().view(__import__("torch").int32)
-
-
 def _stepped(kind, n, dr_on, seed=7):
     """(envdef, env batch) after a reset and 3 env steps: Go2 feet and Airbot fingers in contact"""
-    envdef, E, _, scale = _make(kind, n, dr_on)
+    envdef, E, _, scale = make(kind, n, dr_on)
     rng = np.random.default_rng(3)
     E.reset(prng.split(prng.PRNGKey(seed), n))
     for _ in range(3):
@@ -60,7 +55,7 @@ def _run(cfg):
     x, y = phys.fd_x.clone(), phys.fd_y.clone()
     assert x.shape == (N, ncol, 2, nq + nv + nu) and y.shape == (N, ncol, 2, nq + nv)
     for k in PIPE:                                                 # the call left the record alone
-        assert torch.equal(_bits(E.view(k)), _bits(saved[k])), k
+        assert torch.equal(bits(E.view(k)), bits(saved[k])), k
     bad = torch.zeros((), dtype=torch.int64, device=x.device)
     sd = torch.zeros((N, ncol, 2, nsd), device=x.device)
     for c in range(ncol):
@@ -70,7 +65,7 @@ def _run(cfg):
             phys.qpos.copy_(x[:, c, sg, :nq])
             phys.qvel.copy_(x[:, c, sg, nq:nq + nv])
             phys.step(x[:, c, sg, nq + nv:].contiguous(), ns)
-            bad += (_bits(phys.qpos) != _bits(y[:, c, sg, :nq])).any().long() + (_bits(phys.qvel) != _bits(y[:, c, sg, nq:])).any().long()
+            bad += (bits(phys.qpos) != bits(y[:, c, sg, :nq])).any().long() + (bits(phys.qvel) != bits(y[:, c, sg, nq:])).any().long()
             if nsd:
                 sd[:, c, sg] = phys.sensordata
     ncon = phys.contacts()["ncon"].cpu().numpy()                    # of the last replayed run's last pass
@@ -233,9 +228,9 @@ def test_against_the_oracle_at_the_same_eps(oracle_mod, kind):
     import torch
     from rsr_mjx_amd.physics import Physics
     n = 16
-    envdef, E, _, _ = _make(kind, n, False)
+    envdef, E, _, _ = make(kind, n, False)
     E.reset(prng.split(prng.PRNGKey(1), n))
-    qpos, qvel, ctrl = _free_states(envdef, kind, n, 31)
+    qpos, qvel, ctrl = free_states(envdef, kind, n, 31)
     phys = Physics(E)
     phys.set_state(qpos=qpos, qvel=qvel, ctrl=ctrl)
     phys.transition_fd(nsteps=1, eps=EPS)
@@ -270,16 +265,16 @@ def test_against_the_oracle_at_the_same_eps(oracle_mod, kind):
             J[:, :nv, c] = _differentiate_pos(A, nv, ends[0][0], ends[1][0]) / (2 * EPS)
             J[:, nv:, c] = (ends[0][1] - ends[1][1]) / (2 * EPS)
         ref[prec] = J
-    print(kind, "fd [A B]: max |entry| %.3e, hip to the f32 oracle: max rel %.2e" % (np.abs(ref["f64"]).max(), _rel(hip, ref["f32"]).max()))
+    print(kind, "fd [A B]: max |entry| %.3e, hip to the f32 oracle: max rel %.2e" % (np.abs(ref["f64"]).max(), rel(hip, ref["f32"]).max()))
     fails = []
-    _rule(kind, "fd [A B]", _rel(hip, ref["f64"]), _rel(ref["f32"], ref["f64"]), fails)
+    rule(kind, "fd [A B]", rel(hip, ref["f64"]), rel(ref["f32"], ref["f64"]), fails)
     assert not fails, fails
 
 
 @pytest.mark.gpu
 def test_env_ids_and_no_side_effects():
     """N = 65, a shuffled 7-env subset with envs 0 and 64: the other envs' rows stay bitwise zero, the selected rows equal an
-    all-env call's, the record, side buffer, sensordata, qM and qfrc_constraint are bitwise unchanged, and a following env.step
+    all-env call's, the record and every other buffer of the handle are bitwise unchanged, and a following env.step
     equals that of a batch that never made the call."""
     import torch
     from rsr_mjx_amd.physics import Physics
@@ -294,21 +289,16 @@ def test_env_ids_and_no_side_effects():
         p.dynamics()
         p.constraint_forces()
     assert float(phys.fd_A.abs().max()) == 0.0 and float(phys.fd_C.abs().max()) == 0.0      # zeros until the first call
-    watch = lambda: {**{k: E.view(k).clone() for k in PIPE + ("obs", "info_go2", "first_qpos")},
-                     **{"side_" + k: v.clone() for k, v in phys._side.items()},
-                     "qM": phys.qM.clone(), "qfrc_constraint": phys.qfrc_constraint.clone(), "efc_force": phys.efc_force.clone()}
-    before = watch()
+    before = handle_snapshot(phys, all_but("transition"))
     phys.transition_fd(env_ids=ids, keep_states=True)
-    torch.cuda.synchronize()
-    for k, v in watch().items():
-        assert torch.equal(_bits(v), _bits(before[k])), k
-    cols = phys._fd_view("columns").clone()
-    assert (_bits(cols[others]) == 0).all() and (_bits(phys.fd_x[others]) == 0).all() and (_bits(phys.fd_y[others]) == 0).all()
+    assert_unchanged(before, handle_snapshot(phys, all_but("transition")))
+    cols = handle_views(phys, "transition")["columns"].clone()
+    assert (bits(cols[others]) == 0).all() and (bits(phys.fd_x[others]) == 0).all() and (bits(phys.fd_y[others]) == 0).all()
     assert float(cols[ids].abs().amax(dim=(1, 2)).min()) > 0
     phys.transition_fd()
     torch.cuda.synchronize()
-    full = phys._fd_view("columns")
-    assert torch.equal(_bits(full[ids]), _bits(cols[ids]))
+    full = handle_views(phys, "transition")["columns"]
+    assert torch.equal(bits(full[ids]), bits(cols[ids]))
     assert float(full[others].abs().amax(dim=(1, 2)).min()) > 0
     for bad in ([0, 0], [n], [-1]):
         with pytest.raises(ValueError):
@@ -321,7 +311,7 @@ def test_env_ids_and_no_side_effects():
     F.step(None, act)
     torch.cuda.synchronize()
     for k in PIPE + ("obs", "reward"):
-        assert torch.equal(_bits(E.view(k)), _bits(F.view(k))), k
+        assert torch.equal(bits(E.view(k)), bits(F.view(k))), k
 
 
 @pytest.mark.gpu
@@ -342,7 +332,7 @@ def test_sensor_rows():
     assert np.abs(got).max() > 0.5                                  # the gyro reads the base's angular velocity
     bare = _run(CONFIGS[0])
     assert bare["dims"][4] == 0 and bare["blocks"]["C"].shape == (N, 0, 2 * bare["dims"][1]) and bare["blocks"]["D"].shape == (N, 0, bare["dims"][2])
-    envdef, E, _, _ = _make("go2flat", 4, False)
+    envdef, E, _, _ = make("go2flat", 4, False)
     E.reset(prng.split(prng.PRNGKey(2), 4))
     phys = Physics(E)
     assert phys.fd_C.shape == (4, 0, 2 * nv) and phys.fd_D.shape == (4, 0, nu)
