@@ -8,6 +8,8 @@
  *   rsr_physics_rollout <- mujoco.rollout.rollout / lax.scan(mjx.step): T control steps in one launch, trajectories [N, T, w].
  *   rsr_physics_sample_rollouts <- mujoco.rollout.rollout on K copies of a state / vmap(lax.scan(mjx.step)): K ctrl sequences
  *                          per env from its current state, trajectories [M, K, T, w]; the record is read only.
+ *   rsr_physics_param_rollouts <- the same with the model varied: vmap(lambda leaves: lax.scan(mjx.step)) over K sets of model
+ *                          leaves per env (friction, mass, damping, gains, ...), with no replica batch; the record is read only.
  *   rsr_physics_set_sensors: the site sensors of data.sensordata (RSR_P_SENSORDATA, and a rollout's sensordata rows).
  *   rsr_physics_set_applied / rsr_physics_applied_view: data.xfrc_applied and data.qfrc_applied, per-env inputs of every forward
  *                          pass of these calls (zero until set).
@@ -133,6 +135,33 @@ int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int nsteps, co
  * T nsteps at or above 2^31. */
 int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int K, int T, int nsteps,
                                 const rsr_rollout_out* out, void* hip_stream);
+
+/* Parameter rollouts, for system identification, domain-randomised planning and CEM over model parameters: from the state each
+ * listed env is in now, K sets of model leaves, each run for T control steps, one launch with one wavefront per (env, sample)
+ * and no replica batch.  M = count, or num_envs with env_ids NULL.  Sample (s, k) starts from the record of env e = env_ids[s]
+ * as it stands (qpos, qvel, qacc_warmstart, time), with, while they are on, env e's applied forces (held for all T control
+ * steps), and with env e's leaves except those `params` gives: bit for bit the trajectory rsr_physics_rollout would record on a
+ * batch whose env holds that record row and, as its per-env leaves, row (s, k) of every given leaf.
+ * Per-sample model leaves: device float32 [M, K, width], width as rsr_batch_set_dr_field, indexed by enum rsr_dr_field;
+ * a NULL member = the env's own leaf (its per-env value, or the model's).  params may be NULL or all-NULL: every sample then
+ * runs the env's own leaves, and with RSR_PR_CTRL_PER_SAMPLE the call is rsr_physics_sample_rollouts.
+ * ctrl: device float32 [M, T, nu], one sequence shared by the K samples of a slot (one logged control sequence), or with
+ * RSR_PR_CTRL_PER_SAMPLE [M, K, T, nu].  out: the non-NULL members are [M, K, T, width], the fields and their meaning per
+ * control step as for rsr_physics_rollout; rows, of ctrl, params and out alike, are indexed by slot s, the position in env_ids,
+ * not by env id.  Only the buffers of out are written: the record (the K samples of an env share its row, read only), the side
+ * buffer, RSR_P_SENSORDATA, the dynamics, constraint, transition and inverse buffers and the batch's own leaf tensors
+ * (rsr_batch_set_dr / rsr_batch_set_dr_field) are untouched, and no PRNG key advances; the handle owns no buffer for this call.
+ * A member of out holds 4 M K T width bytes: record only what the loss reads.
+ * env_ids: device int32 [count], or NULL for every env (count is ignored); an id outside [0, num_envs) runs nothing and its
+ * slot's rows are left alone.  Checked before any device work.  RSR_ERR_ARG: null handle, null ctrl, null out or an out with all
+ * six members NULL, K < 1, T < 1, nsteps < 1, unknown flag bits, env_ids with count < 1, sensordata requested with no sensor
+ * table set, M K or T nsteps at or above 2^31.  RSR_ERR_UNSUPPORTED: a non-NULL member among the last five leaves
+ * (RSR_DR_BODY_IPOS ..) on a model whose kernels lack them (the Airbot ones), as rsr_batch_set_dr_field. */
+typedef struct rsr_param_samples { const float* leaf[RSR_DR_COUNT]; } rsr_param_samples;
+#define RSR_PR_CTRL_PER_SAMPLE 1     /* ctrl is [M, K, T, nu]; without it [M, T, nu], shared by a slot's K samples */
+int rsr_physics_param_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl,
+                               const rsr_param_samples* params, int K, int T, int nsteps, int flags,
+                               const rsr_rollout_out* out, void* hip_stream);
 
 /* Applied forces (MuJoCo's data.xfrc_applied / data.qfrc_applied): per-env state of the handle, added in every forward pass of
  * rsr_physics_step (each substep), _forward, _forward_envs and _rollout (each substep, held for all T control steps):

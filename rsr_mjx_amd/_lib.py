@@ -44,7 +44,7 @@ PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step",
                 "rsr_physics_view", "rsr_physics_set_sensors", "rsr_physics_rollout", "rsr_physics_set_applied",
                 "rsr_physics_applied_view", "rsr_physics_set_jac_sites", "rsr_physics_dynamics", "rsr_physics_dynamics_view",
                 "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
-                "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts"]
+                "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -75,6 +75,15 @@ MAX_SENSORDATA = 64
 class RolloutOut(C.Structure):
     """struct rsr_rollout_out (include/rsr_physics.h): device pointers, NULL = not recorded."""
     _fields_ = [(n, C.c_void_p) for n in ("qpos", "qvel", "time", "actuator_force", "ncon", "sensordata")]
+
+
+class ParamSamples(C.Structure):
+    """struct rsr_param_samples (include/rsr_physics.h): device pointers [M, K, width] in DR_FIELDS order, NULL = the env's own leaf."""
+    _fields_ = [("leaf", C.c_void_p * len(DR_FIELDS))]
+
+
+# the RSR_PR_* flags (include/rsr_physics.h)
+PR_CTRL_PER_SAMPLE = 1
 
 SYMBOLS = [
     "rsr_model_create", "rsr_model_dims", "rsr_model_destroy", "rsr_batch_create", "rsr_batch_destroy",
@@ -130,6 +139,7 @@ def lib() -> C.CDLL:
     L.rsr_physics_inverse.argtypes = [vp, vp, vp, i32, i32, vp]
     L.rsr_physics_inverse_view.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p]
     L.rsr_physics_sample_rollouts.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp]
+    L.rsr_physics_param_rollouts.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

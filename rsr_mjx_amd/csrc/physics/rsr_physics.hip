@@ -2,12 +2,14 @@
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse) and sampled rollouts (rsr_physics_sample_rollouts).  The kernels are in the family units (physics/rsr_physics_kernels.hpp).
+// Parameter rollouts (rsr_physics_param_rollouts) launch through the sweep units (physics/rsr_sweep_launch.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
 #include "../rsr_host.hpp"
+#include "rsr_sweep_launch.hpp"
 
 // The side buffer belongs to a handle of its own, on a batch it borrows.
 struct rsr_physics {
@@ -220,6 +222,47 @@ extern "C" int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_id
   x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
   x.ph.K = K;
   return counted(p, physics_launch(p, rsr::OP_PHYS_SAMPLE, x, "rsr_physics_sample_rollouts"));
+}
+
+// Parameter rollouts: an op in all but the enum (rsr_sweep_launch.hpp).  The sweep unit of the model's family launches; a launch
+// error is reported as physics_launch reports one.
+static int sweep_launch(rsr_physics* ph, const rsr::Launch& x, const rsr::SweepArgs& sw, const char* who) {
+  HIPCHK(hipSetDevice(ph->b->device));
+  switch (ph->b->model->spec->family) {
+    case rsr::FAMILY_CUBE: rsr::launch_sweep_cube(x, sw); break;
+    case rsr::FAMILY_TSHAPE: rsr::launch_sweep_tshape(x, sw); break;
+    case rsr::FAMILY_GO2: rsr::launch_sweep_go2(x, sw); break;
+  }
+  { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
+  return RSR_OK;
+}
+
+extern "C" int rsr_physics_param_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, const rsr_param_samples* params,
+                                          int K, int T, int nsteps, int flags, const rsr_rollout_out* out, void* hip_stream) {
+  const char* who = "rsr_physics_param_rollouts";
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: null handle");
+  if (!ctrl) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: null ctrl");
+  if (!out || !(out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata))
+    return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: null out, or nothing to record");
+  if (K < 1 || T < 1 || nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: K, T and nsteps must be >= 1");
+  if (flags & ~RSR_PR_CTRL_PER_SAMPLE) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: unknown flag bits");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, who, &n)) return rc;
+  if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: sensordata requested with no sensor table set");
+  const int64_t grid = (int64_t)n * K;           // one wave per (slot, sample)
+  if (grid > INT32_MAX || (int64_t)T * nsteps > INT32_MAX)
+    return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: envs x K and T x nsteps must stay below 2^31");
+  rsr::SweepArgs sw{};
+  sw.K = K;
+  sw.ctrl_per_sample = (flags & RSR_PR_CTRL_PER_SAMPLE) != 0;
+  for (int f = 0; params && f < RSR_DR_COUNT; ++f) {
+    if (params->leaf[f] && f >= RSR_DR_BODY_IPOS && p->b->model->spec->family != rsr::FAMILY_GO2)
+      return fail(RSR_ERR_UNSUPPORTED, "rsr_physics_param_rollouts: this leaf is per-env only in the Go2 kernels (rsr_batch_set_dr_field); the Airbot kernels take the first four");
+    sw.leaf[f] = params->leaf[f];
+  }
+  rsr::Launch x = physics_args(p, nullptr, env_ids, (int)grid, nsteps, hip_stream);
+  x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
+  return counted(p, sweep_launch(p, x, sw, who));
 }
 
 // the applied-force buffers, on first use: both or neither

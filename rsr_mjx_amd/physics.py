@@ -6,6 +6,10 @@
     mujoco.rollout on K copies of a state / vmap(lax.scan(mjx.step)) ->  Physics.sample_rollouts(ctrl [M, K, T, nu])
                                                                                           (K sequences per env from its current
                                                                                            state, [M, K, T, w]; the record stays)
+    vmap over model leaves of lax.scan(mjx.step) ->  Physics.param_rollouts(ctrl [M, T, nu], {leaf: [M, K, ...]})
+                                                                                          (K sets of model leaves per env from its
+                                                                                           current state, [M, K, T, w]; no replica
+                                                                                           batch, the record and the leaves stay)
     mjx_env.get_sensor_data(model, data, name)  ->  Physics.sensor(name)                 (site sensors, Physics.set_sensors)
     data.replace(xfrc_applied=..., qfrc_applied=...) ->  Physics.set_applied(xfrc, qfrc)  (held by every later step / forward /
                                                                                            rollout, like a Data field)
@@ -91,6 +95,7 @@ class Physics:
         self._inv: Optional[Dict[str, Any]] = None
         self._qacc_in = None                       # the accelerations of inverse()'s last launch
         self._sample_ctrl_in = None                # the control sequences of sample_rollouts()'s last launch
+        self._param_in = None                      # the control sequences and leaf tensors of param_rollouts()'s last launch
         # the env-id tensor of each entry point's last launch (_call_envs)
         self._ids_in: Dict[str, Any] = {}
         if sensors is not None:
@@ -482,6 +487,88 @@ class Physics:
         self._sample_ctrl_in = c                   # kept alive until the next call (the launch is asynchronous)
         self._call_envs("rsr_physics_sample_rollouts", "sample_rollouts", ids, C.c_void_p(c.data_ptr()), K, T, nsteps, C.byref(ptrs),
                         checked=True)
+        return res
+
+    def _leaf_shapes(self) -> Dict[str, tuple]:
+        """per-env shape of each leaf of _lib.DR_FIELDS (BatchedEnv.set_randomization)"""
+        d = self.dims
+        return dict(geom_friction=(d.ngeom, 3), body_mass=(d.nbody,), dof_damping=(d.nv,), dof_frictionloss=(d.nv,),
+                    body_ipos=(d.nbody, 3), qpos0=(d.nq,), dof_armature=(d.nv,), actuator_gainprm=(d.nu, 3), actuator_biasprm=(d.nu, 3))
+
+    def param_rollouts(self, ctrl, params, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), env_ids=None,
+                       out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """What system identification, domain-randomised planning and CEM over model parameters ask: from the state each env is
+        in now, K sets of model leaves, each run for T control steps, one launch with one wave per (env, sample) and no replica
+        batch.  `params` is {leaf name: contiguous float32 tensor [M, K, ...] on the env's device}: the names and shapes of
+        BatchedEnv.set_randomization with K after the env dim, e.g. geom_friction [M, K, ngeom, 3], body_mass [M, K, nbody],
+        dof_damping [M, K, nv], actuator_gainprm [M, K, nu, 3] (the last five of _lib.DR_FIELDS on the Go2 models only); a leaf
+        that is not given stays the env's own (its per-env value, or the model's).  M = len(env_ids) (default: every env).
+        ctrl is a float32 tensor [M, T, nu], one sequence shared by an env's K samples (one logged control sequence), or
+        [M, K, T, nu]; K comes from `params`, or from a 4-D ctrl when `params` is empty, and the two must agree.  Sample (s, k)
+        starts from the record of env env_ids[s] as it stands (qpos, qvel, qacc_warmstart, time) with that env's applied forces:
+        bit for bit the trajectory rollout() records on a batch whose env holds that record row and, through set_randomization,
+        row (s, k) of every given leaf.  With no params and a 4-D ctrl this is sample_rollouts.  Returns {field: [M, K, T, w]} for
+        `fields` (ROLLOUT_FIELDS, as rollout), rows in env_ids order.  `out`: caller-owned float32 tensors to fill instead of new
+        ones.  Writes nothing else: the record, the side buffer, sensordata, every other buffer of the handle and the batch's own
+        leaf tensors stay as they are.  A field takes 4 * M * K * T * w bytes: ask for what the loss reads."""
+        import torch
+        from .envs import config as cfg
+        nsteps = self.n_substeps if nsteps is None else int(nsteps)
+        if nsteps < 1:
+            raise ValueError(f"param_rollouts: nsteps must be >= 1, got {nsteps}")
+        ids = None if env_ids is None else self._ids(env_ids, "param_rollouts")
+        M, nu, dev = self.num_envs if ids is None else int(ids.numel()), self.dims.nu, self.qvel.device
+        if not torch.is_tensor(ctrl) or ctrl.dtype != torch.float32 or ctrl.dim() not in (3, 4) or ctrl.shape[0] != M or ctrl.shape[-1] != nu \
+                or min(ctrl.shape[1:-1]) < 1 or ctrl.device != dev:
+            raise ValueError(f"param_rollouts expects ctrl as a float32 tensor of shape ({M}, T >= 1, {nu}) or ({M}, K >= 1, T >= 1, {nu}) on {dev}")
+        per_sample = ctrl.dim() == 4
+        T, K = int(ctrl.shape[-2]), int(ctrl.shape[1]) if per_sample else None
+        params = dict(params or {})
+        unknown = sorted(set(params) - set(_lib.DR_FIELDS))
+        if unknown:
+            raise ValueError(f"param_rollouts: not a model leaf: {unknown}; leaves: {_lib.DR_FIELDS}")
+        shapes = self._leaf_shapes()
+        ps, leaves = _lib.ParamSamples(), []
+        for fid, name in enumerate(_lib.DR_FIELDS):
+            t = params.get(name)
+            if t is None:
+                continue
+            if fid >= _lib.DR_FIELDS.index("body_ipos") and int(self.dims.env_kind) not in (cfg.ENV_GO2, cfg.ENV_GO2_HANDSTAND):
+                raise ValueError(f"param_rollouts: {name} is a per-sample leaf on the Go2 models only")
+            want = f"({M}, K >= 1, {', '.join(str(int(w)) for w in shapes[name])})"
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 + len(shapes[name]) or t.shape[0] != M or t.shape[1] < 1 \
+                    or tuple(t.shape[2:]) != tuple(int(w) for w in shapes[name]) or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"param_rollouts: params[{name!r}] must be a contiguous float32 tensor of shape {want} on {dev}")
+            if K is not None and int(t.shape[1]) != K:
+                raise ValueError(f"param_rollouts: params[{name!r}] has K = {int(t.shape[1])}, the others (or ctrl) K = {K}")
+            K = int(t.shape[1])
+            ps.leaf[fid] = t.data_ptr()
+            leaves.append(t)
+        if K is None:
+            raise ValueError("param_rollouts: K is not given: pass sampled leaves in params, or a 4-D ctrl [M, K, T, nu]")
+        fields = tuple(fields)
+        bad = [f for f in fields if f not in ROLLOUT_FIELDS]
+        if bad or not fields:
+            raise ValueError(f"param_rollouts: unknown or no fields {bad}; recordable: {ROLLOUT_FIELDS}")
+        if "sensordata" in fields and self.nsensordata == 0:
+            raise ValueError("param_rollouts: sensordata requested but no sensors are set (set_sensors)")
+        d = self.dims
+        width = dict(qpos=d.nq, qvel=d.nv, time=1, actuator_force=d.nu, ncon=1, sensordata=self.nsensordata)
+        res, ptrs = {}, _lib.RolloutOut()
+        out = out or {}
+        for f in fields:
+            shape = (M, K, T, width[f])
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=torch.float32, device=ctrl.device)
+            elif (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != ctrl.device):
+                raise ValueError(f"param_rollouts: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {ctrl.device}")
+            res[f] = t
+            setattr(ptrs, f, t.data_ptr())
+        c = ctrl.contiguous()
+        self._param_in = (c, leaves)               # kept alive until the next call (the launch is asynchronous)
+        self._call_envs("rsr_physics_param_rollouts", "param_rollouts", ids, C.c_void_p(c.data_ptr()), C.byref(ps), K, T, nsteps,
+                        _lib.PR_CTRL_PER_SAMPLE if per_sample else 0, C.byref(ptrs), checked=True)
         return res
 
     def forward(self) -> None:

@@ -8,6 +8,10 @@ the friction of the model's LAST geom set to p.  A ctypes stepper is not differe
 need to be: every data point is replicated once per perturbed parameter value (p, p +- eps e_k) in ONE batch, so a
 central-difference gradient costs a single `rsr_step` launch per optimiser step.
 
+`RolloutLoss` is the same idea without the replica batch, on the physics layer: Physics.param_rollouts runs every data point
+under every candidate parameter value from the record as it stands, so nothing is replicated and nothing is copied back between
+evaluations.  It scores trajectories of a physics field, not observations (see its docstring).
+
 Data format (README.md:333-357 of the reference): text files with one comma-separated row of floats per line.
 """
 from __future__ import annotations
@@ -102,6 +106,55 @@ class _StepLoss:
         self.env.step(self.state, self.actions)
         err = (self.env.view("obs") - self.target) @ self.w              # jnp.dot(w, error), then |.|
         return err.abs().view(self.nd, self.nvar).sum(0).cpu().numpy()
+
+
+class RolloutLoss:
+    """Trajectory loss of M envs for many parameter values at once, on Physics.param_rollouts: callable as
+    loss_many(P [nvar, nparam]) -> [nvar], which is what adam_fd_minimise takes.
+
+    phys: a Physics handle whose envs (env_ids, default all: M of them) stand at the states the logged trajectories start from.
+    ctrl: float32 tensor [M, T, nu] on the env's device, the logged control sequence of each env, shared by all variants.
+    target: [M, T, w], the logged trajectory of `field` (one of physics.ROLLOUT_FIELDS, e.g. "qpos" or "sensordata").
+    make_leaves(P) -> {leaf name: [nvar, ...]}: the model leaves of each row of P, names and per-env shapes as
+    BatchedEnv.set_randomization (numpy or torch); leaves it does not return stay each env's own.
+    weights: [w], default ones.
+
+    A call broadcasts the leaves over the M envs, runs param_rollouts once (M * nvar waves, shared ctrl, `field` alone recorded) and
+    returns, per variant, the sum over envs, control steps and columns of |weights[c] * (traj[e, v, t, c] - target[e, t, c])|.
+    The record is read only, so every call starts from the same states: nothing is restored between calls.
+
+    This is not the loss of env_params_tuning.  The reference's loss is in observation space, and an observation is made by the
+    env's epilogue (obs, reward, done: the env kernels), which the physics layer does not run; env_params_tuning and _StepLoss keep
+    that loss on a replica batch.  Use this one where the log holds physics quantities: joint positions, velocities, sensors."""
+
+    def __init__(self, phys, ctrl, target, field: str, make_leaves: Callable[[np.ndarray], Dict[str, Any]], weights=None, env_ids=None):
+        import torch
+        self.torch = torch
+        self.phys, self.ctrl, self.field, self.make_leaves, self.env_ids = phys, ctrl, field, make_leaves, env_ids
+        dev = ctrl.device
+        self.target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target, dtype=torch.float32).to(dev)
+        M, T = int(ctrl.shape[0]), int(ctrl.shape[1])
+        if self.target.dim() != 3 or tuple(self.target.shape[:2]) != (M, T):
+            raise ValueError(f"RolloutLoss expects target of shape ({M}, {T}, w), got {tuple(self.target.shape)}")
+        w = self.target.shape[2]
+        self.w = torch.ones(w, dtype=torch.float32, device=dev) if weights is None else \
+            torch.as_tensor(np.asarray(weights, dtype=np.float32), device=dev)
+        if tuple(self.w.shape) != (w,):
+            raise ValueError(f"RolloutLoss expects weights of shape ({w},), got {tuple(self.w.shape)}")
+
+    def __call__(self, P: np.ndarray) -> np.ndarray:
+        torch = self.torch
+        P = np.atleast_2d(np.asarray(P))
+        nvar, M = P.shape[0], int(self.ctrl.shape[0])
+        leaves = {}
+        for name, v in self.make_leaves(P).items():
+            t = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v, dtype=torch.float32).to(self.ctrl.device)
+            if t.shape[0] != nvar:
+                raise ValueError(f"RolloutLoss: make_leaves gave {name} for {t.shape[0]} variants, P has {nvar}")
+            leaves[name] = t[None].expand((M,) + tuple(t.shape)).contiguous()      # [M, nvar, ...]: every env tries every variant
+        traj = self.phys.param_rollouts(self.ctrl, leaves, fields=(self.field,), env_ids=self.env_ids)[self.field]
+        err = (traj - self.target[:, None]) * self.w                     # [M, nvar, T, w]
+        return err.abs().double().sum(dim=(0, 2, 3)).cpu().numpy()
 
 
 def env_params_tuning(init_env, num_steps: int, init_env_params, env_params_min, env_params_max, obs, actions, next_obs_true,

@@ -1,0 +1,288 @@
+"""Parameter rollouts of the physics layer (rsr_physics_param_rollouts, Physics.param_rollouts, tuning.RolloutLoss), host side
+only: the ABI, the sweep units and their dispatch beside the pinned ops, the Python surface and the tuning helper's reduction.
+The kernel is covered by tests/test_param_rollouts_gpu.py."""
+import ctypes as C
+import inspect
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
+SIG = ("int rsr_physics_param_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, "
+       "const rsr_param_samples* params, int K, int T, int nsteps, int flags, const rsr_rollout_out* out, void* hip_stream);")
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+
+
+def _read(*parts):
+    return open(os.path.join(CSRC, *parts)).read()
+
+
+def test_header_declares_the_call_and_the_struct():
+    h = _header()
+    flat = re.sub(r"\s+", " ", h)
+    assert SIG in flat                                             # (the declaration may break its lines)
+    assert "typedef struct rsr_param_samples { const float* leaf[RSR_DR_COUNT]; } rsr_param_samples;" in flat
+    assert re.search(r"#define RSR_PR_CTRL_PER_SAMPLE 1\b", h)
+    doc = h[h.index("/* Parameter rollouts"):h.index("typedef struct rsr_param_samples")]
+    for word in ("[M, K, width]", "[M, T, nu]", "[M, K, T, nu]", "[M, K, T, width]", "bit for bit", "qacc_warmstart",
+                 "position in env_ids", "untouched", "own leaf tensors", "no PRNG key advances", "left alone", "before any device work",
+                 "2^31", "RSR_ERR_UNSUPPORTED", "unknown flag bits", "rsr_physics_sample_rollouts", "owns no buffer"):
+        assert word in doc, word
+    assert h.count("typedef struct rsr_rollout_out") == 1          # the existing struct, not a second one
+    assert "rsr_param" not in open(os.path.join(ROOT, "include", "rsr_mjx.h")).read()
+
+
+def test_library_exports_and_null_handle():
+    from rsr_mjx_amd import _lib
+    L = _lib.lib()
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert "rsr_physics_param_rollouts" in _lib.PHYS_SYMBOLS
+    fn = L.rsr_physics_param_rollouts
+    assert fn.argtypes is not None and len(fn.argtypes) == 11
+    assert _lib.PR_CTRL_PER_SAMPLE == 1
+    ps = _lib.ParamSamples()
+    assert C.sizeof(ps) == len(_lib.DR_FIELDS) * C.sizeof(C.c_void_p) and len(ps.leaf) == 9 and not any(ps.leaf)
+    ids = (C.c_int32 * 2)(0, 1)
+    ctrl = (C.c_float * 8)()
+    o = _lib.RolloutOut()
+    for table, k in ((None, 0), (ids, 2), (ids, 0)):
+        for params in (None, C.byref(ps)):
+            assert fn(None, table, k, ctrl, params, 1, 1, 1, 0, C.byref(o), None) == -1
+            assert b"null handle" in L.rsr_last_error()
+
+
+def _body(src, name):
+    b = src[src.index(name + "("):]
+    return b[:b.index("\n}\n")]
+
+
+def test_refusals_come_before_device_work():
+    """Every refusal comes ahead of every device call (by source order, as a handle needs a device), and the call allocates
+    nothing: the handle owns no buffer for it."""
+    src = _read("physics", "rsr_physics.hip")
+    call = _body(src, "int rsr_physics_param_rollouts")
+    dev = ("hipSetDevice", "hipMalloc", "hipMemset", "hipMemcpy", "zeroed_once", "launch(")
+    first_dev = min(call.index(k) for k in dev if k in call)
+    assert first_dev == call.index("sweep_launch(") + len("sweep_")
+    checks = ("!p)", "!ctrl)", "!out ||", "out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata)",
+              "K < 1", "T < 1", "nsteps < 1", "flags & ~RSR_PR_CTRL_PER_SAMPLE", "env_count(", "out->sensordata && p->nsd == 0",
+              "grid > INT32_MAX", "(int64_t)T * nsteps > INT32_MAX", "RSR_ERR_UNSUPPORTED", "f >= RSR_DR_BODY_IPOS")
+    at = [call.index(c) for c in checks]
+    assert all(i < first_dev for i in at), [c for c, i in zip(checks, at) if i >= first_dev]
+    assert "(int64_t)n * K" in call and call.count("RSR_ERR_ARG") == 7 and call.count("RSR_ERR_UNSUPPORTED") == 1
+    for k in ("hipMalloc", "hipMemset", "hipMemcpy", "hipFree", "zeroed_once", "_buffer", "new ", "std::vector", "OP_PHYS_"):
+        assert k not in call, k
+    assert "_alloc" not in src and src.count("static int zeroed_once(") == 1
+    assert call.index("physics_args(") < call.index("x.ph.r = rsr::RollArgs{ctrl, T, ") < call.index("sweep_launch(")
+
+
+def test_the_launch_has_units_of_its_own_beside_the_pinned_ops():
+    from rsr_mjx_amd import build
+    units = dict(build.UNITS)
+    assert len(build.UNITS) == 8 and len(units) == 8
+    for fam, src in (("cube", "rsr_cube.hip"), ("tshape", "rsr_tshape.hip"), ("go2", "rsr_go2.hip")):
+        sweep = os.path.join("physics", f"rsr_sweep_{fam}.hip")
+        assert units[sweep] == units[src], fam                     # the family unit's flags: the bit-identity tests compare across them
+        text = _read(sweep)
+        assert '#include "rsr_sweep.hpp"' in text and re.findall(r"\bint (launch_\w+)\(", text.replace("static int", "")) == [f"launch_sweep_{fam}"]
+        assert "sizeof(Smem<C>)" in text and "sweep_kernel<C, " in text and "Applied>" in text
+        assert re.findall(r"\b(\w+_kernel)\b", re.sub(r"//.*", "", text)) == ["sweep_kernel"] * 2, fam
+    assert units[os.path.join("physics", "rsr_sweep_tshape.hip")] == ["-fno-slp-vectorize"] == units[os.path.join("physics", "rsr_sweep_go2.hip")]
+    # the same WAVES and the same Dims pick as the family units
+    pick = lambda text: re.findall(r"<(\w+Dims), (RSR_\w+)>", text)
+    assert pick(_read("physics", "rsr_sweep_go2.hip")) == pick(_read("rsr_go2.hip"))
+    assert "x.env_kind == ENV_GO2_HANDSTAND" in _read("physics", "rsr_sweep_go2.hip") and "if (x.hfield)" in _read("physics", "rsr_sweep_go2.hip")
+    for fam in ("cube", "tshape"):
+        assert "RSR_WAVES_PER_EU" in _read("physics", f"rsr_sweep_{fam}.hip") and "launch_physics<C, RSR_WAVES_PER_EU>" in _read(f"rsr_{fam}.hip")
+    # the arguments and the three prototypes: a header of their own, not the pinned ones
+    hdr = _read("physics", "rsr_sweep_launch.hpp")
+    assert "struct SweepArgs" in hdr and "const float* leaf[RSR_DR_COUNT];" in hdr
+    assert re.findall(r"\bint (launch_sweep_\w+)\(const Launch& x, const SweepArgs& sw\);", hdr) == ["launch_sweep_cube", "launch_sweep_tshape", "launch_sweep_go2"]
+    for pinned in ("rsr_physics.hpp", "rsr_physics_kernels.hpp", "rsr_sample.hpp"):
+        text = _read("physics", pinned)
+        assert "sweep" not in text.lower() and "SweepArgs" not in text, pinned
+    # the host picks the unit by the model's family, in one place
+    host = _read("physics", "rsr_physics.hip")
+    pickfn = _body(host, "static int sweep_launch")
+    assert "p->b->model->spec->family" in pickfn.replace("ph->", "p->") and host.count("launch_sweep_") == 3 and pickfn.count("launch_sweep_") == 3
+    assert "hipGetLastError()" in pickfn and "RSR_ERR_HIP" in pickfn
+    # nothing directly under csrc/ knows; the hashed sources are the parent's
+    for f in os.listdir(CSRC):
+        if f.endswith((".hip", ".hpp")):
+            text = open(os.path.join(CSRC, f)).read()
+            assert "sweep_kernel" not in text and "rsr_sweep" not in text and "SweepArgs" not in text, f
+    import bench
+    import parity_envelopes as PE
+    assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
+    enum = re.sub(r"//.*", "", re.search(r"enum PhysOp \{(.*?)\};", _read("physics", "rsr_physics.hpp"), re.S).group(1))
+    assert len(re.findall(r"\bOP_PHYS_\w+", enum)) == 8
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    sec = design[design.index("### 4j."):]
+    assert "op in all but the enum" in sec and "PhysOp" in sec
+
+
+def test_the_kernel_is_the_sample_loop_with_one_stage_more():
+    kern = _read("physics", "rsr_sweep.hpp")
+    assert "void sweep_kernel(" in kern and "void overlay_leaves(" in kern
+    code = re.sub(r"//.*", "", kern)
+    assert code.count("forward<C>(") == 1 and code.count("integrate<C>(") == 1
+    for k in ("sensor_stage<C>(", "force_stage<C>(e, ", "load_overrides<C>(m, s, a, e, lane)", "overlay_leaves<C>(m, s, sw, b, lane)",
+              "lrec_lane(lane)", "if constexpr (C::XFRC)"):
+        assert k in code, k
+    assert code.index("load_overrides<C>(m, s, a, e, lane)") < code.index("overlay_leaves<C>(m, s, sw, b, lane)") < code.index("forward<C>(")
+    for k in ("store_pipeline", "store_side", "asm", "atomic"):
+        assert k not in kern, k
+    # the record is read only, and neither the side buffer nor the sensordata row is written
+    assert "const float* rec = a.state + (size_t)e * L.rec;" in code and not re.search(r"(?<!const )float\* rec\b", code)
+    assert not re.search(r"\brec\[[^\]]*\]\s*=[^=]", code) and "p.sd" not in code and "p.out" not in code
+    # one flattened loop, rows by workgroup and ctrl by slot or workgroup, in size_t
+    assert len(re.findall(r"\bfor \(int k = 0; k < total; \+\+k\)", code)) == 1 and "const int total = r.T * p.nsteps;" in code
+    assert "const size_t cb = sw.ctrl_per_sample ? (size_t)b : (size_t)slot;" in code and "const size_t row = (size_t)b * r.T + t;" in code
+    assert "slot = b / K" in code and "p.ids ? p.ids[slot] : slot" in code and "if (e < 0 || e >= a.n) return;" in code
+    # the overlay: all nine images, rows in size_t, friction through the geom slots, every load ahead of the first store
+    ov = code[code.index("void overlay_leaves("):code.index("void sweep_kernel(")]
+    for img in ("s.fric[", "s.mass[", "s.damp[", "s.floss[", "s.dx_ipos[", "s.dx_qpos0[", "s.dx_arma[", "s.dx_gain[", "s.dx_bias["):
+        assert ov.count(img) == 1, img
+    assert "(size_t)b * width" in ov and "m.geom_slot_ids[tt / 3]" in ov and "C::NGA == C::NG" in ov and "WSYNC" not in ov
+    first_store = min(m.start() for m in re.finditer(r"\bs\.\w+\[[^\]]*\] = ", ov))
+    last_load = max(m.start() for m in re.finditer(r"= p_\w+\[", ov))
+    assert last_load < first_store
+    # the statements the two kernels share are the same text
+    sample = re.sub(r"//.*", "", _read("physics", "rsr_sample.hpp"))
+    body = lambda c, name: [ln.strip() for ln in c[c.index(f"void {name}("):].splitlines() if ln.strip()]
+    sw, sa = body(code, "sweep_kernel"), body(sample, "sample_kernel")
+    extra = [ln for ln in sw if ln not in sa]
+    assert len(extra) <= 8, extra                                   # the signature, K, the overlay, cb and the two ctrl loads
+    assert [ln for ln in sa if ln not in sw and "r.ctrl[" not in ln and "sample_kernel" not in ln and "slot = b / K" not in ln] == []
+
+
+def test_physics_module_surface():
+    import torch
+    from rsr_mjx_amd import physics
+    from rsr_mjx_amd.physics import Physics
+    sig = inspect.signature(Physics.param_rollouts)
+    assert list(sig.parameters) == ["self", "ctrl", "params", "nsteps", "fields", "env_ids", "out"]
+    d = {k: v.default for k, v in sig.parameters.items() if k not in ("self", "ctrl", "params")}
+    assert d == dict(nsteps=None, fields=("qpos", "qvel", "time"), env_ids=None, out=None)
+    assert "Physics.param_rollouts(ctrl [M, T, nu], {leaf: [M, K, ...]})" in physics.__doc__
+    assert "4 * M * K * T * w bytes" in Physics.param_rollouts.__doc__
+    src = inspect.getsource(Physics.param_rollouts)
+    assert 'self._call_envs("rsr_physics_param_rollouts", "param_rollouts", ' in src and "_lib.lib()" not in src
+    assert src.rindex("raise ValueError") < src.index("self._call_envs(")
+    assert "self._param_in = (c, leaves)" in src
+    # sample_rollouts is as it was
+    assert list(inspect.signature(Physics.sample_rollouts).parameters) == ["self", "ctrl", "nsteps", "fields", "env_ids", "out"]
+    # every bad input is refused before the C call (the stand-in has no handle to call with)
+    p = Physics.__new__(Physics)
+    p._h = None
+    dims = types.SimpleNamespace(nu=3, nq=5, nv=4, n_frames=2, ngeom=6, nbody=3, env_kind=0)          # (kind 0: an Airbot model)
+    p.num_envs, p.dims, p.qvel, p.device = 4, dims, torch.zeros((4, 4)), torch.device("cpu")
+    p.sensordata = torch.zeros((4, 0))                      # no sensors set
+    shared, each = torch.zeros((4, 3, 3)), torch.zeros((4, 2, 3, 3))
+    mass, fric, damp = torch.zeros((4, 2, 3)), torch.zeros((4, 2, 6, 3)), torch.zeros((4, 2, 4))
+    ok = dict(body_mass=mass)
+    cases = [(dict(ctrl=torch.zeros((4, 3)), params=ok), "expects ctrl"),                               # 2-D
+             (dict(ctrl=torch.zeros((4, 3, 2)), params=ok), "expects ctrl"),                            # wrong nu
+             (dict(ctrl=shared.double(), params=ok), "expects ctrl"),                                   # float64
+             (dict(ctrl=torch.zeros((4, 3, 3), device="meta"), params=ok), "expects ctrl"),             # wrong device
+             (dict(ctrl=shared.numpy(), params=ok), "expects ctrl"),
+             (dict(ctrl=shared, params=ok, env_ids=[0, 2]), "expects ctrl"),                            # M != len(env_ids)
+             (dict(ctrl=shared[:3], params=ok), "expects ctrl"),                                        # M != num_envs
+             (dict(ctrl=shared[:2], params=dict(body_mass=mass[:2]), env_ids=[0, 4]), "env_ids must lie in"),
+             (dict(ctrl=shared, params={}), "K is not given"),                                          # nothing says K
+             (dict(ctrl=shared, params=None), "K is not given"),
+             (dict(ctrl=shared, params=dict(mass=mass)), "not a model leaf"),                           # name
+             (dict(ctrl=shared, params=dict(body_mass=torch.zeros((4, 2, 4)))), r"params\['body_mass'\]"),      # shape
+             (dict(ctrl=shared, params=dict(geom_friction=torch.zeros((4, 2, 18)))), r"params\['geom_friction'\]"),
+             (dict(ctrl=shared, params=dict(body_mass=mass[:3])), r"params\['body_mass'\]"),            # M
+             (dict(ctrl=shared, params=dict(body_mass=mass.double())), r"params\['body_mass'\]"),       # dtype
+             (dict(ctrl=shared, params=dict(body_mass=torch.zeros((4, 2, 3), device="meta"))), r"params\['body_mass'\]"),
+             (dict(ctrl=shared, params=dict(body_mass=mass.numpy())), r"params\['body_mass'\]"),
+             (dict(ctrl=shared, params=dict(body_mass=torch.zeros((4, 3, 2)).transpose(1, 2))), r"params\['body_mass'\]"),    # contiguity
+             (dict(ctrl=shared, params=dict(body_mass=mass, dof_damping=torch.zeros((4, 3, 4)))), "K = 3"),      # disagreeing K
+             (dict(ctrl=torch.zeros((4, 5, 3, 3)), params=ok), "K = 2"),                                # ... with a 4-D ctrl
+             (dict(ctrl=shared, params=dict(qpos0=torch.zeros((4, 2, 5)))), "Go2 models only"),
+             (dict(ctrl=shared, params=ok, fields=("qpos", "qacc")), "unknown"),
+             (dict(ctrl=shared, params=ok, fields=()), "no fields"),
+             (dict(ctrl=shared, params=ok, fields=("sensordata",)), "no sensors are set"),
+             (dict(ctrl=shared, params=ok, nsteps=0), "nsteps must be >= 1"),
+             (dict(ctrl=shared, params=ok, out={"qpos": torch.zeros((4, 2, 3, 4))}), "out\\['qpos'\\]"),
+             (dict(ctrl=each, params=dict(geom_friction=fric, dof_damping=damp), out={"qvel": torch.zeros((4, 3, 3, 4))}), "out\\['qvel'\\]")]
+    for kw, msg in cases:
+        with pytest.raises(ValueError, match=msg):
+            p.param_rollouts(**kw)
+
+
+class _FakePhys:
+    """param_rollouts as a known function of the leaves: qpos[e, v, t, c] = (e + 1) * (t + 1) * damping[e, v, c] + c * mass[e, v, 0]"""
+
+    def __init__(self):
+        self.calls = []
+
+    def param_rollouts(self, ctrl, params, nsteps=None, fields=("qpos", "qvel", "time"), env_ids=None, out=None):
+        import torch
+        self.calls.append(dict(ctrl=ctrl, params=params, fields=fields, env_ids=env_ids))
+        M, T = ctrl.shape[0], ctrl.shape[1]
+        damp = params["dof_damping"]
+        assert damp.shape[0] == M and damp.is_contiguous() and damp.dtype == torch.float32
+        mass = params["body_mass"] if "body_mass" in params else torch.zeros((M, damp.shape[1], 1))
+        e = torch.arange(1, M + 1, dtype=torch.float32)[:, None, None, None]
+        t = torch.arange(1, T + 1, dtype=torch.float32)[None, None, :, None]
+        c = torch.arange(damp.shape[2], dtype=torch.float32)[None, None, None, :]
+        return {fields[0]: e * t * damp[:, :, None, :] + c * mass[:, :, None, :1]}
+
+
+def test_rollout_loss_reduces_and_broadcasts():
+    import torch
+    from rsr_mjx_amd import tuning
+    sig = inspect.signature(tuning.RolloutLoss.__init__)
+    assert list(sig.parameters) == ["self", "phys", "ctrl", "target", "field", "make_leaves", "weights", "env_ids"]
+    assert sig.parameters["weights"].default is None and sig.parameters["env_ids"].default is None
+    assert "epilogue" in tuning.RolloutLoss.__doc__ and "observation" in tuning.RolloutLoss.__doc__
+    M, T, w = 3, 4, 2
+    fake = _FakePhys()
+    ctrl = torch.zeros((M, T, 5))
+    truth = np.array([0.7, -0.2])
+    leaves = lambda P: {"dof_damping": np.asarray(P, np.float32), "body_mass": np.ones((len(P), 6), np.float32) * 2.0}
+    e, t = np.arange(1, M + 1)[:, None, None], np.arange(1, T + 1)[None, :, None]
+    at_truth = {f: torch.as_tensor(v)[None].expand((M,) + v.shape).contiguous() for f, v in leaves(truth[None]).items()}
+    target = fake.param_rollouts(ctrl, at_truth, fields=("qpos",))["qpos"][:, 0].numpy()          # the fake's own arithmetic: exact at the truth
+    assert np.allclose(target, e * t * truth[None, None, :] + np.arange(w)[None, None, :] * 2.0, rtol=1e-6)
+    fake.calls.clear()
+    weights = np.array([1.0, 10.0], np.float32)
+    loss = tuning.RolloutLoss(fake, ctrl, target, "qpos", leaves, weights=weights, env_ids=[2, 0, 1])
+    P = np.array([[0.7, -0.2], [0.5, -0.2], [0.7, 0.3], [0.0, 0.0]])
+    got = loss(P)
+    assert got.shape == (4,)
+    # sum over envs, steps and columns of |w_c (traj - target)| = sum_e (e+1) sum_t (t+1) sum_c w_c |p_c - truth_c|
+    want = np.array([e.sum() * t.sum() * float((weights * np.abs(np.float32(row) - np.float32(truth))).sum()) for row in P])
+    assert got[0] == 0.0 and np.allclose(got, want, rtol=1e-5), (got, want)
+    call = fake.calls[-1]
+    assert call["ctrl"] is ctrl and call["fields"] == ("qpos",) and call["env_ids"] == [2, 0, 1]          # one call, shared ctrl
+    for name, per in (("dof_damping", P.astype(np.float32)), ("body_mass", np.full((4, 6), 2.0, np.float32))):
+        leaf = call["params"][name]
+        assert tuple(leaf.shape) == (M,) + per.shape and leaf.is_contiguous()
+        for env in range(M):
+            assert np.array_equal(leaf[env].numpy(), per), name                                           # every env gets every variant
+    assert len(fake.calls) == 1
+    # default weights are ones; a bad target or weight shape is refused
+    plain = tuning.RolloutLoss(fake, ctrl, target, "qpos", leaves)
+    assert np.allclose(plain(P[1:2]), e.sum() * t.sum() * np.abs(np.float32(0.5) - np.float32(0.7)), rtol=1e-5)
+    with pytest.raises(ValueError, match="target"):
+        tuning.RolloutLoss(fake, ctrl, target[:, :3], "qpos", leaves)
+    with pytest.raises(ValueError, match="weights"):
+        tuning.RolloutLoss(fake, ctrl, target, "qpos", leaves, weights=np.ones(3))
+    # it is what adam_fd_minimise takes: 2 k + 1 variants per step, and the parameters move toward the minimum
+    fake.calls.clear()
+    p0 = np.array([0.2, 0.2])
+    p, hist = tuning.adam_fd_minimise(loss, p0, -1.0, 1.0, num_steps=40, lr=0.02)
+    assert len(fake.calls) == 40 and fake.calls[0]["params"]["dof_damping"].shape == (M, 5, 2)
+    assert np.abs(p - truth).sum() < 0.5 * np.abs(p0 - truth).sum() and hist["loss"][-1] < 0.5 * hist["loss"][0]
