@@ -967,7 +967,7 @@ static void collision(const omodel *m, odata *d) {
         break;
       default: n = 0;
     }
-    real includemargin = m->pair_margin[p] - m->pair_gap[p];
+    real includemargin = (real)m->pair_margin[p] - (real)m->pair_gap[p];   /* (the blob's floats, subtracted in `real`) */
     for (int i = 0; i < n; i++) {
       if (g_cull && !(pts[i].dist - includemargin < 0)) continue;
       if (d->ncon >= g_ncon_cap) { d->ncon_overflow++; continue; }
@@ -1043,7 +1043,7 @@ static void make_constraint(const omodel *m, odata *d) {
     for (int i = 0; i < nv; i++) J[i] = 0;
     if (j2 >= 0) J[m->jnt_dofadr[j2]] = -deriv;
     J[m->jnt_dofadr[j1]] = 1;
-    real iw = m->dof_invweight0[m->jnt_dofadr[j1]] + (j2 >= 0 ? m->dof_invweight0[m->jnt_dofadr[j2]] : 0);
+    real iw = (real)m->dof_invweight0[m->jnt_dofadr[j1]] + (j2 >= 0 ? (real)m->dof_invweight0[m->jnt_dofadr[j2]] : 0);
     real sr[2] = {m->eq_solref[2 * e], m->eq_solref[2 * e + 1]}, si[5];
     for (int k = 0; k < 5; k++) si[k] = m->eq_solimp[5 * e + k];
     add_row(m, d, J, pos1 - poly, iw, sr, si, 0);
@@ -1090,7 +1090,7 @@ static void make_constraint(const omodel *m, odata *d) {
         }
         diff[r * nv + i] = sp; diff[(3 + r) * nv + i] = sr_;
       }
-    real t = m->body_invweight0[2 * c->body1] + m->body_invweight0[2 * c->body2];
+    real t = (real)m->body_invweight0[2 * c->body1] + (real)m->body_invweight0[2 * c->body2];
     if (c->condim == 1) {
       for (int i = 0; i < nv; i++) J[i] = active ? diff[i] : 0;
       add_row(m, d, J, pos, t, c->solref, c->solimp, 0);

@@ -38,15 +38,15 @@ def sensor_spec(kind, envdef):
 
 # ---- batches and states
 
-def make(kind, n, dr_on):
-    """(envdef, batched env, dr dict or None, action scale); no Episode / AutoReset wrappers, no Go2 kicks."""
+def make(kind, n, dr_on, variant=None):
+    """(envdef, batched env, dr dict or None, action scale); no Episode / AutoReset wrappers, no Go2 kicks.  variant: a name of
+    tests/model_variants.py, applied to envdef.sys.arrays before the batch (and its blob) is built."""
+    from model_variants import envdef_of
     from rsr_mjx_amd.envs import airbot, go2
+    envdef = envdef_of(kind, variant)
     if kind in ("cube", "tshape"):
-        envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
         dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n)) if dr_on else None
         return envdef, envdef.batched(n, randomization=dr), dr, 1.0
-    name = {"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind]
-    envdef = go2.load(name)
     dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n)) if dr_on else None
     return envdef, envdef.batched(n, randomization=dr), dr, 0.5
 
@@ -70,26 +70,31 @@ def pair(kind, n, seed=3, steps=3):
 _STATES = {}
 
 
+def perturb(A, qpos, qvel, seed):
+    """(qpos, qvel, ctrl) in fp32: the given reset states [n, nq] / [n, nv] with hinge and slide angles moved by N(0, 0.05), qvel by
+    N(0, 0.2), and a ctrl drawn uniformly inside the control range, from default_rng(seed); A: the model's arrays"""
+    n = len(qpos)
+    rng = np.random.default_rng(seed)
+    qpos, qvel = np.asarray(qpos).astype(np.float64), np.asarray(qvel).astype(np.float64)
+    jt, qa = A["jnt_type"], A["jnt_qposadr"]
+    for j in range(len(jt)):
+        if jt[j] in (2, 3):                               # hinge / slide: perturb the angle
+            qpos[:, qa[j]] += rng.normal(scale=0.05, size=n)
+    qvel += rng.normal(scale=0.2, size=qvel.shape)
+    lo, hi = A["actuator_ctrlrange"][:, 0], A["actuator_ctrlrange"][:, 1]
+    ctrl = lo + (hi - lo) * rng.uniform(size=(n, len(lo)))
+    return qpos.astype(np.float32), qvel.astype(np.float32), ctrl.astype(np.float32)
+
+
 def random_states(envdef, kind, n, seed):
-    """Reset distribution of the env plus a perturbation of qpos / qvel, and a random ctrl inside the control range.  Computed once
-    per (kind, n, seed); every call gets copies of its own."""
+    """Reset distribution of the shipped env plus perturb(): a perturbation of qpos / qvel, and a random ctrl inside the control
+    range.  Computed once per (kind, n, seed); every call gets copies of its own."""
     if (kind, n, seed) not in _STATES:
         import torch
         _, E, _, _ = make(kind, n, False)
         E.reset(prng.split(prng.PRNGKey(seed), n))
         torch.cuda.synchronize()
-        rng = np.random.default_rng(seed)
-        qpos = E.view("qpos").cpu().numpy().astype(np.float64)
-        qvel = E.view("qvel").cpu().numpy().astype(np.float64)
-        A = envdef.sys.arrays
-        jt, qa = A["jnt_type"], A["jnt_qposadr"]
-        for j in range(len(jt)):
-            if jt[j] in (2, 3):                               # hinge / slide: perturb the angle
-                qpos[:, qa[j]] += rng.normal(scale=0.05, size=n)
-        qvel += rng.normal(scale=0.2, size=qvel.shape)
-        lo, hi = A["actuator_ctrlrange"][:, 0], A["actuator_ctrlrange"][:, 1]
-        ctrl = lo + (hi - lo) * rng.uniform(size=(n, len(lo)))
-        _STATES[(kind, n, seed)] = (qpos.astype(np.float32), qvel.astype(np.float32), ctrl.astype(np.float32))
+        _STATES[(kind, n, seed)] = perturb(envdef.sys.arrays, E.view("qpos").cpu().numpy(), E.view("qvel").cpu().numpy(), seed)
     return tuple(a.copy() for a in _STATES[(kind, n, seed)])
 
 
@@ -115,11 +120,12 @@ def free_states(envdef, kind, n, seed, zero_vel=False):
     return qpos, qvel, ctrl
 
 
-def setup(kind, n=256, seed=11, sensors=None, zero_floss=False):
+def setup(kind, n=256, seed=11, sensors=None, zero_floss=False, variant=None):
     """(envdef, E, Physics(E, sensors), qpos, qvel, ctrl): a DR-off batch after reset(PRNGKey(1)) and random_states(kind, n, seed),
-    not yet written into it; zero_floss: dof friction loss zeroed through the batch's per-env leaf."""
+    not yet written into it; zero_floss: dof friction loss zeroed through the batch's per-env leaf; variant: see make (the states
+    stay those of the shipped model)."""
     from rsr_mjx_amd.physics import Physics
-    envdef, E, _, _ = make(kind, n, False)
+    envdef, E, _, _ = make(kind, n, False, variant)
     if zero_floss:
         E.set_randomization({"dof_frictionloss": np.zeros((n, E.dims.nv), np.float32)})
     E.reset(prng.split(prng.PRNGKey(1), n))
@@ -215,6 +221,43 @@ def stacked(rows, names):
     return {k: np.stack([np.asarray(r[k], np.float64).reshape(-1) for r in rows]) for k in names}
 
 
+# ---- the row law at a given acceleration (what Physics.inverse evaluates), on the oracle's rows
+
+def row_forces(r, a, dt):
+    """efc_force at acceleration a in arithmetic dt: x = J a - aref; equality rows -D x; friction-loss rows -D x, clamped to
+    +-floss outside |x| < R floss; limit and contact rows -D min(x, 0)"""
+    J, aref, D, R, fl = (r[k].astype(dt) for k in ("efc_J", "efc_aref", "efc_D", "efc_R", "efc_floss"))
+    x = (J @ a.astype(dt) - aref).astype(dt)
+    f = (-D * x).astype(dt)
+    ne, nf = r["ne"], r["nf"]
+    fr = slice(ne, ne + nf)
+    rf = (R[fr] * fl[fr]).astype(dt)
+    f[fr] = np.where(x[fr] <= -rf, fl[fr], np.where(x[fr] >= rf, -fl[fr], f[fr]))
+    f[ne + nf:] = (-D[ne + nf:] * np.minimum(x[ne + nf:], 0)).astype(dt)
+    return f
+
+
+def inverse_ref(r, a, dt, nefc_max):
+    """the four checked outputs at acceleration a from oracle env r, in arithmetic dt"""
+    f = row_forces(r, a, dt)
+    qfc = (r["efc_J"].astype(dt).T @ f).astype(dt)
+    a = a.astype(dt)
+    qfi = ((r["M"].astype(dt) @ a).astype(dt) + r["qfrc_bias"].astype(dt) - r["qfrc_passive"].astype(dt) - qfc).astype(dt)
+    pad = np.zeros(nefc_max, dt)
+    pad[:len(f)] = f
+    return dict(efc_force=pad, qfrc_constraint=qfc, qfrc_actuator=r["qfrc_actuator"].astype(dt), qfrc_inverse=qfi)
+
+
+def inverse_inputs(ref64, seed):
+    """the three accelerations of the inverse parity tests, fp32 [n, nv]: the f64 oracle's own qacc, that plus seeded noise of scale
+    0.3 max(1, |qacc|_inf), zeros"""
+    own = np.stack([r["qacc"] for r in ref64]).astype(np.float32)
+    rng = np.random.default_rng(seed)
+    scale = 0.3 * np.maximum(1.0, np.abs(own).max(1, keepdims=True))
+    noisy = (own + scale * rng.normal(size=own.shape)).astype(np.float32)
+    return dict(own=own, noisy=noisy, zeros=np.zeros_like(own))
+
+
 # ---- row counts, the exclusion, contact wrenches from the oracle's rows
 
 def npyr(env):
@@ -239,6 +282,14 @@ def keep(kind, hip_counts, ref, npyr):
           % (flips.sum(), len(hip), (hip != c64).any(1).sum(), (c32 != c64).any(1).sum()))
     assert flips.mean() <= 0.02, f"{kind}: row counts differ in {flips.sum()} of {len(hip)} envs"
     return ~flips
+
+
+def keep_inverse(kind, phys, ref, npyr):
+    """keep on the counts of the last inverse()"""
+    hc = phys.inverse_efc_counts.cpu().numpy().astype(int)
+    ncon = hc[:, 0] - hc[:, 1] - hc[:, 2] - hc[:, 3]
+    assert (ncon % npyr == 0).all() and (ncon >= 0).all()
+    return keep(kind, np.stack([hc[:, 1], hc[:, 2], hc[:, 3], ncon // npyr], 1), ref, npyr)
 
 
 def contact_order_check(kind, A, geom1, geom2, ref, kept):

@@ -6,7 +6,7 @@ States: random_states(envdef, kind, 256, 11), the states of test_constraint_gpu,
 whose row counts flip: tests/physics_support.py.
 
 The reference: per env Oracle.forward(q, v, ctrl, zeros) in f64 and in f32 gives M, qfrc_bias, qfrc_passive, qfrc_actuator and
-the rows efc_J, efc_aref, efc_D, efc_R, efc_floss with their counts; row_forces() below applies the row law at the given
+the rows efc_J, efc_aref, efc_D, efc_R, efc_floss with their counts; physics_support.row_forces() applies the row law at the given
 acceleration (the law oracle_debug_cost states as a cost), then J^T f and M a + bias - passive - J^T f.  The f64 oracle's terms in
 float64 are the reference, the f32 oracle's terms in float32 the spread.  On the CPU, with the oracle's own reset states for seed 11
 and the same perturbation, the f32-vs-f64 part of the exclusion leaves out 0 of 256 envs on all five families (re-checked for this
@@ -19,39 +19,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from physics_support import (FAMILIES, IMPLICIT, PIPE, all_but, assert_unchanged, bits, handle_snapshot, handle_views, make, oracle_pass,
-                             rel, rule, setup)
-from physics_support import keep as keep_rows, npyr as npyr_of
+from physics_support import (FAMILIES, IMPLICIT, PIPE, all_but, assert_unchanged, bits, handle_snapshot, handle_views, inverse_inputs, inverse_ref,
+                             keep_inverse, make, oracle_pass, rel, rule, setup)
+from physics_support import npyr as npyr_of
 from rsr_mjx_amd import prng
 
 N = 256
 SEED = 11
 OUT = ("efc_force", "qfrc_constraint", "qfrc_actuator", "qfrc_inverse")
-
-
-def row_forces(r, a, dt):
-    """efc_force at acceleration a in arithmetic dt: x = J a - aref; equality rows -D x; friction-loss rows -D x, clamped to
-    +-floss outside |x| < R floss; limit and contact rows -D min(x, 0)"""
-    J, aref, D, R, fl = (r[k].astype(dt) for k in ("efc_J", "efc_aref", "efc_D", "efc_R", "efc_floss"))
-    x = (J @ a.astype(dt) - aref).astype(dt)
-    f = (-D * x).astype(dt)
-    ne, nf = r["ne"], r["nf"]
-    fr = slice(ne, ne + nf)
-    rf = (R[fr] * fl[fr]).astype(dt)
-    f[fr] = np.where(x[fr] <= -rf, fl[fr], np.where(x[fr] >= rf, -fl[fr], f[fr]))
-    f[ne + nf:] = (-D[ne + nf:] * np.minimum(x[ne + nf:], 0)).astype(dt)
-    return f
-
-
-def inverse_ref(r, a, dt, nefc_max):
-    """the four checked outputs at acceleration a from oracle env r, in arithmetic dt"""
-    f = row_forces(r, a, dt)
-    qfc = (r["efc_J"].astype(dt).T @ f).astype(dt)
-    a = a.astype(dt)
-    qfi = ((r["M"].astype(dt) @ a).astype(dt) + r["qfrc_bias"].astype(dt) - r["qfrc_passive"].astype(dt) - qfc).astype(dt)
-    pad = np.zeros(nefc_max, dt)
-    pad[:len(f)] = f
-    return dict(efc_force=pad, qfrc_constraint=qfc, qfrc_actuator=r["qfrc_actuator"].astype(dt), qfrc_inverse=qfi)
 
 
 def to_continuous(r, a, h, damp, dt):
@@ -65,21 +40,11 @@ def _ref(oracle_mod, E, qpos, qvel, ctrl):
 
 
 def _keep(kind, phys, ref, npyr):
-    """keep on the counts of the last inverse()"""
-    hc = phys.inverse_efc_counts.cpu().numpy().astype(int)
-    ncon = hc[:, 0] - hc[:, 1] - hc[:, 2] - hc[:, 3]
-    assert (ncon % npyr == 0).all() and (ncon >= 0).all()
-    return keep_rows(kind, np.stack([hc[:, 1], hc[:, 2], hc[:, 3], ncon // npyr], 1), ref, npyr)
+    return keep_inverse(kind, phys, ref, npyr)
 
 
 def _inputs(ref64):
-    """the three accelerations of the parity test, fp32 [N, nv]: the f64 oracle's own qacc, that plus seeded noise of scale
-    0.3 max(1, |qacc|_inf), zeros"""
-    own = np.stack([r["qacc"] for r in ref64]).astype(np.float32)
-    rng = np.random.default_rng(SEED)
-    scale = 0.3 * np.maximum(1.0, np.abs(own).max(1, keepdims=True))
-    noisy = (own + scale * rng.normal(size=own.shape)).astype(np.float32)
-    return dict(own=own, noisy=noisy, zeros=np.zeros_like(own))
+    return inverse_inputs(ref64, SEED)
 
 
 def _dev(x, phys):
