@@ -666,6 +666,16 @@ static int plane_cylinder(const real *ppos, const real *pmat, const real *cpos, 
   real dist0 = v3dot(rel, n);
   real vec[3] = {axis[0] * prjaxis - n[0], axis[1] * prjaxis - n[1], axis[2] * prjaxis - n[2]};
   real len = v3norm(vec);
+  /* The rim direction lies in the disk's plane.  The subtraction above leaves a part along the axis: its rounding, and
+   * (|axis|^2 - 1) prjaxis of an axis that is unit to 1e-8 only (the blob's float32 quaternions).  Against a `len` of the same
+   * size -- axis within 1e-3 rad of the normal -- that part pushed the "rim" points off the disk by up to the radius.  Within
+   * 1e-2 of alignment it is taken out (a departure from the published source, which normalises `vec` as it stands); beyond,
+   * where it is under 1e-5 of `len`, the arithmetic stays as it was. */
+  if (len < (real)1e-2) {
+    real along = v3dot(vec, axis) / v3dot(axis, axis);
+    for (int k = 0; k < 3; k++) vec[k] -= axis[k] * along;
+    len = v3norm(vec);
+  }
   if (len < (real)1e-12) for (int k = 0; k < 3; k++) vec[k] = cmat[3 * k] * radius;     /* disk parallel to the plane: the cylinder's x axis */
   else for (int k = 0; k < 3; k++) vec[k] = vec[k] / len * radius;
   real prjvec = v3dot(vec, n);

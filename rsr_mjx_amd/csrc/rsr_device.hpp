@@ -1605,7 +1605,10 @@ __device__ __forceinline__ void collision(const DModel& m, const Hot& h, Smem<C>
         const float r = size2.x, hl = size2.y;
         const float dist0 = dot(p2 - p1, n);
         V3 vec = axis * prjaxis - n;
-        const float len = fsqrt(dot(vec, vec));
+        float len = fsqrt(dot(vec, vec));
+        // the rim direction lies in the disk's plane: within 1e-2 of alignment, take out what rounding (and an axis that is unit to
+        // 1e-7 only) leaves of vec along the axis; within 1e-3 rad that part is as large as len, and put the rim points up to r off the disk
+        if (len < 1e-2f) { vec = vec - axis * (dot(vec, axis) * frcp(dot(axis, axis))); len = fsqrt(dot(vec, vec)); }
         if (len < 1e-12f) vec = col(R2.m, 0) * r;
         else { const float rl = frcp(len); vec = v3(vec.x * rl * r, vec.y * rl * r, vec.z * rl * r); }
         const float prjvec = dot(vec, n);

@@ -3,8 +3,12 @@ bit-identity with the fused env step, parity with the CPU oracle's forward / ste
 import numpy as np
 import pytest
 
+from boxbox_cases import by_pair, match_sets
+from planeprim_cases import PAIR_PLANE_CAPSULE, PAIR_PLANE_CYLINDER, PAIR_PLANE_SPHERE
 from physics_support import FAMILIES, PIPE, assert_unchanged, bits, handle_snapshot, make, random_states, rel, rule
 from rsr_mjx_amd import prng
+
+PRIMITIVE_KINDS = (PAIR_PLANE_SPHERE, PAIR_PLANE_CAPSULE, PAIR_PLANE_CYLINDER)
 
 
 @pytest.mark.gpu
@@ -108,7 +112,8 @@ def test_physics_oracle_parity(oracle_mod, kind):
 @pytest.mark.parametrize("kind", FAMILIES)
 def test_physics_contacts_view(oracle_mod, kind):
     """Active contacts after forward() against the oracle's narrow phase on the same state (f64, contacts on the oracle's own
-    geom_xpos / geom_xmat): count, depth and normal per (geom1, geom2) pair; ncon_dropped = uncapped count - capped count."""
+    geom_xpos / geom_xmat): count, depth and normal per (geom1, geom2) pair, and for plane-sphere, -capsule and -cylinder pairs
+    also pos, set-matched per pair within 2e-5; ncon_dropped = uncapped count - capped count."""
     import torch
     from rsr_mjx_amd.physics import Physics
     n = 256
@@ -125,7 +130,8 @@ def test_physics_contacts_view(oracle_mod, kind):
     A = envdef.sys.arrays
     pg1, pg2 = A["pair_geom1"], A["pair_geom2"]
     o = oracle_mod.Oracle(E.blob, "f64")
-    mismatch = 0
+    pair_of = {(int(a), int(b)): p for p, (a, b) in enumerate(zip(pg1, pg2))}
+    mismatch = pos_checked = 0
     for e in range(n):
         o.set_ncon_cap(1 << 20)
         o.forward(qpos[e], qvel[e], ctrl[e], None)
@@ -145,7 +151,15 @@ def test_physics_contacts_view(oracle_mod, kind):
             assert abs(h[2] - r[2]) <= 2e-5, (kind, e, h[2], r[2])
             assert np.abs(np.array(h[3]) - np.array(r[3])).max() <= 1e-4, (kind, e)      # (height-field facet normals: 2e-5 in fp32)
         assert (c["geom1"][e, nc:] == -1).all() and (c["dist"][e, nc:] == 0).all()
+        # spheres, capsules and cylinders against a plane have no selection step: the points of a pair are the same set, so pos too
+        hp = by_pair([pair_of[(int(a), int(b))] for a, b in zip(c["geom1"][e, :nc], c["geom2"][e, :nc])], c["dist"][e, :nc], c["pos"][e, :nc], c["normal"][e, :nc])
+        for p, (_, opos, _) in by_pair(rc[:, 9], rc[:, 0], rc[:, 1:4], rc[:, 4:7]).items():
+            if int(A["pair_kind"][p]) in PRIMITIVE_KINDS:
+                assert p in hp and len(hp[p][1]) == len(opos), (kind, e, p)
+                assert match_sets(opos, hp[p][1])[1] <= 2e-5, (kind, e, p, opos, hp[p][1])
+                pos_checked += 1
     assert mismatch <= max(2, n // 100), f"{kind}: contact count differs from the oracle in {mismatch} of {n} envs"
+    assert pos_checked > 0 or kind in ("cube", "tshape", "go2rough"), kind
     if kind == "footstand":
         assert (c["ncon_dropped"] > 0).any() and (c["ncon"] == cap).any()
 
