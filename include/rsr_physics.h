@@ -10,6 +10,8 @@
  *                          per env from its current state, trajectories [M, K, T, w]; the record is read only.
  *   rsr_physics_param_rollouts <- the same with the model varied: vmap(lambda leaves: lax.scan(mjx.step)) over K sets of model
  *                          leaves per env (friction, mass, damping, gains, ...), with no replica batch; the record is read only.
+ *   rsr_physics_feedback_rollouts <- the same in closed loop: lax.scan of u = ctrl + gain (x (-) x_ref) then mjx.step, the control
+ *                          of every control step computed on the device from the sample's own state; the record is read only.
  *   rsr_physics_set_sensors: the site sensors of data.sensordata (RSR_P_SENSORDATA, and a rollout's sensordata rows).
  *   rsr_physics_set_applied / rsr_physics_applied_view: data.xfrc_applied and data.qfrc_applied, per-env inputs of every forward
  *                          pass of these calls (zero until set).
@@ -162,6 +164,34 @@ typedef struct rsr_param_samples { const float* leaf[RSR_DR_COUNT]; } rsr_param_
 int rsr_physics_param_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl,
                                const rsr_param_samples* params, int K, int T, int nsteps, int flags,
                                const rsr_rollout_out* out, void* hip_stream);
+
+/* Closed-loop rollouts, for iLQR / iLQG forward passes, MPPI with a feedback term, CEM over controller gains and identification
+ * from logs recorded under a controller: rsr_physics_param_rollouts in every respect but one (one wavefront per (env, sample),
+ * the record read only, rows indexed by slot, params NULL or partly NULL, applied forces held for all T control steps).  At the
+ * start of control step t the control is computed from the sample's own current state (the record's at t = 0, the state after
+ * control step t-1 otherwise):
+ *   dq  = mj_differentiatePos(qpos_ref[., t], qpos) with dt = 1: qpos (-) qpos_ref in the tangent space [nv]; a free joint's
+ *         rotation is the rotation vector of conj(q_ref) q, as rsr_physics_transition_fd takes its differences
+ *   dv  = qvel - qvel_ref[., t]                                                                          [nv]
+ *   u_j = ctrl[., t, j] + sum_{i < nv} gain[., t, j, i] dq_i + sum_{i < nv} gain[., t, j, nv + i] dv_i
+ *         accumulated in that order from ctrl[., t, j], one fp32 fma per term
+ *   u_j = clamp(u_j, actuator_ctrlrange_j)     only with RSR_FB_CLAMP and actuator_ctrllimited_j
+ * and u is held for the control step's nsteps substeps.  An iLQR line search folds its alpha k_t into a per-sample ctrl.
+ * ctrl: device float32 [M, T, nu], or with RSR_FB_CTRL_PER_SAMPLE [M, K, T, nu].  fb: gain [M, T, nu, 2 nv], qpos_ref [M, T, nq]
+ * and qvel_ref [M, T, nv], shared by the K samples of a slot, or with RSR_FB_PER_SAMPLE [M, K, T, ..] all three.  params, out,
+ * env_ids, K, T, nsteps: as rsr_physics_param_rollouts.  ctrl_out: NULL, or device float32 [M, K, T, nu] that receives the u that
+ * was applied.  Only the buffers of out and ctrl_out are written: the record, every buffer of the handle, the batch's own leaf
+ * tensors and the PRNG keys are untouched; the handle owns no buffer for this call.  An id outside [0, num_envs) runs nothing and
+ * its slot's rows, those of ctrl_out included, are left alone.  Checked before any device work.  RSR_ERR_ARG: everything
+ * rsr_physics_param_rollouts refuses, except that an out with all six members NULL is refused only when ctrl_out is NULL too (a
+ * NULL out always is); a NULL fb or an fb with a NULL member; unknown flag bits.  RSR_ERR_UNSUPPORTED: as rsr_physics_param_rollouts. */
+typedef struct rsr_feedback { const float* gain; const float* qpos_ref; const float* qvel_ref; } rsr_feedback;
+#define RSR_FB_CTRL_PER_SAMPLE 1   /* ctrl is [M,K,T,nu]; without it [M,T,nu]                          */
+#define RSR_FB_PER_SAMPLE      2   /* gain / qpos_ref / qvel_ref rows are [M,K,T,..]; without it [M,T,..] */
+#define RSR_FB_CLAMP           4   /* clamp u to actuator_ctrlrange where actuator_ctrllimited         */
+int rsr_physics_feedback_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl,
+                                  const rsr_feedback* fb, const rsr_param_samples* params, int K, int T, int nsteps,
+                                  int flags, const rsr_rollout_out* out, float* ctrl_out, void* hip_stream);
 
 /* Applied forces (MuJoCo's data.xfrc_applied / data.qfrc_applied): per-env state of the handle, added in every forward pass of
  * rsr_physics_step (each substep), _forward, _forward_envs and _rollout (each substep, held for all T control steps):

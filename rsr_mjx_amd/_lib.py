@@ -44,7 +44,8 @@ PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step",
                 "rsr_physics_view", "rsr_physics_set_sensors", "rsr_physics_rollout", "rsr_physics_set_applied",
                 "rsr_physics_applied_view", "rsr_physics_set_jac_sites", "rsr_physics_dynamics", "rsr_physics_dynamics_view",
                 "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
-                "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts"]
+                "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts",
+                "rsr_physics_feedback_rollouts"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -84,6 +85,15 @@ class ParamSamples(C.Structure):
 
 # the RSR_PR_* flags (include/rsr_physics.h)
 PR_CTRL_PER_SAMPLE = 1
+
+
+class Feedback(C.Structure):
+    """struct rsr_feedback (include/rsr_physics.h): device pointers, gain [.., T, nu, 2 nv], qpos_ref [.., T, nq], qvel_ref [.., T, nv]."""
+    _fields_ = [(n, C.c_void_p) for n in ("gain", "qpos_ref", "qvel_ref")]
+
+
+# the RSR_FB_* flags (include/rsr_physics.h)
+FB_CTRL_PER_SAMPLE, FB_PER_SAMPLE, FB_CLAMP = 1, 2, 4
 
 SYMBOLS = [
     "rsr_model_create", "rsr_model_dims", "rsr_model_destroy", "rsr_batch_create", "rsr_batch_destroy",
@@ -140,6 +150,7 @@ def lib() -> C.CDLL:
     L.rsr_physics_inverse_view.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p]
     L.rsr_physics_sample_rollouts.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp]
     L.rsr_physics_param_rollouts.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.rsr_physics_feedback_rollouts.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

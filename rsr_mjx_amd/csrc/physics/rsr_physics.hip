@@ -2,7 +2,8 @@
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse) and sampled rollouts (rsr_physics_sample_rollouts).  The kernels are in the family units (physics/rsr_physics_kernels.hpp).
-// Parameter rollouts (rsr_physics_param_rollouts) launch through the sweep units (physics/rsr_sweep_launch.hpp).
+// Parameter rollouts (rsr_physics_param_rollouts) and closed-loop rollouts (rsr_physics_feedback_rollouts) launch through the sweep
+// units (physics/rsr_sweep_launch.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -260,6 +261,42 @@ extern "C" int rsr_physics_param_rollouts(rsr_physics* p, const int32_t* env_ids
       return fail(RSR_ERR_UNSUPPORTED, "rsr_physics_param_rollouts: this leaf is per-env only in the Go2 kernels (rsr_batch_set_dr_field); the Airbot kernels take the first four");
     sw.leaf[f] = params->leaf[f];
   }
+  rsr::Launch x = physics_args(p, nullptr, env_ids, (int)grid, nsteps, hip_stream);
+  x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
+  return counted(p, sweep_launch(p, x, sw, who));
+}
+
+// Closed-loop rollouts: the parameter rollout's launch with the feedback rows set (rsr_feedback.hpp).
+extern "C" int rsr_physics_feedback_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, const rsr_feedback* fb,
+                                             const rsr_param_samples* params, int K, int T, int nsteps, int flags, const rsr_rollout_out* out,
+                                             float* ctrl_out, void* hip_stream) {
+  const char* who = "rsr_physics_feedback_rollouts";
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: null handle");
+  if (!ctrl) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: null ctrl");
+  if (!fb || !fb->gain || !fb->qpos_ref || !fb->qvel_ref) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: null fb, or a null member of it");
+  if (!out) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: null out");
+  if (!ctrl_out && !(out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata))
+    return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: nothing to record and null ctrl_out");
+  if (K < 1 || T < 1 || nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: K, T and nsteps must be >= 1");
+  if (flags & ~(RSR_FB_CTRL_PER_SAMPLE | RSR_FB_PER_SAMPLE | RSR_FB_CLAMP)) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: unknown flag bits");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, who, &n)) return rc;
+  if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: sensordata requested with no sensor table set");
+  const int64_t grid = (int64_t)n * K;           // one wave per (slot, sample)
+  if (grid > INT32_MAX || (int64_t)T * nsteps > INT32_MAX)
+    return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: envs x K and T x nsteps must stay below 2^31");
+  rsr::SweepArgs sw{};
+  sw.K = K;
+  sw.ctrl_per_sample = (flags & RSR_FB_CTRL_PER_SAMPLE) != 0;
+  for (int f = 0; params && f < RSR_DR_COUNT; ++f) {
+    if (params->leaf[f] && f >= RSR_DR_BODY_IPOS && p->b->model->spec->family != rsr::FAMILY_GO2)
+      return fail(RSR_ERR_UNSUPPORTED, "rsr_physics_feedback_rollouts: this leaf is per-env only in the Go2 kernels (rsr_batch_set_dr_field); the Airbot kernels take the first four");
+    sw.leaf[f] = params->leaf[f];
+  }
+  sw.fb_gain = fb->gain; sw.fb_qpos = fb->qpos_ref; sw.fb_qvel = fb->qvel_ref;
+  sw.ctrl_out = ctrl_out;
+  sw.fb_per_sample = (flags & RSR_FB_PER_SAMPLE) != 0;
+  sw.fb_clamp = (flags & RSR_FB_CLAMP) != 0;
   rsr::Launch x = physics_args(p, nullptr, env_ids, (int)grid, nsteps, hip_stream);
   x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
   return counted(p, sweep_launch(p, x, sw, who));

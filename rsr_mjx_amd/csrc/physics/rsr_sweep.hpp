@@ -9,10 +9,15 @@
 // a batch whose env holds that record row and, as its per-env leaves, that sample's (tests/test_param_rollouts_gpu.py).  ctrl is
 // per sample, or one sequence shared by a slot's K samples (the identification case: one logged control sequence).  The record is
 // read only, and nothing but the caller's trajectory buffers is written: no record, no side buffer, no sensordata row.
+//
+// rsr_physics_feedback_rollouts is the same launch with sw.fb_gain set: feedback_ctrl (rsr_feedback.hpp) then turns the ctrl row
+// just loaded into ctrl + gain (x (-) x_ref) on the sample's own state, at the start and at every control-step boundary.  The
+// branch is wave-uniform (a kernel argument), and with it off the kernel runs the statements it ran before.
 #pragma once
 #include "rsr_sweep_launch.hpp"
 #include "rsr_sensors.hpp"
 #include "rsr_applied.hpp"
+#include "rsr_feedback.hpp"
 
 namespace rsr {
 
@@ -105,6 +110,7 @@ void sweep_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs 
   const size_t cb = sw.ctrl_per_sample ? (size_t)b : (size_t)slot;
   // one loop over the T * nsteps substeps, the control-step boundary a wave-uniform branch, as in rollout_kernel
   if (lane < C::NU) s.ctrl[lane] = r.ctrl[cb * r.T * C::NU + lane];
+  if (sw.fb_gain) feedback_ctrl<C>(m, hot, s, sw, (sw.fb_per_sample ? (size_t)b : (size_t)slot) * r.T, (size_t)b * r.T, lane);
   WSYNC();
   const int total = r.T * p.nsteps;              // (T * nsteps < 2^31: rsr_physics_param_rollouts)
   int t = 0, fr = 0;
@@ -129,6 +135,7 @@ void sweep_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs 
     if (r.sd && lt < nsd) r.sd[row * nsd + lt] = sv;
     if (++t < r.T) {
       if (lt < C::NU) s.ctrl[lt] = r.ctrl[(cb * r.T + t) * C::NU + lt];
+      if (sw.fb_gain) feedback_ctrl<C>(m, hot, s, sw, (sw.fb_per_sample ? (size_t)b : (size_t)slot) * r.T + t, (size_t)b * r.T + t, lt);
       WSYNC();
     }
   }

@@ -10,6 +10,10 @@
                                                                                           (K sets of model leaves per env from its
                                                                                            current state, [M, K, T, w]; no replica
                                                                                            batch, the record and the leaves stay)
+    lax.scan of u = ctrl + gain (x (-) x_ref), mjx.step ->  Physics.feedback_rollouts(ctrl, gain, qpos_ref, qvel_ref)
+                                                                                          (the same in closed loop: the control of
+                                                                                           every control step from the sample's own
+                                                                                           state, on the device; [M, K, T, w])
     mjx_env.get_sensor_data(model, data, name)  ->  Physics.sensor(name)                 (site sensors, Physics.set_sensors)
     data.replace(xfrc_applied=..., qfrc_applied=...) ->  Physics.set_applied(xfrc, qfrc)  (held by every later step / forward /
                                                                                            rollout, like a Data field)
@@ -96,6 +100,7 @@ class Physics:
         self._qacc_in = None                       # the accelerations of inverse()'s last launch
         self._sample_ctrl_in = None                # the control sequences of sample_rollouts()'s last launch
         self._param_in = None                      # the control sequences and leaf tensors of param_rollouts()'s last launch
+        self._feedback_in = None                   # the inputs of feedback_rollouts()'s last launch
         # the env-id tensor of each entry point's last launch (_call_envs)
         self._ids_in: Dict[str, Any] = {}
         if sensors is not None:
@@ -495,6 +500,62 @@ class Physics:
         return dict(geom_friction=(d.ngeom, 3), body_mass=(d.nbody,), dof_damping=(d.nv,), dof_frictionloss=(d.nv,),
                     body_ipos=(d.nbody, 3), qpos0=(d.nq,), dof_armature=(d.nv,), actuator_gainprm=(d.nu, 3), actuator_biasprm=(d.nu, 3))
 
+    def _sampled_leaves(self, who: str, params, M: int, K: Optional[int]):
+        """(_lib.ParamSamples, the tensors it points to, K) of `params` {leaf name: [M, K, ...]}, checked for the method `who`; K:
+        what the caller's other inputs say, or None"""
+        import torch
+        from .envs import config as cfg
+        dev = self.qvel.device
+        params = dict(params or {})
+        unknown = sorted(set(params) - set(_lib.DR_FIELDS))
+        if unknown:
+            raise ValueError(f"{who}: not a model leaf: {unknown}; leaves: {_lib.DR_FIELDS}")
+        shapes = self._leaf_shapes()
+        ps, leaves = _lib.ParamSamples(), []
+        for fid, name in enumerate(_lib.DR_FIELDS):
+            t = params.get(name)
+            if t is None:
+                continue
+            if fid >= _lib.DR_FIELDS.index("body_ipos") and int(self.dims.env_kind) not in (cfg.ENV_GO2, cfg.ENV_GO2_HANDSTAND):
+                raise ValueError(f"{who}: {name} is a per-sample leaf on the Go2 models only")
+            want = f"({M}, K >= 1, {', '.join(str(int(w)) for w in shapes[name])})"
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 + len(shapes[name]) or t.shape[0] != M or t.shape[1] < 1 \
+                    or tuple(t.shape[2:]) != tuple(int(w) for w in shapes[name]) or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{who}: params[{name!r}] must be a contiguous float32 tensor of shape {want} on {dev}")
+            if K is not None and int(t.shape[1]) != K:
+                raise ValueError(f"{who}: params[{name!r}] has K = {int(t.shape[1])}, the others (or ctrl) K = {K}")
+            K = int(t.shape[1])
+            ps.leaf[fid] = t.data_ptr()
+            leaves.append(t)
+        return ps, leaves, K
+
+    def _trajectory_out(self, who: str, fields, lead: tuple, out, extra: Optional[Dict[str, int]] = None):
+        """({field: tensor lead + (w,)}, _lib.RolloutOut) for `fields` of ROLLOUT_FIELDS (and of `extra` {name: width}, which
+        RolloutOut does not hold), checked for the method `who`; `out`: caller-owned tensors to use instead of new ones"""
+        import torch
+        extra = extra or {}
+        fields = tuple(fields)
+        bad = [f for f in fields if f not in ROLLOUT_FIELDS and f not in extra]
+        if bad or not fields:
+            raise ValueError(f"{who}: unknown or no fields {bad}; recordable: {ROLLOUT_FIELDS + tuple(extra)}")
+        if "sensordata" in fields and self.nsensordata == 0:
+            raise ValueError(f"{who}: sensordata requested but no sensors are set (set_sensors)")
+        d, dev = self.dims, self.qvel.device
+        width = dict(qpos=d.nq, qvel=d.nv, time=1, actuator_force=d.nu, ncon=1, sensordata=self.nsensordata, **extra)
+        res, ptrs = {}, _lib.RolloutOut()
+        out = out or {}
+        for f in fields:
+            shape = tuple(lead) + (width[f],)
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            elif (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
+                raise ValueError(f"{who}: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {dev}")
+            res[f] = t
+            if f not in extra:
+                setattr(ptrs, f, t.data_ptr())
+        return res, ptrs
+
     def param_rollouts(self, ctrl, params, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), env_ids=None,
                        out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """What system identification, domain-randomised planning and CEM over model parameters ask: from the state each env is
@@ -512,7 +573,6 @@ class Physics:
         ones.  Writes nothing else: the record, the side buffer, sensordata, every other buffer of the handle and the batch's own
         leaf tensors stay as they are.  A field takes 4 * M * K * T * w bytes: ask for what the loss reads."""
         import torch
-        from .envs import config as cfg
         nsteps = self.n_substeps if nsteps is None else int(nsteps)
         if nsteps < 1:
             raise ValueError(f"param_rollouts: nsteps must be >= 1, got {nsteps}")
@@ -523,52 +583,76 @@ class Physics:
             raise ValueError(f"param_rollouts expects ctrl as a float32 tensor of shape ({M}, T >= 1, {nu}) or ({M}, K >= 1, T >= 1, {nu}) on {dev}")
         per_sample = ctrl.dim() == 4
         T, K = int(ctrl.shape[-2]), int(ctrl.shape[1]) if per_sample else None
-        params = dict(params or {})
-        unknown = sorted(set(params) - set(_lib.DR_FIELDS))
-        if unknown:
-            raise ValueError(f"param_rollouts: not a model leaf: {unknown}; leaves: {_lib.DR_FIELDS}")
-        shapes = self._leaf_shapes()
-        ps, leaves = _lib.ParamSamples(), []
-        for fid, name in enumerate(_lib.DR_FIELDS):
-            t = params.get(name)
-            if t is None:
-                continue
-            if fid >= _lib.DR_FIELDS.index("body_ipos") and int(self.dims.env_kind) not in (cfg.ENV_GO2, cfg.ENV_GO2_HANDSTAND):
-                raise ValueError(f"param_rollouts: {name} is a per-sample leaf on the Go2 models only")
-            want = f"({M}, K >= 1, {', '.join(str(int(w)) for w in shapes[name])})"
-            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 + len(shapes[name]) or t.shape[0] != M or t.shape[1] < 1 \
-                    or tuple(t.shape[2:]) != tuple(int(w) for w in shapes[name]) or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"param_rollouts: params[{name!r}] must be a contiguous float32 tensor of shape {want} on {dev}")
-            if K is not None and int(t.shape[1]) != K:
-                raise ValueError(f"param_rollouts: params[{name!r}] has K = {int(t.shape[1])}, the others (or ctrl) K = {K}")
-            K = int(t.shape[1])
-            ps.leaf[fid] = t.data_ptr()
-            leaves.append(t)
+        ps, leaves, K = self._sampled_leaves("param_rollouts", params, M, K)
         if K is None:
             raise ValueError("param_rollouts: K is not given: pass sampled leaves in params, or a 4-D ctrl [M, K, T, nu]")
-        fields = tuple(fields)
-        bad = [f for f in fields if f not in ROLLOUT_FIELDS]
-        if bad or not fields:
-            raise ValueError(f"param_rollouts: unknown or no fields {bad}; recordable: {ROLLOUT_FIELDS}")
-        if "sensordata" in fields and self.nsensordata == 0:
-            raise ValueError("param_rollouts: sensordata requested but no sensors are set (set_sensors)")
-        d = self.dims
-        width = dict(qpos=d.nq, qvel=d.nv, time=1, actuator_force=d.nu, ncon=1, sensordata=self.nsensordata)
-        res, ptrs = {}, _lib.RolloutOut()
-        out = out or {}
-        for f in fields:
-            shape = (M, K, T, width[f])
-            t = out.get(f)
-            if t is None:
-                t = torch.empty(shape, dtype=torch.float32, device=ctrl.device)
-            elif (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != ctrl.device):
-                raise ValueError(f"param_rollouts: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {ctrl.device}")
-            res[f] = t
-            setattr(ptrs, f, t.data_ptr())
+        res, ptrs = self._trajectory_out("param_rollouts", fields, (M, K, T), out)
         c = ctrl.contiguous()
         self._param_in = (c, leaves)               # kept alive until the next call (the launch is asynchronous)
         self._call_envs("rsr_physics_param_rollouts", "param_rollouts", ids, C.c_void_p(c.data_ptr()), C.byref(ps), K, T, nsteps,
                         _lib.PR_CTRL_PER_SAMPLE if per_sample else 0, C.byref(ptrs), checked=True)
+        return res
+
+    def feedback_rollouts(self, ctrl, gain, qpos_ref, qvel_ref, params=None, nsteps: Optional[int] = None,
+                          fields: Sequence[str] = ("qpos", "qvel", "time"), env_ids=None, clamp: bool = False,
+                          out: Optional[Dict[str, Any]] = None, K: Optional[int] = None) -> Dict[str, Any]:
+        """What an iLQR / iLQG forward pass, MPPI with a feedback term and CEM over controller gains ask: param_rollouts in closed
+        loop.  At the start of control step t each sample computes its control from its own current state (the record's at
+        t = 0, the state after control step t - 1 otherwise),
+            u = ctrl[.., t] + gain[.., t] @ [qpos (-) qpos_ref[.., t]; qvel - qvel_ref[.., t]],
+        (-) in the tangent space of qpos (mj_differentiatePos: nv numbers, a free joint's rotation as a rotation vector, as
+        transition_fd takes its differences), accumulated in fp32 from ctrl in index order, and holds it for the step's `nsteps`
+        substeps; `clamp` then clips u to actuator_ctrlrange where the actuator is ctrl-limited.  All float32 tensors on the
+        env's device, M = len(env_ids) (default: every env): ctrl [M, T, nu], or [M, K, T, nu] per sample (an iLQR line search
+        folds alpha * k_t into it); gain [M, T, nu, 2 nv] with qpos_ref [M, T, nq] and qvel_ref [M, T, nv], shared by an env's K
+        samples, or all three per sample, [M, K, T, ..] (candidate gain sets).  `params`: per-sample model leaves as
+        param_rollouts takes them, or None.  K comes from whichever input is per-sample (they must agree); pass `K` when none is.
+        Returns {field: [M, K, T, w]} for `fields`: ROLLOUT_FIELDS as param_rollouts, and "ctrl", the controls that were applied
+        [M, K, T, nu] (fed to sample_rollouts they reproduce the trajectories bit for bit).  `out`: caller-owned float32 tensors
+        to fill instead of new ones.  Writes nothing else: the record, every buffer of the handle and the batch's own leaf
+        tensors stay as they are.  A field takes 4 * M * K * T * w bytes: ask for what the cost reads."""
+        import torch
+        who = "feedback_rollouts"
+        nsteps = self.n_substeps if nsteps is None else int(nsteps)
+        if nsteps < 1:
+            raise ValueError(f"{who}: nsteps must be >= 1, got {nsteps}")
+        ids = None if env_ids is None else self._ids(env_ids, who)
+        d, dev = self.dims, self.qvel.device
+        M, nu, nv, nq = self.num_envs if ids is None else int(ids.numel()), int(d.nu), int(d.nv), int(d.nq)
+
+        def rows(name, t, tail, ranks):
+            """(K or None, T) of a [M, (K,) T, *tail] input"""
+            want = f"({M}, T >= 1, {', '.join(map(str, tail))}) or ({M}, K >= 1, T >= 1, {', '.join(map(str, tail))})"
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() not in ranks or t.shape[0] != M \
+                    or tuple(t.shape[t.dim() - len(tail):]) != tail or min(t.shape[1:t.dim() - len(tail)]) < 1 or t.device != dev:
+                raise ValueError(f"{who} expects {name} as a float32 tensor of shape {want} on {dev}")
+            per = t.dim() == len(tail) + 3
+            return (int(t.shape[1]) if per else None), int(t.shape[-len(tail) - 1])
+
+        Kc, T = rows("ctrl", ctrl, (nu,), (3, 4))
+        Kg, Tg = rows("gain", gain, (nu, 2 * nv), (4, 5))
+        fb_rank = gain.dim() - 1                         # the refs' rank: [M, T, w] or [M, K, T, w]
+        Kq, Tq = rows("qpos_ref", qpos_ref, (nq,), (fb_rank,))
+        Kv, Tv = rows("qvel_ref", qvel_ref, (nv,), (fb_rank,))
+        if (Tg, Tq, Tv) != (T, T, T):
+            raise ValueError(f"{who}: gain, qpos_ref and qvel_ref have T = {Tg}, {Tq}, {Tv}, ctrl T = {T}")
+        for name, k in (("ctrl", Kc), ("gain", Kg), ("qpos_ref", Kq), ("qvel_ref", Kv)):
+            if k is not None and K is not None and k != int(K):
+                raise ValueError(f"{who}: {name} has K = {k}, the others (or the K given) K = {int(K)}")
+            K = k if k is not None else K
+        if K is not None and int(K) < 1:
+            raise ValueError(f"{who}: K must be >= 1, got {K}")
+        ps, leaves, K = self._sampled_leaves(who, params, M, None if K is None else int(K))
+        if K is None:
+            raise ValueError(f"{who}: K is not given: pass it, or a per-sample ctrl, gain or leaf")
+        res, ptrs = self._trajectory_out(who, fields, (M, K, T), out, extra=dict(ctrl=nu))
+        c, g, qr, vr = ctrl.contiguous(), gain.contiguous(), qpos_ref.contiguous(), qvel_ref.contiguous()
+        fb = _lib.Feedback(g.data_ptr(), qr.data_ptr(), vr.data_ptr())
+        self._feedback_in = (c, g, qr, vr, leaves)  # kept alive until the next call (the launch is asynchronous)
+        flags = (_lib.FB_CTRL_PER_SAMPLE if Kc is not None else 0) | (_lib.FB_PER_SAMPLE if Kg is not None else 0) | (_lib.FB_CLAMP if clamp else 0)
+        applied = C.c_void_p(res["ctrl"].data_ptr()) if "ctrl" in res else None
+        self._call_envs("rsr_physics_feedback_rollouts", who, ids, C.c_void_p(c.data_ptr()), C.byref(fb), C.byref(ps), K, T, nsteps, flags,
+                        C.byref(ptrs), applied, checked=True)
         return res
 
     def forward(self) -> None:
