@@ -8,15 +8,12 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "librsrmjx.so")
-# One translation unit per source: the kernels of one model family each (cube, T-shape, Go2: rsr_launch.hpp), the two host
-# units (the C ABI of include/rsr_mjx.h and of include/rsr_physics.h) and, beside each family unit and with its flags, the sweep
-# unit of rsr_physics_param_rollouts and rsr_physics_feedback_rollouts (physics/rsr_sweep_launch.hpp).  The T-shape and Go2 units are built with the SLP vectoriser
+# One translation unit per source: the kernels of one model family each (cube, T-shape, Go2: rsr_launch.hpp) and the two host
+# units (the C ABI of include/rsr_mjx.h and of include/rsr_physics.h).  The T-shape and Go2 units are built with the SLP vectoriser
 # off (its packed-fp32 pairing costs the Go2 and T-shape kernels ~3 % and gains the cube kernels ~0.5 %; measured A/B on one box).
 # Kernels of one unit also perturb each other's register allocation: a unit holds one model family.
 UNITS = [("rsr_cube.hip", []), ("rsr_tshape.hip", ["-fno-slp-vectorize"]), ("rsr_go2.hip", ["-fno-slp-vectorize"]),
-         ("rsr_mjx.hip", []), (os.path.join("physics", "rsr_physics.hip"), []),
-         (os.path.join("physics", "rsr_sweep_cube.hip"), []), (os.path.join("physics", "rsr_sweep_tshape.hip"), ["-fno-slp-vectorize"]),
-         (os.path.join("physics", "rsr_sweep_go2.hip"), ["-fno-slp-vectorize"])]
+         ("rsr_mjx.hip", []), (os.path.join("physics", "rsr_physics.hip"), [])]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 

@@ -5,7 +5,7 @@
 // forward pass, MPPI with a feedback term and CEM over controller gains ask of a rollout.  A stage of its own header: the text
 // between overlay_leaves and sweep_kernel is pinned (tests/test_param_rollouts_api.py).
 #pragma once
-#include "rsr_sweep_launch.hpp"
+#include "../rsr_launch.hpp"
 #include "rsr_transition.hpp"
 
 namespace rsr {

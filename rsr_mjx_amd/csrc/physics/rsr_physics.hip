@@ -1,16 +1,16 @@
 // rsr_physics.hip -- the C ABI of the physics layer (include/rsr_physics.h): rsr_physics_step / rsr_physics_forward /
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
-// (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse) and sampled rollouts (rsr_physics_sample_rollouts).  The kernels are in the family units (physics/rsr_physics_kernels.hpp).
-// Parameter rollouts (rsr_physics_param_rollouts) and closed-loop rollouts (rsr_physics_feedback_rollouts) launch through the sweep
-// units (physics/rsr_sweep_launch.hpp).
+// (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse), sampled rollouts (rsr_physics_sample_rollouts), parameter
+// rollouts (rsr_physics_param_rollouts) and closed-loop rollouts (rsr_physics_feedback_rollouts).  Every launch is a physics op
+// (rsr::PhysOp) sent through physics_launch; the kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
 #include "../rsr_host.hpp"
-#include "rsr_sweep_launch.hpp"
+#include "../rsr_launch.hpp"
 
 // The side buffer belongs to a handle of its own, on a batch it borrows.
 struct rsr_physics {
@@ -81,7 +81,7 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
 }
 
 // The arguments of a physics op on `grid` envs (ids: which, or null: the first `grid`): the handle's buffers as every op's; the
-// caller adds what its op owns (r, fd, inv, K).
+// caller adds what its op owns (r, fd, inv, K, sw).
 static rsr::Launch physics_args(rsr_physics* ph, const float* ctrl, const int* ids, int grid, int nsteps, void* hip_stream) {
   rsr::Launch x = launch_args(ph->b, hip_stream);
   x.grid = grid;
@@ -206,71 +206,72 @@ extern "C" int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int
   return counted(p, physics_launch(p, rsr::OP_PHYS_ROLLOUT, x, "rsr_physics_rollout"));
 }
 
+// The refusals the three (slot, sample) rollouts share, after each entry's own argument checks and in `who`'s name; *waves: the
+// launch's workgroups.  Only reads.
+static int sample_grid(const rsr_physics* p, const int32_t* env_ids, int count, int K, int T, int nsteps, const rsr_rollout_out* out,
+                       const char* who, int* waves) {
+  int n;
+  if (const int rc = env_count(p, env_ids, count, who, &n)) return rc;
+  if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, std::string(who) + ": sensordata requested with no sensor table set");
+  const int64_t grid = (int64_t)n * K;           // one wave per (slot, sample)
+  if (grid > INT32_MAX || (int64_t)T * nsteps > INT32_MAX)
+    return fail(RSR_ERR_ARG, std::string(who) + ": envs x K and T x nsteps must stay below 2^31");
+  *waves = (int)grid;
+  return RSR_OK;
+}
+
 extern "C" int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int K, int T, int nsteps,
                                            const rsr_rollout_out* out, void* hip_stream) {
+  const char* who = "rsr_physics_sample_rollouts";
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: null handle");
   if (!ctrl) return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: null ctrl");
   if (!out || !(out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata))
     return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: null out, or nothing to record");
   if (K < 1 || T < 1 || nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: K, T and nsteps must be >= 1");
-  int n;
-  if (const int rc = env_count(p, env_ids, count, "rsr_physics_sample_rollouts", &n)) return rc;
-  if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: sensordata requested with no sensor table set");
-  const int64_t grid = (int64_t)n * K;           // one wave per (slot, sample)
-  if (grid > INT32_MAX || (int64_t)T * nsteps > INT32_MAX)
-    return fail(RSR_ERR_ARG, "rsr_physics_sample_rollouts: envs x K and T x nsteps must stay below 2^31");
-  rsr::Launch x = physics_args(p, nullptr, env_ids, (int)grid, nsteps, hip_stream);
+  int grid;
+  if (const int rc = sample_grid(p, env_ids, count, K, T, nsteps, out, who, &grid)) return rc;
+  rsr::Launch x = physics_args(p, nullptr, env_ids, grid, nsteps, hip_stream);
   x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
   x.ph.K = K;
-  return counted(p, physics_launch(p, rsr::OP_PHYS_SAMPLE, x, "rsr_physics_sample_rollouts"));
+  return counted(p, physics_launch(p, rsr::OP_PHYS_SAMPLE, x, who));
 }
 
-// Parameter rollouts: an op in all but the enum (rsr_sweep_launch.hpp).  The sweep unit of the model's family launches; a launch
-// error is reported as physics_launch reports one.
-static int sweep_launch(rsr_physics* ph, const rsr::Launch& x, const rsr::SweepArgs& sw, const char* who) {
-  HIPCHK(hipSetDevice(ph->b->device));
-  switch (ph->b->model->spec->family) {
-    case rsr::FAMILY_CUBE: rsr::launch_sweep_cube(x, sw); break;
-    case rsr::FAMILY_TSHAPE: rsr::launch_sweep_tshape(x, sw); break;
-    case rsr::FAMILY_GO2: rsr::launch_sweep_go2(x, sw); break;
+// The tail of the two sweep entries (parameter and closed-loop rollouts), after each entry's own argument checks: sample_grid's
+// refusals and the leaves', then the one launch of sw.K samples per listed env.  The entry has filled what it owns of `sw` (K, the
+// flags, the feedback rows); `params` null: no leaf is sampled.
+static int sweep_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, const rsr_param_samples* params,
+                          rsr::SweepArgs sw, int T, int nsteps, const rsr_rollout_out* out, void* hip_stream, const char* who) {
+  int grid;
+  if (const int rc = sample_grid(p, env_ids, count, sw.K, T, nsteps, out, who, &grid)) return rc;
+  for (int f = 0; params && f < RSR_DR_COUNT; ++f) {
+    if (params->leaf[f] && f >= RSR_DR_BODY_IPOS && p->b->model->spec->family != rsr::FAMILY_GO2)
+      return fail(RSR_ERR_UNSUPPORTED, std::string(who) + ": this leaf is per-env only in the Go2 kernels (rsr_batch_set_dr_field); the Airbot kernels take the first four");
+    sw.leaf[f] = params->leaf[f];
   }
-  { hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(RSR_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(le)); }
-  return RSR_OK;
+  rsr::Launch x = physics_args(p, nullptr, env_ids, grid, nsteps, hip_stream);
+  x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
+  x.ph.sw = sw;
+  return counted(p, physics_launch(p, rsr::OP_PHYS_SWEEP, x, who));
 }
 
 extern "C" int rsr_physics_param_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, const rsr_param_samples* params,
                                           int K, int T, int nsteps, int flags, const rsr_rollout_out* out, void* hip_stream) {
-  const char* who = "rsr_physics_param_rollouts";
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: null handle");
   if (!ctrl) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: null ctrl");
   if (!out || !(out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata))
     return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: null out, or nothing to record");
   if (K < 1 || T < 1 || nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: K, T and nsteps must be >= 1");
   if (flags & ~RSR_PR_CTRL_PER_SAMPLE) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: unknown flag bits");
-  int n;
-  if (const int rc = env_count(p, env_ids, count, who, &n)) return rc;
-  if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: sensordata requested with no sensor table set");
-  const int64_t grid = (int64_t)n * K;           // one wave per (slot, sample)
-  if (grid > INT32_MAX || (int64_t)T * nsteps > INT32_MAX)
-    return fail(RSR_ERR_ARG, "rsr_physics_param_rollouts: envs x K and T x nsteps must stay below 2^31");
   rsr::SweepArgs sw{};
   sw.K = K;
   sw.ctrl_per_sample = (flags & RSR_PR_CTRL_PER_SAMPLE) != 0;
-  for (int f = 0; params && f < RSR_DR_COUNT; ++f) {
-    if (params->leaf[f] && f >= RSR_DR_BODY_IPOS && p->b->model->spec->family != rsr::FAMILY_GO2)
-      return fail(RSR_ERR_UNSUPPORTED, "rsr_physics_param_rollouts: this leaf is per-env only in the Go2 kernels (rsr_batch_set_dr_field); the Airbot kernels take the first four");
-    sw.leaf[f] = params->leaf[f];
-  }
-  rsr::Launch x = physics_args(p, nullptr, env_ids, (int)grid, nsteps, hip_stream);
-  x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
-  return counted(p, sweep_launch(p, x, sw, who));
+  return sweep_rollouts(p, env_ids, count, ctrl, params, sw, T, nsteps, out, hip_stream, "rsr_physics_param_rollouts");
 }
 
 // Closed-loop rollouts: the parameter rollout's launch with the feedback rows set (rsr_feedback.hpp).
 extern "C" int rsr_physics_feedback_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, const rsr_feedback* fb,
                                              const rsr_param_samples* params, int K, int T, int nsteps, int flags, const rsr_rollout_out* out,
                                              float* ctrl_out, void* hip_stream) {
-  const char* who = "rsr_physics_feedback_rollouts";
   if (!p) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: null handle");
   if (!ctrl) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: null ctrl");
   if (!fb || !fb->gain || !fb->qpos_ref || !fb->qvel_ref) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: null fb, or a null member of it");
@@ -279,27 +280,14 @@ extern "C" int rsr_physics_feedback_rollouts(rsr_physics* p, const int32_t* env_
     return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: nothing to record and null ctrl_out");
   if (K < 1 || T < 1 || nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: K, T and nsteps must be >= 1");
   if (flags & ~(RSR_FB_CTRL_PER_SAMPLE | RSR_FB_PER_SAMPLE | RSR_FB_CLAMP)) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: unknown flag bits");
-  int n;
-  if (const int rc = env_count(p, env_ids, count, who, &n)) return rc;
-  if (out->sensordata && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: sensordata requested with no sensor table set");
-  const int64_t grid = (int64_t)n * K;           // one wave per (slot, sample)
-  if (grid > INT32_MAX || (int64_t)T * nsteps > INT32_MAX)
-    return fail(RSR_ERR_ARG, "rsr_physics_feedback_rollouts: envs x K and T x nsteps must stay below 2^31");
   rsr::SweepArgs sw{};
   sw.K = K;
   sw.ctrl_per_sample = (flags & RSR_FB_CTRL_PER_SAMPLE) != 0;
-  for (int f = 0; params && f < RSR_DR_COUNT; ++f) {
-    if (params->leaf[f] && f >= RSR_DR_BODY_IPOS && p->b->model->spec->family != rsr::FAMILY_GO2)
-      return fail(RSR_ERR_UNSUPPORTED, "rsr_physics_feedback_rollouts: this leaf is per-env only in the Go2 kernels (rsr_batch_set_dr_field); the Airbot kernels take the first four");
-    sw.leaf[f] = params->leaf[f];
-  }
   sw.fb_gain = fb->gain; sw.fb_qpos = fb->qpos_ref; sw.fb_qvel = fb->qvel_ref;
   sw.ctrl_out = ctrl_out;
   sw.fb_per_sample = (flags & RSR_FB_PER_SAMPLE) != 0;
   sw.fb_clamp = (flags & RSR_FB_CLAMP) != 0;
-  rsr::Launch x = physics_args(p, nullptr, env_ids, (int)grid, nsteps, hip_stream);
-  x.ph.r = rsr::RollArgs{ctrl, T, out->qpos, out->qvel, out->time, out->actuator_force, out->ncon, out->sensordata};
-  return counted(p, sweep_launch(p, x, sw, who));
+  return sweep_rollouts(p, env_ids, count, ctrl, params, sw, T, nsteps, out, hip_stream, "rsr_physics_feedback_rollouts");
 }
 
 // the applied-force buffers, on first use: both or neither

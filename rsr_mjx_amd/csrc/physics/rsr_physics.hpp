@@ -112,6 +112,20 @@ struct InvArgs {
   const float* qacc;    // [N][nv] the accelerations, row e env e's
   int flags;            // RSR_INV_*
 };
+// The launch arguments of OP_PHYS_SWEEP (PhysLaunch::sw): what sweep_kernel (rsr_sweep.hpp) takes beside sample_kernel's arguments
+// (PhysArgs p, RollArgs r, and Applied while the forces are on).
+struct SweepArgs {
+  const float* leaf[RSR_DR_COUNT];   // per-sample leaves [M][K][width], indexed by enum rsr_dr_field; null: the env's own leaf
+  int K;                             // samples per slot
+  int ctrl_per_sample;               // r.ctrl is [M][K][T][nu]; 0: [M][T][nu], shared by a slot's K samples
+  // rsr_physics_feedback_rollouts (rsr_feedback.hpp); fb_gain null: open loop, r.ctrl is applied as it stands
+  const float* fb_gain;              // [M][T][nu][2 nv], or with fb_per_sample [M][K][T][nu][2 nv]
+  const float* fb_qpos;              // [..][T][nq]
+  const float* fb_qvel;              // [..][T][nv]
+  float* ctrl_out;                   // [M][K][T][nu] the applied ctrl, or null
+  int fb_per_sample;                 // the three feedback rows are per sample
+  int fb_clamp;                      // clamp to actuator_ctrlrange where actuator_ctrllimited
+};
 
 // The physics ops of a family unit's launch entry (launch_physics, rsr_physics_kernels.hpp).  An entry takes its op as an int, of
 // enum Op (rsr_launch.hpp) or of this enum: these start above enum Op's, so that no value names two ops.  A new op is a member
@@ -126,16 +140,19 @@ enum PhysOp {
   OP_PHYS_INVERSE,       // rsr_physics_inverse (inv): grid = envs or listed envs (inv.ids)
   OP_PHYS_SAMPLE,        // rsr_physics_sample_rollouts (p, r, K): grid = envs x K, or listed envs (p.ids) x K; r.ctrl [M][K][T][nu],
                          // the trajectory rows [M][K][T][w]
+  OP_PHYS_SWEEP,         // rsr_physics_param_rollouts and rsr_physics_feedback_rollouts (p, r, sw): grid and rows as OP_PHYS_SAMPLE's;
+                         // r.ctrl [M][K][T][nu] or [M][T][nu]
 };
 // The physics ops' arguments (Launch::ph), one field per op that needs its own
 struct PhysLaunch {
-  PhysArgs p;           // OP_PHYS_FORWARD, OP_PHYS_STEP, OP_PHYS_ROLLOUT, OP_PHYS_TRANSITION, OP_PHYS_SAMPLE
-  RollArgs r;           // OP_PHYS_ROLLOUT, OP_PHYS_SAMPLE
+  PhysArgs p;           // OP_PHYS_FORWARD, OP_PHYS_STEP, OP_PHYS_ROLLOUT, OP_PHYS_TRANSITION, OP_PHYS_SAMPLE, OP_PHYS_SWEEP
+  RollArgs r;           // OP_PHYS_ROLLOUT, OP_PHYS_SAMPLE, OP_PHYS_SWEEP
   DynArgs d;            // OP_PHYS_DYNAMICS
   ConArgs c;            // OP_PHYS_CONSTRAINT
   FdArgs fd;            // OP_PHYS_TRANSITION
   InvArgs inv;          // OP_PHYS_INVERSE
   int K;                // OP_PHYS_SAMPLE: the control sequences per env
+  SweepArgs sw;         // OP_PHYS_SWEEP
   Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
 };
 

@@ -1,9 +1,9 @@
 // rsr_physics_kernels.hpp -- the physics-level kernels (include/rsr_physics.h): each family unit instantiates them for its Dims,
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
 // forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp), constraint_kernel (rsr_constraint.hpp), transition_kernel
-// (rsr_transition.hpp), inverse_kernel (rsr_inverse.hpp) and sample_kernel (rsr_sample.hpp); all but dynamics_kernel and inverse_kernel
-// are instantiated plain and with applied forces: the applied kernels take the handle's Applied buffers as one more argument and
-// pass forward<C> their env's rows as its force stage (rsr_applied.hpp).
+// (rsr_transition.hpp), inverse_kernel (rsr_inverse.hpp), sample_kernel (rsr_sample.hpp) and sweep_kernel (rsr_sweep.hpp); all but
+// dynamics_kernel and inverse_kernel are instantiated plain and with applied forces: the applied kernels take the handle's Applied
+// buffers as one more argument and pass forward<C> their env's rows as its force stage (rsr_applied.hpp).
 #pragma once
 #include "../rsr_launch.hpp"
 #include "rsr_sensors.hpp"
@@ -13,6 +13,7 @@
 #include "rsr_transition.hpp"
 #include "rsr_inverse.hpp"
 #include "rsr_sample.hpp"
+#include "rsr_sweep.hpp"
 
 namespace rsr {
 
@@ -179,6 +180,7 @@ int launch_physics(int op, const Launch& x) {
     case OP_PHYS_CONSTRAINT: return ap ? go(constraint_kernel<C, WAVES, Applied>, ph.c, ph.ap) : go(constraint_kernel<C, WAVES>, ph.c);
     case OP_PHYS_INVERSE: return go(inverse_kernel<C, WAVES>, ph.inv);
     case OP_PHYS_SAMPLE: return ap ? go(sample_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.K, ph.ap) : go(sample_kernel<C, WAVES>, ph.p, ph.r, ph.K);
+    case OP_PHYS_SWEEP: return ap ? go(sweep_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.sw, ph.ap) : go(sweep_kernel<C, WAVES>, ph.p, ph.r, ph.sw);
     default: return -1;
   }
 }

@@ -14,7 +14,7 @@
 // just loaded into ctrl + gain (x (-) x_ref) on the sample's own state, at the start and at every control-step boundary.  The
 // branch is wave-uniform (a kernel argument), and with it off the kernel runs the statements it ran before.
 #pragma once
-#include "rsr_sweep_launch.hpp"
+#include "../rsr_launch.hpp"
 #include "rsr_sensors.hpp"
 #include "rsr_applied.hpp"
 #include "rsr_feedback.hpp"

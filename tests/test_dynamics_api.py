@@ -85,7 +85,7 @@ def test_argument_checks_come_before_device_work():
 
 def test_the_dynamics_op_is_an_ordinary_op():
     """The op is a member of the physics op enum and its arguments a field of the physics launch struct, like every other physics
-    op's (all eight are checked here); nothing is carried through another op's arguments.  The enum, the struct, the kernel, its
+    op's (all nine are checked here); nothing is carried through another op's arguments.  The enum, the struct, the kernel, its
     arguments' type and its buffer layout are in the physics layer: no source directly under csrc/ names a physics op."""
     import re
     csrc = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
@@ -106,7 +106,7 @@ def test_the_dynamics_op_is_an_ordinary_op():
     # op: the field it owns (forward and step share the one struct physics_kernel takes), and every field its case may read
     ops = {"FORWARD": ("PhysArgs p", "p ap"), "STEP": ("PhysArgs p", "p ap"), "ROLLOUT": ("RollArgs r", "p r ap"),
            "DYNAMICS": ("DynArgs d", "d"), "CONSTRAINT": ("ConArgs c", "c ap"), "TRANSITION": ("FdArgs fd", "p fd ap"),
-           "INVERSE": ("InvArgs inv", "inv"), "SAMPLE": ("int K", "p r K ap")}
+           "INVERSE": ("InvArgs inv", "inv"), "SAMPLE": ("int K", "p r K ap"), "SWEEP": ("SweepArgs sw", "p r sw ap")}
     assert sorted(re.findall(r"\bOP_PHYS_(\w+)", enum)) == sorted(ops) and "switch (op)" in lp
     assert len(re.findall(r"\bcase \w+:", lp)) == len(ops)                   # one case per op, nothing else
     for op, (own, reads) in ops.items():

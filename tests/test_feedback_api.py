@@ -69,12 +69,18 @@ def _body(src, name):
 
 def test_refusals_come_before_device_work():
     """Every refusal comes ahead of the one device call (by source order, as a handle needs a device), and the call allocates
-    nothing: the handle owns no buffer for it.  It launches through the parameter rollout's sweep_launch, which is as it was."""
+    nothing: the handle owns no buffer for it.  Its own checks, then the tail it shares with the parameter rollout's entry."""
     src = _read("physics", "rsr_physics.hip")
-    call = _body(src, "int rsr_physics_feedback_rollouts")
+    entry, tail = _body(src, "int rsr_physics_feedback_rollouts"), _body(src, "static int sweep_rollouts")
+    first = "if (const int rc = sample_grid(p, env_ids, count, sw.K, T, nsteps, out, who, &grid)) return rc;"
+    assert first in tail
+    tail = tail.replace(first, _body(src, "static int sample_grid"))                       # the shared refusals, read in their place
+    assert entry.rstrip().endswith('return sweep_rollouts(p, env_ids, count, ctrl, params, sw, T, nsteps, out, hip_stream, "rsr_physics_feedback_rollouts");')
+    assert "OP_PHYS_" not in entry
+    call = entry + tail
     dev = ("hipSetDevice", "hipMalloc", "hipMemset", "hipMemcpy", "zeroed_once", "launch(")
     first_dev = min(call.index(k) for k in dev if k in call)
-    assert first_dev == call.index("sweep_launch(") + len("sweep_")
+    assert first_dev == call.index("physics_launch(") + len("physics_")
     checks = ("!p)", "!ctrl)", "!fb || !fb->gain || !fb->qpos_ref || !fb->qvel_ref)", "!out)",
               "!ctrl_out && !(out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata)",
               "K < 1", "T < 1", "nsteps < 1", "flags & ~(RSR_FB_CTRL_PER_SAMPLE | RSR_FB_PER_SAMPLE | RSR_FB_CLAMP)", "env_count(",
@@ -82,14 +88,14 @@ def test_refusals_come_before_device_work():
               "f >= RSR_DR_BODY_IPOS")
     at = [call.index(c) for c in checks]
     assert all(i < first_dev for i in at), [c for c, i in zip(checks, at) if i >= first_dev]
-    assert call.count("RSR_ERR_ARG") == 9 and call.count("RSR_ERR_UNSUPPORTED") == 1 and call.count("sweep_launch(") == 1
-    for k in ("hipMalloc", "hipMemset", "hipMemcpy", "hipFree", "zeroed_once", "_buffer", "new ", "std::vector", "OP_PHYS_"):
+    assert call.count("RSR_ERR_ARG") == 9 and call.count("RSR_ERR_UNSUPPORTED") == 1 and call.count("physics_launch(") == 1
+    for k in ("hipMalloc", "hipMemset", "hipMemcpy", "hipFree", "zeroed_once", "_buffer", "new ", "std::vector"):
         assert k not in call, k
     assert "_alloc" not in src and src.count("static int zeroed_once(") == 1
     for k in ("sw.fb_gain = fb->gain", "sw.fb_qpos = fb->qpos_ref", "sw.fb_qvel = fb->qvel_ref", "sw.ctrl_out = ctrl_out",
               "sw.fb_per_sample = (flags & RSR_FB_PER_SAMPLE) != 0", "sw.fb_clamp = (flags & RSR_FB_CLAMP) != 0",
               "sw.ctrl_per_sample = (flags & RSR_FB_CTRL_PER_SAMPLE) != 0"):
-        assert k in call and call.index(k) < first_dev, k
+        assert k in entry and entry.index(k) < entry.index("sweep_rollouts("), k          # the entry's own, ahead of the shared tail
     # the open-loop call zero-initialises the arguments and sets no feedback member
     assert "rsr::SweepArgs sw{};" in call
     assert "rsr::SweepArgs sw{};" in _body(src, "int rsr_physics_param_rollouts") and "fb_" not in _body(src, "int rsr_physics_param_rollouts")
@@ -108,7 +114,7 @@ def test_the_stage_is_a_header_of_its_own_called_twice():
     assert body.count("__builtin_fmaf(") == 2 and body.index("__shfl(dv, i)") < body.index("if (lane < C::NU)")
     assert "m.actuator_ctrllimited[j]" in body and "m.actuator_ctrlrange[2 * j]" in body and "m.actuator_ctrlrange[2 * j + 1]" in body
     assert "sw.fb_clamp" in body and "if (sw.ctrl_out) sw.ctrl_out[out_row * C::NU + lane] = u;" in body
-    hdr = _read("physics", "rsr_sweep_launch.hpp")
+    hdr = _read("physics", "rsr_physics.hpp")
     for k in ("const float* fb_gain;", "const float* fb_qpos;", "const float* fb_qvel;", "float* ctrl_out;", "int fb_per_sample;", "int fb_clamp;"):
         assert k in hdr, k
     kern = re.sub(r"//.*", "", _read("physics", "rsr_sweep.hpp"))
@@ -121,8 +127,8 @@ def test_the_stage_is_a_header_of_its_own_called_twice():
     assert k.index("s.ctrl[lane] = r.ctrl[") < first < k.index("const int total") and k.index("if (++t < r.T)") < k.index("s.ctrl[lt] = r.ctrl[") < second
     assert "(size_t)b * r.T + t, lt);" in calls[1] and "(size_t)b * r.T, lane);" in calls[0]
     assert calls[0].count("sw.fb_per_sample ? (size_t)b : (size_t)slot") == 1 == calls[1].count("sw.fb_per_sample ? (size_t)b : (size_t)slot")
-    # the family units and the pinned headers do not know
-    for f in ("rsr_physics.hpp", "rsr_physics_kernels.hpp", "rsr_sample.hpp", "rsr_transition.hpp"):
+    # the family units and the other ops' headers do not know
+    for f in ("rsr_physics_kernels.hpp", "rsr_sample.hpp", "rsr_transition.hpp"):
         assert "feedback" not in _read("physics", f).lower(), f
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):

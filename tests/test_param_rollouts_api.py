@@ -1,5 +1,5 @@
 """Parameter rollouts of the physics layer (rsr_physics_param_rollouts, Physics.param_rollouts, tuning.RolloutLoss), host side
-only: the ABI, the sweep units and their dispatch beside the pinned ops, the Python surface and the tuning helper's reduction.
+only: the ABI, the launch as an op of the physics layer, the Python surface and the tuning helper's reduction.
 The kernel is covered by tests/test_param_rollouts_gpu.py."""
 import ctypes as C
 import inspect
@@ -66,54 +66,60 @@ def _body(src, name):
 
 def test_refusals_come_before_device_work():
     """Every refusal comes ahead of every device call (by source order, as a handle needs a device), and the call allocates
-    nothing: the handle owns no buffer for it."""
+    nothing: the handle owns no buffer for it.  The entry's own checks, then the tail the two sweep entries share, which opens
+    with the refusals of all three (slot, sample) rollouts (sample_grid)."""
     src = _read("physics", "rsr_physics.hip")
-    call = _body(src, "int rsr_physics_param_rollouts")
+    entry, tail = _body(src, "int rsr_physics_param_rollouts"), _body(src, "static int sweep_rollouts")
+    first = "if (const int rc = sample_grid(p, env_ids, count, sw.K, T, nsteps, out, who, &grid)) return rc;"
+    assert re.findall(r"^  (?:if|for|return)\b.*", tail, re.M)[0].strip() == first          # the tail's first statement
+    tail = tail.replace(first, _body(src, "static int sample_grid"))                       # ... read in its place
+    assert entry.rstrip().endswith('return sweep_rollouts(p, env_ids, count, ctrl, params, sw, T, nsteps, out, hip_stream, "rsr_physics_param_rollouts");')
+    assert entry.count("sweep_rollouts(") == 1 and "OP_PHYS_" not in entry
+    call = entry + tail
     dev = ("hipSetDevice", "hipMalloc", "hipMemset", "hipMemcpy", "zeroed_once", "launch(")
     first_dev = min(call.index(k) for k in dev if k in call)
-    assert first_dev == call.index("sweep_launch(") + len("sweep_")
+    assert first_dev == call.index("physics_launch(") + len("physics_")
     checks = ("!p)", "!ctrl)", "!out ||", "out->qpos || out->qvel || out->time || out->actuator_force || out->ncon || out->sensordata)",
               "K < 1", "T < 1", "nsteps < 1", "flags & ~RSR_PR_CTRL_PER_SAMPLE", "env_count(", "out->sensordata && p->nsd == 0",
               "grid > INT32_MAX", "(int64_t)T * nsteps > INT32_MAX", "RSR_ERR_UNSUPPORTED", "f >= RSR_DR_BODY_IPOS")
     at = [call.index(c) for c in checks]
-    assert all(i < first_dev for i in at), [c for c, i in zip(checks, at) if i >= first_dev]
+    assert at[:-1] == sorted(at[:-1]) and all(i < first_dev for i in at), [c for c, i in zip(checks, at) if i >= first_dev]      # (today's order)
     assert "(int64_t)n * K" in call and call.count("RSR_ERR_ARG") == 7 and call.count("RSR_ERR_UNSUPPORTED") == 1
-    for k in ("hipMalloc", "hipMemset", "hipMemcpy", "hipFree", "zeroed_once", "_buffer", "new ", "std::vector", "OP_PHYS_"):
+    for k in ("hipMalloc", "hipMemset", "hipMemcpy", "hipFree", "zeroed_once", "_buffer", "new ", "std::vector"):
         assert k not in call, k
     assert "_alloc" not in src and src.count("static int zeroed_once(") == 1
-    assert call.index("physics_args(") < call.index("x.ph.r = rsr::RollArgs{ctrl, T, ") < call.index("sweep_launch(")
+    # the tail names the one op, and every message is the entry's: built from `who`
+    assert re.findall(r"\bOP_PHYS_\w+", tail) == ["OP_PHYS_SWEEP"] and "rsr_physics_" not in tail
+    assert tail.count("std::string(who) + ") == 3 and tail.count("fail(") == 3
+    assert tail.index("physics_args(") < tail.index("x.ph.r = rsr::RollArgs{ctrl, T, ") < tail.index("x.ph.sw = sw;") < tail.index("physics_launch(")
+    assert "counted(p, physics_launch(p, rsr::OP_PHYS_SWEEP, x, who))" in tail
 
 
-def test_the_launch_has_units_of_its_own_beside_the_pinned_ops():
+def test_the_launch_is_an_ordinary_op():
     from rsr_mjx_amd import build
-    units = dict(build.UNITS)
-    assert len(build.UNITS) == 8 and len(units) == 8
-    for fam, src in (("cube", "rsr_cube.hip"), ("tshape", "rsr_tshape.hip"), ("go2", "rsr_go2.hip")):
-        sweep = os.path.join("physics", f"rsr_sweep_{fam}.hip")
-        assert units[sweep] == units[src], fam                     # the family unit's flags: the bit-identity tests compare across them
-        text = _read(sweep)
-        assert '#include "rsr_sweep.hpp"' in text and re.findall(r"\bint (launch_\w+)\(", text.replace("static int", "")) == [f"launch_sweep_{fam}"]
-        assert "sizeof(Smem<C>)" in text and "sweep_kernel<C, " in text and "Applied>" in text
-        assert re.findall(r"\b(\w+_kernel)\b", re.sub(r"//.*", "", text)) == ["sweep_kernel"] * 2, fam
-    assert units[os.path.join("physics", "rsr_sweep_tshape.hip")] == ["-fno-slp-vectorize"] == units[os.path.join("physics", "rsr_sweep_go2.hip")]
-    # the same WAVES and the same Dims pick as the family units
-    pick = lambda text: re.findall(r"<(\w+Dims), (RSR_\w+)>", text)
-    assert pick(_read("physics", "rsr_sweep_go2.hip")) == pick(_read("rsr_go2.hip"))
-    assert "x.env_kind == ENV_GO2_HANDSTAND" in _read("physics", "rsr_sweep_go2.hip") and "if (x.hfield)" in _read("physics", "rsr_sweep_go2.hip")
-    for fam in ("cube", "tshape"):
-        assert "RSR_WAVES_PER_EU" in _read("physics", f"rsr_sweep_{fam}.hip") and "launch_physics<C, RSR_WAVES_PER_EU>" in _read(f"rsr_{fam}.hip")
-    # the arguments and the three prototypes: a header of their own, not the pinned ones
-    hdr = _read("physics", "rsr_sweep_launch.hpp")
-    assert "struct SweepArgs" in hdr and "const float* leaf[RSR_DR_COUNT];" in hdr
-    assert re.findall(r"\bint (launch_sweep_\w+)\(const Launch& x, const SweepArgs& sw\);", hdr) == ["launch_sweep_cube", "launch_sweep_tshape", "launch_sweep_go2"]
-    for pinned in ("rsr_physics.hpp", "rsr_physics_kernels.hpp", "rsr_sample.hpp"):
-        text = _read("physics", pinned)
-        assert "sweep" not in text.lower() and "SweepArgs" not in text, pinned
-    # the host picks the unit by the model's family, in one place
+    assert len(build.UNITS) == 5 and len(dict(build.UNITS)) == 5
+    physics = os.listdir(os.path.join(CSRC, "physics"))
+    assert not [f for f in physics if f.startswith("rsr_sweep_")] and "rsr_sweep.hpp" in physics
+    # the host sends the op like every other: no entry of its own per family, no second family switch
     host = _read("physics", "rsr_physics.hip")
-    pickfn = _body(host, "static int sweep_launch")
-    assert "p->b->model->spec->family" in pickfn.replace("ph->", "p->") and host.count("launch_sweep_") == 3 and pickfn.count("launch_sweep_") == 3
-    assert "hipGetLastError()" in pickfn and "RSR_ERR_HIP" in pickfn
+    assert set(re.findall(r"\b(\w*launch\w*)\(", host)) == {"launch", "launch_args", "physics_launch"}
+    assert "spec->family" not in host.replace("spec->family != rsr::FAMILY_GO2", "")
+    assert "switch (ph->b->model" not in host and "FAMILY_CUBE" not in host and "FAMILY_TSHAPE" not in host
+    # the arguments beside the other ops'
+    phys = _read("physics", "rsr_physics.hpp")
+    assert "struct SweepArgs" in phys and "const float* leaf[RSR_DR_COUNT];" in phys
+    assert re.search(r"\bSweepArgs sw;", re.search(r"struct PhysLaunch \{(.*?)\};", phys, re.S).group(1))
+    # the op's own case, up to the next label: its kernel, plain and applied, with p, r and sw, and no other kernel
+    kernels = _read("physics", "rsr_physics_kernels.hpp")
+    assert '#include "rsr_sweep.hpp"' in kernels
+    lp = kernels[kernels.index("int launch_physics("):]
+    case = re.search(r"case OP_PHYS_SWEEP:(.*?)\n\s*(?:case |default:)", lp, re.S).group(1)
+    assert case.count("sweep_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.sw, ph.ap)") == 1 and case.count("sweep_kernel<C, WAVES>, ph.p, ph.r, ph.sw)") == 1
+    assert re.findall(r"\b\w+_kernel\b", case) == ["sweep_kernel"] * 2 and lp.count("sweep_kernel") == 2
+    assert lp.index("case OP_PHYS_SAMPLE:") < lp.index("case OP_PHYS_SWEEP:") < lp.index("default:")
+    assert lp.count("hipLaunchKernelGGL(") == 1 and "op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>)" in lp
+    for hdr in ("rsr_sweep.hpp", "rsr_feedback.hpp"):
+        assert '#include "../rsr_launch.hpp"' in _read("physics", hdr), hdr
     # nothing directly under csrc/ knows; the hashed sources are the parent's
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
@@ -122,11 +128,11 @@ def test_the_launch_has_units_of_its_own_beside_the_pinned_ops():
     import bench
     import parity_envelopes as PE
     assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
-    enum = re.sub(r"//.*", "", re.search(r"enum PhysOp \{(.*?)\};", _read("physics", "rsr_physics.hpp"), re.S).group(1))
-    assert len(re.findall(r"\bOP_PHYS_\w+", enum)) == 8
+    enum = re.sub(r"//.*", "", re.search(r"enum PhysOp \{(.*?)\};", phys, re.S).group(1))
+    assert len(re.findall(r"\bOP_PHYS_\w+", enum)) == 9 and "OP_PHYS_SWEEP" in enum
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
-    sec = design[design.index("### 4j."):]
-    assert "op in all but the enum" in sec and "PhysOp" in sec
+    sec = design[design.index("### 4j."):design.index("### 4k.")]
+    assert "**Dispatch: an ordinary op.**" in sec and "OP_PHYS_SWEEP" in sec and "PhysLaunch::sw" in sec
 
 
 def test_the_kernel_is_the_sample_loop_with_one_stage_more():

@@ -54,9 +54,13 @@ def _body(src, name):
 
 def test_refusals_come_before_device_work():
     """Every refusal of rsr_physics_sample_rollouts is RSR_ERR_ARG ahead of every device call (by source order, as a handle needs
-    a device), and the call allocates nothing: the handle owns no buffer for it."""
+    a device), and the call allocates nothing: the handle owns no buffer for it.  The refusals it shares with the two sweep
+    entries are a helper's (sample_grid), read here in the place of its call."""
     src = open(os.path.join(CSRC, "physics", "rsr_physics.hip")).read()
     call = _body(src, "int rsr_physics_sample_rollouts")
+    shared = "if (const int rc = sample_grid(p, env_ids, count, K, T, nsteps, out, who, &grid)) return rc;"
+    assert call.count(shared) == 1
+    call = call.replace(shared, _body(src, "static int sample_grid"))
     dev = ("hipSetDevice", "hipMalloc", "hipMemset", "hipMemcpy", "zeroed_once", "launch(")
     first_dev = min(call.index(k) for k in dev if k in call)
     assert "launch(" in call and first_dev == call.index("physics_launch(") + len("physics_")
