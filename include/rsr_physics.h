@@ -21,6 +21,8 @@
  *                          state, in a buffer of its own.
  *   rsr_physics_transition_fd <- mjd_transitionFD / jax.jacobian(mjx.step): finite-difference Jacobians A, B, C, D of
  *                          rsr_physics_step about the record's current state, in a buffer of its own.
+ *   rsr_physics_trajectory_fd <- mjd_transitionFD at every step of a nominal rollout / vmap(jax.jacobian(mjx.step)) over the
+ *                          states of lax.scan(mjx.step): A_t, B_t, C_t, D_t for t < T in two launches; the record is read only.
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
@@ -304,6 +306,36 @@ enum rsr_transition_field { RSR_T_COLUMNS = 0, RSR_T_STATES_X, RSR_T_STATES_Y, R
 int rsr_physics_transition_fd(rsr_physics* p, const int32_t* env_ids, int count, int nsteps, float eps, int flags, void* hip_stream);
 /* Zero-copy view (as rsr_physics_view) of the transition buffer or of one half of the states buffer.  RSR_ERR_ARG for an unknown id. */
 int rsr_physics_transition_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);
+
+/* Transition Jacobians along a trajectory, for the backward pass of iLQR, time-varying LQR, linearised MPC and EKF smoothing over
+ * a log: what T rounds of rsr_physics_transition_fd then rsr_physics_step would give, without advancing the env and with every
+ * column of every control step in one launch.  M = count, or num_envs with env_ids NULL; slot s is env e = env_ids[s], and an id
+ * may appear more than once.  Rows of ctrl and of out are indexed by slot s, the position in env_ids, not by env id.
+ * ctrl: device float32 [M, T, nu].
+ * Nominal trajectory: from the record of env e as it stands (qpos, qvel, qacc_warmstart, time), ctrl[s, t] then nsteps x mjx.step
+ * for t = 0 .. T-1, with env e's per-env leaves and, while they are on, its applied forces (held for all T control steps): bit for
+ * bit what rsr_physics_sample_rollouts with K = 1 records.  out->qpos [M, T+1, nq] and out->qvel [M, T+1, nv] are optional (NULL:
+ * not recorded): row 0 is the start state, row t+1 the state after control step t.
+ * out->columns, required: [M, T, ncol, 2 nv + nsensordata] with ncol = 2 nv + nu; the rows are tight, not padded to
+ * RSR_MAX_SENSORDATA (the buffer is the caller's).  Block (s, t) equals, bit for bit, the first 2 nv + nsensordata entries of every
+ * RSR_T_COLUMNS row that rsr_physics_transition_fd(nsteps, eps, flags) would write on a record advanced by t calls of
+ * rsr_physics_step(ctrl[:, 0 .. t-1], nsteps) and holding ctrl[s, t] as its ctrl, the warm start the nominal run carried to step t
+ * included: both perturbed runs of a column start from it, as rsr_physics_transition_fd starts from the record's.  Columns, eps and
+ * the differences are those of rsr_physics_transition_fd.
+ * flags: RSR_FD_CENTERED or 0; RSR_FD_STATES and unknown bits are RSR_ERR_ARG.
+ * Two launches on hip_stream: the nominal run, one wavefront per slot, then one wavefront per (slot, t, column).  The record is
+ * read only.  Only the buffers of out and the handle's nominal scratch are written: the side buffer, RSR_P_SENSORDATA, the
+ * dynamics, constraint, transition, states and inverse buffers, the batch's own leaf tensors and the PRNG keys are untouched.
+ * The nominal scratch holds qpos | qvel | qacc_warmstart before each control step, M T (nq + 2 nv) floats.  It is allocated by the
+ * first call that needs it and replaced only by a call that needs more, which waits for the device first (launches in flight read
+ * it); rsr_physics_destroy frees it.  Two calls on one handle must not overlap on different streams: they share the scratch.
+ * env_ids: device int32 [count], or NULL for every env (count is ignored); an id outside [0, num_envs) runs nothing and its slot's
+ * rows in all three buffers are left alone.  RSR_ERR_ARG, checked before any device work: null handle, null ctrl, null out or null
+ * out->columns, T < 1, nsteps outside [1, 2^30), eps not finite or <= 0, bad flags, env_ids with count < 1, T nsteps or
+ * M T ncol at or above 2^31. */
+typedef struct rsr_trajectory_fd_out { float* columns; float* qpos; float* qvel; } rsr_trajectory_fd_out;
+int rsr_physics_trajectory_fd(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int T, int nsteps,
+                              float eps, int flags, const rsr_trajectory_fd_out* out, void* hip_stream);
 
 /* Inverse dynamics (mj_inverse / mjx.inverse): given an acceleration per env, the generalised force that must have acted
  * (data.qfrc_inverse).  One launch evaluates the record's current state -- its qpos / qvel / ctrl with the batch's per-env

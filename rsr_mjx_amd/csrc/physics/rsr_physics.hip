@@ -2,7 +2,8 @@
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse), sampled rollouts (rsr_physics_sample_rollouts), parameter
-// rollouts (rsr_physics_param_rollouts) and closed-loop rollouts (rsr_physics_feedback_rollouts).  Every launch is a physics op
+// rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts) and the transition Jacobians along a
+// trajectory (rsr_physics_trajectory_fd).  Every launch is a physics op
 // (rsr::PhysOp) sent through physics_launch; the kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,8 @@ struct rsr_physics {
   float* fd = nullptr;    // the transition buffer [n][FdLayout::env], allocated on first use (fd_buffers)
   float* fd_states = nullptr;  // the states buffer of RSR_FD_STATES, allocated on first request (fd_buffers)
   float* inv = nullptr;   // the inverse buffer [n][InvLayout::stride], allocated on first use (inv_buffer)
+  float* nominal = nullptr;  // the nominal scratch of rsr_physics_trajectory_fd [M][T][nq + 2 nv], grown on demand (nominal_scratch)
+  size_t nominal_floats = 0;
 };
 
 // `*slot`, a buffer of the handle, on first use: `bytes` of device memory, zeroed; once there it never moves.  A failure is reported
@@ -77,6 +80,7 @@ extern "C" void rsr_physics_destroy(rsr_physics* p) {
   if (p->fd) (void)hipFree(p->fd);
   if (p->fd_states) (void)hipFree(p->fd_states);
   if (p->inv) (void)hipFree(p->inv);
+  if (p->nominal) (void)hipFree(p->nominal);
   delete p;
 }
 
@@ -447,6 +451,46 @@ extern "C" int rsr_physics_transition_view(rsr_physics* p, int field, void** dev
   if (field == RSR_T_COLUMNS) return view_out(p, p->fd, FL.env, FL.env, dev_ptr, shape, stride);
   if (field == RSR_T_STATES_X) return view_out(p, p->fd_states, xrow, xrow, dev_ptr, shape, stride);
   return view_out(p, p->fd_states + (size_t)p->b->n * xrow, yrow, yrow, dev_ptr, shape, stride);
+}
+
+// The nominal scratch, at least `floats` long: allocated by the first call that needs it, and replaced only by a call that needs
+// more, after a wait for the device (launches in flight read the one there).  Not zeroed: every row read was written by the same call.
+static int nominal_scratch(rsr_physics* p, size_t floats, const char* who) {
+  if (floats <= p->nominal_floats) return RSR_OK;
+  HIPCHK(hipSetDevice(p->b->device));
+  if (p->nominal) HIPCHK(hipDeviceSynchronize());
+  float* buf = nullptr;
+  if (hipMalloc(&buf, floats * sizeof(float)) != hipSuccess) return fail(RSR_ERR_NOMEM, std::string(who) + ": hipMalloc(nominal scratch)");
+  if (p->nominal) (void)hipFree(p->nominal);
+  p->nominal = buf;
+  p->nominal_floats = floats;
+  return RSR_OK;
+}
+
+// Two launches on the caller's stream: the nominal trajectory, one wave per slot, then every column of every control step.
+extern "C" int rsr_physics_trajectory_fd(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int T, int nsteps,
+                                         float eps, int flags, const rsr_trajectory_fd_out* out, void* hip_stream) {
+  const char* who = "rsr_physics_trajectory_fd";
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_trajectory_fd: null handle");
+  if (!ctrl) return fail(RSR_ERR_ARG, "rsr_physics_trajectory_fd: null ctrl");
+  if (!out || !out->columns) return fail(RSR_ERR_ARG, "rsr_physics_trajectory_fd: null out, or null out->columns");
+  if (T < 1) return fail(RSR_ERR_ARG, "rsr_physics_trajectory_fd: T must be >= 1");
+  if (nsteps < 1 || nsteps > INT32_MAX / 2) return fail(RSR_ERR_ARG, "rsr_physics_trajectory_fd: nsteps must lie in [1, 2^30)");
+  if (!std::isfinite(eps) || !(eps > 0.0f)) return fail(RSR_ERR_ARG, "rsr_physics_trajectory_fd: eps must be finite and > 0");
+  if (flags & ~RSR_FD_CENTERED) return fail(RSR_ERR_ARG, "rsr_physics_trajectory_fd: only RSR_FD_CENTERED is accepted");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, who, &n)) return rc;
+  const rsr_dims& d = p->b->model->dims;
+  const rsr::FdLayout FL = rsr::fd_layout(d.nq, d.nv, d.nu);
+  const int64_t cells = (int64_t)n * T;           // (slot, t): one row of the scratch each; one wave per (slot, t, column)
+  if ((int64_t)T * nsteps > INT32_MAX || cells > INT32_MAX || cells * FL.ncol > INT32_MAX)
+    return fail(RSR_ERR_ARG, "rsr_physics_trajectory_fd: T x nsteps and envs x T x columns must stay below 2^31");
+  if (const int rc = nominal_scratch(p, (size_t)cells * (d.nq + 2 * d.nv), who)) return rc;
+  rsr::Launch x = physics_args(p, nullptr, env_ids, n, nsteps, hip_stream);
+  x.ph.tj = rsr::TrajArgs{ctrl, T, p->nominal, out->qpos, out->qvel, out->columns, eps, flags};
+  if (const int rc = physics_launch(p, rsr::OP_TRAJ_NOMINAL, x, who)) return rc;
+  x.grid = (int)(cells * FL.ncol);
+  return physics_launch(p, rsr::OP_TRAJ_FD, x, who);
 }
 
 // the inverse buffer, on first use

@@ -1,4 +1,4 @@
-// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics, constraint, transition and inverse buffer) its ops (PhysOp) and their launch
+// rsr_physics.hpp -- the physics layer's buffer layouts (side, dynamics, constraint, transition and inverse buffer, nominal scratch) its ops (PhysOp) and their launch
 // arguments, one struct per op that needs its own (host and device).
 #pragma once
 #include "../../../include/rsr_physics.h"
@@ -126,6 +126,18 @@ struct SweepArgs {
   int fb_per_sample;                 // the three feedback rows are per sample
   int fb_clamp;                      // clamp to actuator_ctrlrange where actuator_ctrllimited
 };
+// rsr_physics_trajectory_fd (rsr_trajectory.hpp), both of its launches (PhysLaunch::tj).  The nominal scratch, per (slot, t),
+// floats: qpos [nq] | qvel [nv] | qacc_warmstart [nv], the state before control step t: written by nominal_kernel, read by
+// trajectory_fd_kernel.  Every row of ctrl and of the caller's buffers is indexed by slot.
+struct TrajArgs {
+  const float* ctrl;    // [M][T][nu]
+  int T;
+  float* nominal;       // the handle's scratch [M][T][nq + 2 nv]
+  float *qpos, *qvel;   // the nominal rows [M][T+1][nq] / [M][T+1][nv], each null = not recorded (OP_TRAJ_NOMINAL)
+  float* columns;       // [M][T][ncol][2 nv + nsd], tight rows (OP_TRAJ_FD)
+  float eps;
+  int flags;            // RSR_FD_CENTERED or 0
+};
 
 // The physics ops of a family unit's launch entry (launch_physics, rsr_physics_kernels.hpp).  An entry takes its op as an int, of
 // enum Op (rsr_launch.hpp) or of this enum: these start above enum Op's, so that no value names two ops.  A new op is a member
@@ -142,10 +154,12 @@ enum PhysOp {
                          // the trajectory rows [M][K][T][w]
   OP_PHYS_SWEEP,         // rsr_physics_param_rollouts and rsr_physics_feedback_rollouts (p, r, sw): grid and rows as OP_PHYS_SAMPLE's;
                          // r.ctrl [M][K][T][nu] or [M][T][nu]
+  OP_TRAJ_NOMINAL,       // rsr_physics_trajectory_fd, first launch (p, tj): grid = envs or listed envs (p.ids)
+  OP_TRAJ_FD,            // rsr_physics_trajectory_fd, second launch (p, tj): grid = envs x T x columns, or listed envs (p.ids) x T x columns
 };
 // The physics ops' arguments (Launch::ph), one field per op that needs its own
 struct PhysLaunch {
-  PhysArgs p;           // OP_PHYS_FORWARD, OP_PHYS_STEP, OP_PHYS_ROLLOUT, OP_PHYS_TRANSITION, OP_PHYS_SAMPLE, OP_PHYS_SWEEP
+  PhysArgs p;           // OP_PHYS_FORWARD, OP_PHYS_STEP, OP_PHYS_ROLLOUT, OP_PHYS_TRANSITION, OP_PHYS_SAMPLE, OP_PHYS_SWEEP, OP_TRAJ_*
   RollArgs r;           // OP_PHYS_ROLLOUT, OP_PHYS_SAMPLE, OP_PHYS_SWEEP
   DynArgs d;            // OP_PHYS_DYNAMICS
   ConArgs c;            // OP_PHYS_CONSTRAINT
@@ -153,6 +167,7 @@ struct PhysLaunch {
   InvArgs inv;          // OP_PHYS_INVERSE
   int K;                // OP_PHYS_SAMPLE: the control sequences per env
   SweepArgs sw;         // OP_PHYS_SWEEP
+  TrajArgs tj;          // OP_TRAJ_NOMINAL, OP_TRAJ_FD
   Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
 };
 

@@ -24,6 +24,9 @@
                                                                                            state; Physics.contact_forces())
     mjd_transitionFD / jax.jacobian(mjx.step)    ->  Physics.transition_fd()              (finite differences of step at a given
                                                                                            eps: fd_A, fd_B, fd_C, fd_D)
+    mjd_transitionFD along a nominal rollout     ->  Physics.trajectory_fd(ctrl [M, T, nu]) (A_t, B_t, C_t, D_t at every control
+                                                                                           step of the trajectory ctrl gives from
+                                                                                           the current state; the record stays)
     mj_inverse / mjx.inverse (data.qfrc_inverse)  ->  Physics.inverse(qacc)               (the force behind a given acceleration,
                                                                                            no solve: qfrc_inverse)
 
@@ -101,6 +104,7 @@ class Physics:
         self._sample_ctrl_in = None                # the control sequences of sample_rollouts()'s last launch
         self._param_in = None                      # the control sequences and leaf tensors of param_rollouts()'s last launch
         self._feedback_in = None                   # the inputs of feedback_rollouts()'s last launch
+        self._trajectory_in = None                 # the control sequences of trajectory_fd()'s last launches
         # the env-id tensor of each entry point's last launch (_call_envs)
         self._ids_in: Dict[str, Any] = {}
         if sensors is not None:
@@ -164,15 +168,15 @@ class Physics:
         data = self.sensordata if data is None else data
         return data[..., adr:adr + w]
 
-    def _ids(self, env_ids, who: str):
-        """env_ids as an int64 tensor on the device (None: every env), checked: in range, no repeats."""
+    def _ids(self, env_ids, who: str, repeats: bool = False):
+        """env_ids as an int64 tensor on the device (None: every env), checked: in range, no repeats (unless `repeats`)."""
         import torch
         if env_ids is None:
             return torch.arange(self.num_envs, device=self.device, dtype=torch.int64)
         ids = torch.as_tensor(env_ids, device=self.device).to(torch.int64).reshape(-1)
         if ids.numel() and bool(((ids < 0) | (ids >= self.num_envs)).any()):
             raise ValueError(f"{who}: env_ids must lie in [0, {self.num_envs})")
-        if torch.unique(ids).numel() != ids.numel():
+        if not repeats and torch.unique(ids).numel() != ids.numel():
             raise ValueError(f"{who}: env_ids must not repeat")
         return ids
 
@@ -653,6 +657,66 @@ class Physics:
         applied = C.c_void_p(res["ctrl"].data_ptr()) if "ctrl" in res else None
         self._call_envs("rsr_physics_feedback_rollouts", who, ids, C.c_void_p(c.data_ptr()), C.byref(fb), C.byref(ps), K, T, nsteps, flags,
                         C.byref(ptrs), applied, checked=True)
+        return res
+
+    def trajectory_fd(self, ctrl, nsteps: Optional[int] = None, eps: float = 1e-3, centered: bool = True, env_ids=None,
+                      nominal: bool = True, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """What the backward pass of iLQR, a time-varying LQR, linearised MPC and an EKF smoother ask: transition_fd at every
+        control step of a nominal trajectory, in two launches and without advancing the env.  ctrl is a float32 tensor
+        [M, T, nu] on the env's device, M = len(env_ids) (default: every env; an env may be listed more than once, e.g. with
+        several candidate plans).  From the record of env env_ids[s] as it stands (qpos, qvel, qacc_warmstart, time), with that
+        env's per-env leaves and applied forces, the nominal run applies ctrl[s, t] then `nsteps` (default n_substeps) x
+        mjx.step for t < T: bit for bit what sample_rollouts records with K = 1.  Then, one wave per (slot, t, column), the
+        finite differences of transition_fd (same columns, `eps`, `centered`) about the state before control step t, the warm
+        start the nominal run carried there included: bit for bit what T rounds of transition_fd() then step(ctrl[:, t]) give.
+        Returns a dict: columns [M, T, ncol, 2 nv + nsensordata] (ncol = 2 nv + nu, one tight row per perturbed coordinate) and
+        its zero-copy views A [M, T, 2nv, 2nv], B [M, T, 2nv, nu], C [M, T, nsensordata, 2nv], D [M, T, nsensordata, nu], oriented
+        as fd_A .. fd_D; with `nominal`, qpos [M, T+1, nq] and qvel [M, T+1, nv], row 0 the start state and row t + 1 the state
+        after control step t.  `out`: caller-owned float32 tensors ("columns", "qpos", "qvel") to fill instead of new ones.
+        Writes nothing else but a scratch buffer of the handle: the record, the side buffer, sensordata and every other buffer
+        of the handle stay as they are.  Two calls on one Physics must not overlap on different streams (they share the scratch)."""
+        import math
+        import torch
+        who = "trajectory_fd"
+        nsteps = self.n_substeps if nsteps is None else int(nsteps)
+        if not 1 <= nsteps < 2 ** 30:
+            raise ValueError(f"{who}: nsteps must lie in [1, 2^30), got {nsteps}")
+        eps = float(eps)
+        if not (math.isfinite(eps) and eps > 0.0):
+            raise ValueError(f"{who}: eps must be finite and > 0, got {eps}")
+        ids = None if env_ids is None else self._ids(env_ids, who, repeats=True)
+        d, dev = self.dims, self.qvel.device
+        M, nu, nv, nq, nsd = self.num_envs if ids is None else int(ids.numel()), int(d.nu), int(d.nv), int(d.nq), self.nsensordata
+        if not torch.is_tensor(ctrl) or ctrl.dtype != torch.float32 or ctrl.dim() != 3 or ctrl.shape[0] != M or ctrl.shape[2] != nu \
+                or ctrl.shape[1] < 1 or ctrl.device != dev:
+            raise ValueError(f"{who} expects ctrl as a float32 tensor of shape ({M}, T >= 1, {nu}) on {dev}")
+        T, ncol, w = int(ctrl.shape[1]), 2 * nv + nu, 2 * nv + nsd
+        if T * nsteps >= 2 ** 31 or M * T * ncol >= 2 ** 31:
+            raise ValueError(f"{who}: T * nsteps and M * T * ncol must stay below 2^31")
+        shapes = dict(columns=(M, T, ncol, w))
+        if nominal:
+            shapes.update(qpos=(M, T + 1, nq), qvel=(M, T + 1, nv))
+        out = dict(out or {})
+        unknown = sorted(set(out) - set(shapes))
+        if unknown:
+            raise ValueError(f"{who}: out has {unknown}; it may hold {tuple(shapes)}" + ("" if nominal else " (nominal=False)"))
+        res, ptrs = {}, _lib.TrajectoryFdOut()
+        for f, shape in shapes.items():
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            elif not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{who}: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {dev}")
+            res[f] = t
+            setattr(ptrs, f, t.data_ptr())
+        c = ctrl.contiguous()
+        self._trajectory_in = c                    # kept alive until the next call (the launches are asynchronous)
+        self._call_envs("rsr_physics_trajectory_fd", who, ids, C.c_void_p(c.data_ptr()), T, nsteps, eps, _lib.FD_CENTERED if centered else 0,
+                        C.byref(ptrs), checked=True)
+        # the buffer holds one row per column of [A B; C D]: the blocks are transposed views, as fd_A .. fd_D
+        col, x, u, sn = res["columns"], slice(0, 2 * nv), slice(2 * nv, ncol), slice(2 * nv, w)
+        res.update(A=col[:, :, x, x].transpose(2, 3), B=col[:, :, u, x].transpose(2, 3), C=col[:, :, x, sn].transpose(2, 3),
+                   D=col[:, :, u, sn].transpose(2, 3))
         return res
 
     def forward(self) -> None:
