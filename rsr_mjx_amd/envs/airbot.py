@@ -221,11 +221,15 @@ class BatchedEnv:
         """Per-env model leaves (numpy or torch, leading dim N): geom_friction [N,ngeom,3], body_mass [N,nbody],
         dof_damping [N,nv], dof_frictionloss [N,nv]; the Go2 kernels also take body_ipos [N,nbody,3], qpos0 [N,nq],
         dof_armature [N,nv], actuator_gainprm / actuator_biasprm [N,nu,3] (go2/randomize.py:6-109).  Missing or None
-        keys restore the model's value."""
+        keys restore the model's value.  A velocity term (column 2 of gainprm / biasprm) is refused on an implicitfast model
+        (model.check_velocity_gains)."""
         import torch
         unknown = set(dr) - set(_lib.DR_FIELDS)
         if unknown:
             raise KeyError(f"not a randomisable model field: {sorted(unknown)}")
+        from ..model import check_velocity_gains
+        as_np = lambda v: None if v is None else (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).reshape(self.num_envs, -1, 3)
+        check_velocity_gains(self.sys.arrays["opt_integrator"][0], as_np(dr.get("actuator_gainprm")), as_np(dr.get("actuator_biasprm")))
         keep = {}
         for fid, k in enumerate(_lib.DR_FIELDS):
             v = dr.get(k)

@@ -367,6 +367,8 @@ class MjcfCompiler:
         b.pos = _vec(node.get("pos"), 3, default=[0, 0, 0])
         b.quat = self._orient(node.attrib)
         b.gravcomp = float(node.get("gravcomp", 0))
+        if b.gravcomp != 0:
+            raise NotImplementedError(f"body {b.name}: gravcomp is not built (qfrc_passive is joint damping only)")
         childclass = node.get("childclass", childclass)
         bid = len(self.bodies)
         self.bodies.append(b)

@@ -71,7 +71,32 @@ def unpack_blob(blob: bytes) -> Dict[str, np.ndarray]:
     return out
 
 
+# arrays that feed MuJoCo's passive forces and that neither the blob's readers (the kernels, the CPU oracle) nor lane_records use:
+# qfrc_passive here is -dof_damping * qvel alone, so a model that sets one of them would be simulated without it
+_UNSUPPORTED_PASSIVE = {"jnt_stiffness": "joint springs", "body_gravcomp": "gravity compensation"}
+
+
+INT_IMPLICITFAST = 3
+
+
+def check_velocity_gains(integrator: int, gainprm, biasprm) -> None:
+    """MuJoCo's implicitfast solves (M - h qDeriv) qacc = f with qDeriv = -diag(damping) + the actuators' velocity derivative,
+    moment^T diag(biasprm[:, 2] + gainprm[:, 2] ctrl) moment.  The integrators here (the kernels' integrate and the CPU oracle's
+    step) solve (M + h diag(damping)) alone, which is implicitfast only while no actuator has a velocity term; Euler, with or
+    without eulerdamp, takes the actuator force explicitly in MuJoCo too.  gainprm / biasprm: [..., nu, 3]."""
+    if int(integrator) != INT_IMPLICITFAST:
+        return
+    for k, a in (("actuator_gainprm", gainprm), ("actuator_biasprm", biasprm)):
+        if a is not None and np.any(np.asarray(a)[..., 2] != 0):
+            raise NotImplementedError(f"{k}[:, 2] is non-zero with the implicitfast integrator: the actuator velocity derivative "
+                                      "of implicitfast is not built (use Euler, or a model without actuator velocity terms)")
+
+
 def model_fields(m: CompiledModel) -> Dict[str, np.ndarray]:
+    for k, what in _UNSUPPORTED_PASSIVE.items():
+        if k in m.arrays and np.any(np.asarray(m.arrays[k]) != 0):
+            raise NotImplementedError(f"{k} is non-zero: {what} are not built (qfrc_passive is joint damping only)")
+    check_velocity_gains(m.arrays["opt_integrator"][0], m.arrays["actuator_gainprm"], m.arrays["actuator_biasprm"])
     f = {}
     for k, v in m.arrays.items():
         if k.startswith(_SKIP_PREFIX):

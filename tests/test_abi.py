@@ -81,6 +81,66 @@ def test_product_does_not_import_the_oracle():
                 assert "rsr_oracle.c" not in text, fn
 
 
+def test_passive_forces_that_are_not_built_are_refused(cube_model):
+    """model_fields refuses a model with a joint spring (jnt_stiffness, in every asset and all zero) or with gravity compensation
+    (body_gravcomp: the compiler refuses the attribute itself and emits no such array, a model loaded from elsewhere may carry one) and names the field: nothing reads either, so such a model would be
+    simulated without them.  All-zero arrays pass."""
+    import copy
+    import numpy as np
+    from rsr_mjx_amd.model import model_fields
+    assert "jnt_stiffness" in cube_model.arrays and not np.any(cube_model.arrays["jnt_stiffness"])
+    for field in ("jnt_stiffness", "body_gravcomp"):
+        m = copy.copy(cube_model)
+        m.arrays = dict(cube_model.arrays)
+        n = cube_model.njnt if field == "jnt_stiffness" else cube_model.nbody
+        m.arrays[field] = np.zeros(n)
+        model_fields(m)
+        stiff = np.zeros(n)
+        stiff[2] = 5.0
+        m.arrays[field] = stiff
+        with pytest.raises(NotImplementedError, match=field):
+            model_fields(m)
+    model_fields(cube_model)
+
+
+def test_velocity_gains_under_implicitfast_are_refused(cube_model, go2_model, tmp_path):
+    """implicitfast here solves (M + h D) alone, without the actuators' velocity derivative that MuJoCo's implicitfast adds, so a
+    model with biasprm[:, 2] or gainprm[:, 2] != 0 under implicitfast is refused, by field name; the same model under Euler, and
+    the per-env leaves' check on batched arrays, pass or refuse alike.  And the compiler refuses a body with gravcomp."""
+    import copy
+    import numpy as np
+    from rsr_mjx_amd import mjcf
+    from rsr_mjx_amd.model import check_velocity_gains, model_fields
+    assert int(cube_model.arrays["opt_integrator"][0]) == 3 and int(go2_model.arrays["opt_integrator"][0]) == 0
+    for field in ("actuator_biasprm", "actuator_gainprm"):
+        for base, refused in ((cube_model, True), (go2_model, False)):
+            m = copy.copy(base)
+            m.arrays = dict(base.arrays)
+            a = np.array(base.arrays[field], dtype=np.float64)
+            a[1, 2] = -0.5
+            m.arrays[field] = a
+            if refused:
+                with pytest.raises(NotImplementedError, match=field):
+                    model_fields(m)
+                m.arrays["opt_integrator"] = np.array([0], np.int32)
+            model_fields(m)
+    leaf = np.zeros((4, 5, 3), np.float32)
+    check_velocity_gains(3, leaf, leaf)
+    check_velocity_gains(3, None, None)
+    leaf[3, 2, 2] = 1.0
+    check_velocity_gains(0, leaf, leaf)
+    with pytest.raises(NotImplementedError, match="actuator_biasprm"):
+        check_velocity_gains(3, None, leaf)
+    xml = open(os.path.join(ROOT, "tests", "golden", "compiler_pusher.xml")).read()
+    assert "gravcomp" not in xml and "<body " in xml
+    path = tmp_path / "gravcomp.xml"
+    path.write_text(xml.replace("<body ", '<body gravcomp="1" ', 1))
+    with pytest.raises(NotImplementedError, match="gravcomp"):
+        mjcf.compile_mjcf(str(path))
+    path.write_text(xml.replace("<body ", '<body gravcomp="0" ', 1))
+    mjcf.compile_mjcf(str(path))
+
+
 def test_malformed_blobs_are_refused(lib, cube_model):
     """rsr_model_create validates the blob's directory before reading through it: truncated blobs, entries pointing outside
     the blob, absurd entry counts and missing fields all return RSR_ERR_ARG (-1) with a message, never a crash."""
