@@ -23,6 +23,9 @@
  *                          rsr_physics_step about the record's current state, in a buffer of its own.
  *   rsr_physics_trajectory_fd <- mjd_transitionFD at every step of a nominal rollout / vmap(jax.jacobian(mjx.step)) over the
  *                          states of lax.scan(mjx.step): A_t, B_t, C_t, D_t for t < T in two launches; the record is read only.
+ *   rsr_physics_lqr_backward <- the backward pass of iLQR / time-varying LQR (the Riccati recursion over lax.scan(reverse=True)):
+ *                          A_t, B_t and a quadratic cost model in, the gains K_t, k_t of rsr_physics_feedback_rollouts out, one
+ *                          launch; neither the model nor the record is read.
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
@@ -173,7 +176,8 @@ int rsr_physics_param_rollouts(rsr_physics* p, const int32_t* env_ids, int count
  * start of control step t the control is computed from the sample's own current state (the record's at t = 0, the state after
  * control step t-1 otherwise):
  *   dq  = mj_differentiatePos(qpos_ref[., t], qpos) with dt = 1: qpos (-) qpos_ref in the tangent space [nv]; a free joint's
- *         rotation is the rotation vector of conj(q_ref) q, as rsr_physics_transition_fd takes its differences
+ *         rotation is the rotation vector of conj(q_ref) q, as rsr_physics_transition_fd takes its differences, and exactly 0
+ *         where q equals q_ref bit for bit: a sample on the reference trajectory with the reference's ctrl stays on it
  *   dv  = qvel - qvel_ref[., t]                                                                          [nv]
  *   u_j = ctrl[., t, j] + sum_{i < nv} gain[., t, j, i] dq_i + sum_{i < nv} gain[., t, j, nv + i] dv_i
  *         accumulated in that order from ctrl[., t, j], one fp32 fma per term
@@ -336,6 +340,46 @@ int rsr_physics_transition_view(rsr_physics* p, int field, void** dev_ptr, int64
 typedef struct rsr_trajectory_fd_out { float* columns; float* qpos; float* qvel; } rsr_trajectory_fd_out;
 int rsr_physics_trajectory_fd(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int T, int nsteps,
                               float eps, int flags, const rsr_trajectory_fd_out* out, void* hip_stream);
+
+/* LQR backward pass, the step between rsr_physics_trajectory_fd and rsr_physics_feedback_rollouts in an iLQR iteration: the
+ * time-varying Riccati recursion of Tassa, Erez and Todorov 2012 (the unregularised Q in the value update) on M independent
+ * problems, one launch with one wavefront per slot.  The handle supplies nv, nu, the device and the family's launch entry only: the
+ * call reads neither the model nor the record, takes no env_ids, and the M slots are whatever the caller's buffers hold.  All
+ * pointers are device float32; nx = 2 nv, ncol = nx + nu.
+ * columns: [M, T, ncol, row_stride], row_stride >= nx: the buffer rsr_physics_trajectory_fd writes, passed as it is with
+ * row_stride = 2 nv + nsensordata; A_t[i][j] = columns[s, t, j, i] for j < nx, B_t[i][j] = columns[s, t, nx + j, i], state
+ * differences in the tangent space (mj_differentiatePos).  Entries at index nx and above of a row are never read.
+ * cost: lx [M, T+1, nx] and lxx [M, T+1, nx, nx], row T the terminal cost; lu [M, T, nu], luu [M, T, nu, nu], lux [M, T, nu, nx];
+ * lux may be NULL (zero: bit for bit what an all-zero lux gives), the other four are required.  lxx and luu are read as given: the
+ * caller passes them symmetric.  mu: [M], one regularisation value per slot, read on the device.
+ * From Vx = lx[T], Vxx = lxx[T], for t = T-1 .. 0:
+ *   Qx  = lx_t + A^T Vx          Qu  = lu_t + B^T Vx
+ *   Qxx = lxx_t + A^T Vxx A      Qux = lux_t + B^T Vxx A      Quu = luu_t + B^T Vxx B
+ *   Quu~ = Quu + mu I,      Qux~ = Qux                        (flags = 0)
+ *   Quu~ = Quu + mu B^T B,  Qux~ = Qux + mu B^T A             (RSR_LQR_REG_STATE)
+ *   k = -Quu~^-1 Qu         K = -Quu~^-1 Qux~                 (Cholesky of Quu~)
+ *   Vx  = Qx  + K^T Quu k + K^T Qu  + Qux^T k
+ *   Vxx = Qxx + K^T Quu K + K^T Qux + Qux^T K, then Vxx = (Vxx + Vxx^T) / 2
+ *   dv[0] += k^T Qu         dv[1] += 1/2 k^T Quu k
+ * in fp32, every output element summed in a fixed order: a slot's result depends on that slot's inputs alone, bit for bit, whatever
+ * M is and from run to run.
+ * out: gain [M, T, nu, nx] = K_t, exactly the gain of rsr_feedback (u = ctrl + gain [dq; dv]); k [M, T, nu]; dv [M, 2], the
+ * expected cost change at step size alpha being alpha dv[0] + alpha^2 dv[1]; status [M], as float; and, optional (NULL: not
+ * recorded), vx [M, T+1, nx] and vxx [M, T+1, nx, nx], row T the terminal cost, row t the value after step t of the recursion.
+ * gain, k, dv and status are required.
+ * Failure: step t fails if a Cholesky pivot of Quu~ is <= 0 or not finite.  The slot stops there: status[s] = t, dv[s] = (0, 0),
+ * rows t' > t of gain / k / vx / vxx keep what was written and rows t' <= t are left alone; the other slots are unaffected.  On
+ * success status[s] = -1.  The caller raises mu[s] and calls again: no host sync is needed to adapt it.
+ * Only the buffers of out are written: the record, every buffer of the handle, the batch's own leaf tensors and the PRNG keys are
+ * untouched; the handle owns no buffer for this call.  RSR_ERR_ARG, checked before any device work: null handle, columns, cost,
+ * mu or out; a NULL required member of cost or out; M < 1 or T < 1; row_stride < 2 nv; unknown flag bits; M (T+1) at or above
+ * 2^31. */
+typedef struct rsr_lqr_cost { const float* lx; const float* lu; const float* lxx; const float* luu; const float* lux; } rsr_lqr_cost;
+typedef struct rsr_lqr_out  { float* gain; float* k; float* dv; float* status; float* vx; float* vxx; } rsr_lqr_out;
+#define RSR_LQR_REG_STATE 1     /* regularise through the state: Quu + mu B^T B, Qux + mu B^T A; without it Quu + mu I */
+int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const float* columns, int row_stride,
+                             const rsr_lqr_cost* cost, const float* mu, int flags,
+                             const rsr_lqr_out* out, void* hip_stream);
 
 /* Inverse dynamics (mj_inverse / mjx.inverse): given an acceleration per env, the generalised force that must have acted
  * (data.qfrc_inverse).  One launch evaluates the record's current state -- its qpos / qvel / ctrl with the batch's per-env

@@ -45,7 +45,7 @@ PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step",
                 "rsr_physics_applied_view", "rsr_physics_set_jac_sites", "rsr_physics_dynamics", "rsr_physics_dynamics_view",
                 "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
                 "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts",
-                "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd"]
+                "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd", "rsr_physics_lqr_backward"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -101,6 +101,22 @@ class TrajectoryFdOut(C.Structure):
     """struct rsr_trajectory_fd_out (include/rsr_physics.h): device pointers, columns [M, T, ncol, 2 nv + nsd] (required), the nominal
     qpos [M, T+1, nq] and qvel [M, T+1, nv] (NULL = not recorded)."""
     _fields_ = [(n, C.c_void_p) for n in ("columns", "qpos", "qvel")]
+
+
+class LqrCost(C.Structure):
+    """struct rsr_lqr_cost (include/rsr_physics.h): device pointers, lx [M, T+1, nx], lu [M, T, nu], lxx [M, T+1, nx, nx],
+    luu [M, T, nu, nu], lux [M, T, nu, nx] (NULL = zero); nx = 2 nv."""
+    _fields_ = [(n, C.c_void_p) for n in ("lx", "lu", "lxx", "luu", "lux")]
+
+
+class LqrOut(C.Structure):
+    """struct rsr_lqr_out (include/rsr_physics.h): device pointers, gain [M, T, nu, nx], k [M, T, nu], dv [M, 2], status [M]
+    (required), vx [M, T+1, nx] and vxx [M, T+1, nx, nx] (NULL = not recorded)."""
+    _fields_ = [(n, C.c_void_p) for n in ("gain", "k", "dv", "status", "vx", "vxx")]
+
+
+# the RSR_LQR_* flags (include/rsr_physics.h)
+LQR_REG_STATE = 1
 
 
 SYMBOLS = [
@@ -160,6 +176,7 @@ def lib() -> C.CDLL:
     L.rsr_physics_param_rollouts.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
     L.rsr_physics_feedback_rollouts.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.rsr_physics_trajectory_fd.argtypes = [vp, vp, i32, vp, i32, i32, C.c_float, i32, vp, vp]
+    L.rsr_physics_lqr_backward.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

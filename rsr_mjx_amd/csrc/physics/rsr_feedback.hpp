@@ -23,7 +23,9 @@ __device__ __forceinline__ void feedback_ctrl(const DModel& m, const Hot& hot, S
   const gp_f p_gain = (gp_f)(sw.fb_gain + ref_row * (size_t)(C::NU * 2 * C::NV));
   const gp_f p_qref = (gp_f)(sw.fb_qpos + ref_row * (size_t)C::NQ), p_vref = (gp_f)(sw.fb_qvel + ref_row * (size_t)C::NV);
   const float yq = lane < C::NQ ? p_qref[lane] : 0.0f;
-  const float dq = -differentiate_pos<C>(hot, s, lane, yq);          // (the helper gives ref (-) qpos; the negation is exact)
+  // (the helper gives ref (-) qpos; the negation is exact.  zero_at_equal: at the reference state every term of the sum is a zero,
+  // so a sample that starts on the nominal trajectory with the nominal ctrl stays on it bit for bit whatever the gain)
+  const float dq = -differentiate_pos<C>(hot, s, lane, yq, true);
   const float dv = lane < C::NV ? s.qvel[lane] - p_vref[lane] : 0.0f;
   const int j = lane < C::NU ? lane : 0;
   const gp_f g = p_gain + j * (2 * C::NV);

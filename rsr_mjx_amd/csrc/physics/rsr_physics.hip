@@ -2,8 +2,8 @@
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse), sampled rollouts (rsr_physics_sample_rollouts), parameter
-// rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts) and the transition Jacobians along a
-// trajectory (rsr_physics_trajectory_fd).  Every launch is a physics op
+// rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts), the transition Jacobians along a
+// trajectory (rsr_physics_trajectory_fd) and the LQR backward pass (rsr_physics_lqr_backward).  Every launch is a physics op
 // (rsr::PhysOp) sent through physics_launch; the kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
@@ -491,6 +491,24 @@ extern "C" int rsr_physics_trajectory_fd(rsr_physics* p, const int32_t* env_ids,
   if (const int rc = physics_launch(p, rsr::OP_TRAJ_NOMINAL, x, who)) return rc;
   x.grid = (int)(cells * FL.ncol);
   return physics_launch(p, rsr::OP_TRAJ_FD, x, who);
+}
+
+// One launch, one wave per slot (rsr_lqr.hpp).  The handle gives nv, nu, the device and the family's entry; none of its buffers is used.
+extern "C" int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const float* columns, int row_stride, const rsr_lqr_cost* cost,
+                                        const float* mu, int flags, const rsr_lqr_out* out, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_lqr_backward: null handle");
+  if (!columns || !cost || !mu || !out) return fail(RSR_ERR_ARG, "rsr_physics_lqr_backward: null columns, cost, mu or out");
+  if (!cost->lx || !cost->lu || !cost->lxx || !cost->luu) return fail(RSR_ERR_ARG, "rsr_physics_lqr_backward: cost needs lx, lu, lxx and luu (only lux may be null)");
+  if (!out->gain || !out->k || !out->dv || !out->status) return fail(RSR_ERR_ARG, "rsr_physics_lqr_backward: out needs gain, k, dv and status (only vx and vxx may be null)");
+  if (M < 1 || T < 1) return fail(RSR_ERR_ARG, "rsr_physics_lqr_backward: M and T must be >= 1");
+  const rsr_dims& d = p->b->model->dims;
+  if (row_stride < 2 * d.nv) return fail(RSR_ERR_ARG, "rsr_physics_lqr_backward: row_stride must be >= 2 nv");
+  if (flags & ~RSR_LQR_REG_STATE) return fail(RSR_ERR_ARG, "rsr_physics_lqr_backward: unknown flag bits");
+  if ((int64_t)M * ((int64_t)T + 1) > INT32_MAX) return fail(RSR_ERR_ARG, "rsr_physics_lqr_backward: M x (T + 1) must stay below 2^31");
+  rsr::Launch x = physics_args(p, nullptr, nullptr, M, 1, hip_stream);
+  x.ph.lq = rsr::LqrArgs{columns, row_stride, T, cost->lx, cost->lu, cost->lxx, cost->luu, cost->lux, mu, flags,
+                         out->gain, out->k, out->dv, out->status, out->vx, out->vxx};
+  return physics_launch(p, rsr::OP_LQR_BACKWARD, x, "rsr_physics_lqr_backward");
 }
 
 // the inverse buffer, on first use

@@ -138,6 +138,17 @@ struct TrajArgs {
   float eps;
   int flags;            // RSR_FD_CENTERED or 0
 };
+// rsr_physics_lqr_backward (rsr_lqr.hpp): the caller's buffers, every row indexed by slot (PhysLaunch::lq).  nx = 2 nv.
+struct LqrArgs {
+  const float* columns; // [M][T][nx + nu][row_stride], entries >= nx of a row are not read
+  int row_stride, T;
+  const float *lx, *lu, *lxx, *luu;   // [M][T+1][nx], [M][T][nu], [M][T+1][nx][nx], [M][T][nu][nu]
+  const float* lux;     // [M][T][nu][nx], or null: zero
+  const float* mu;      // [M]
+  int flags;            // RSR_LQR_REG_STATE or 0
+  float *gain, *k, *dv, *status;      // [M][T][nu][nx], [M][T][nu], [M][2], [M]
+  float *vx, *vxx;      // [M][T+1][nx], [M][T+1][nx][nx], each null = not recorded
+};
 
 // The physics ops of a family unit's launch entry (launch_physics, rsr_physics_kernels.hpp).  An entry takes its op as an int, of
 // enum Op (rsr_launch.hpp) or of this enum: these start above enum Op's, so that no value names two ops.  A new op is a member
@@ -156,6 +167,7 @@ enum PhysOp {
                          // r.ctrl [M][K][T][nu] or [M][T][nu]
   OP_TRAJ_NOMINAL,       // rsr_physics_trajectory_fd, first launch (p, tj): grid = envs or listed envs (p.ids)
   OP_TRAJ_FD,            // rsr_physics_trajectory_fd, second launch (p, tj): grid = envs x T x columns, or listed envs (p.ids) x T x columns
+  OP_LQR_BACKWARD,       // rsr_physics_lqr_backward (lq): grid = slots; reads neither the model nor the record
 };
 // The physics ops' arguments (Launch::ph), one field per op that needs its own
 struct PhysLaunch {
@@ -168,6 +180,7 @@ struct PhysLaunch {
   int K;                // OP_PHYS_SAMPLE: the control sequences per env
   SweepArgs sw;         // OP_PHYS_SWEEP
   TrajArgs tj;          // OP_TRAJ_NOMINAL, OP_TRAJ_FD
+  LqrArgs lq;           // OP_LQR_BACKWARD
   Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
 };
 

@@ -2,9 +2,10 @@
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
 // forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp), constraint_kernel (rsr_constraint.hpp), transition_kernel
 // (rsr_transition.hpp), inverse_kernel (rsr_inverse.hpp), sample_kernel (rsr_sample.hpp), sweep_kernel (rsr_sweep.hpp) and the two
-// of rsr_trajectory.hpp, nominal_kernel and trajectory_fd_kernel; all but dynamics_kernel and inverse_kernel are instantiated
-// plain and with applied forces: the applied kernels take the handle's Applied buffers as one more argument and pass forward<C>
-// their env's rows as its force stage (rsr_applied.hpp).
+// of rsr_trajectory.hpp, nominal_kernel and trajectory_fd_kernel, and lqr_kernel (rsr_lqr.hpp), which runs no physics and takes of
+// a family only nv and nu; all but dynamics_kernel, inverse_kernel and lqr_kernel are instantiated plain and with applied forces:
+// the applied kernels take the handle's Applied buffers as one more argument and pass forward<C> their env's rows as its force
+// stage (rsr_applied.hpp).
 #pragma once
 #include "../rsr_launch.hpp"
 #include "rsr_sensors.hpp"
@@ -16,6 +17,7 @@
 #include "rsr_sample.hpp"
 #include "rsr_sweep.hpp"
 #include "rsr_trajectory.hpp"
+#include "rsr_lqr.hpp"
 
 namespace rsr {
 
@@ -168,14 +170,16 @@ void rollout_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
 static_assert((int)OP_STEP_OCCUPANCY < (int)OP_PHYS_FORWARD, "an entry takes an Op or a PhysOp as one int: the values must not meet");
 template <class C, int WAVES>
 int launch_physics(int op, const Launch& x) {
-  // (the LDS of the transition and of the trajectory's columns: Smem<C> and the words the first run's end state waits in)
-  const size_t lds = op == OP_TRAJ_FD || op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>);
+  // (the LDS of the transition and of the trajectory's columns: Smem<C> and the words the first run's end state waits in; the
+  // backward pass has an image of its own, LqrDims<C>)
+  const size_t lds = op == OP_LQR_BACKWARD ? lqr_lds_bytes<C>() : op == OP_TRAJ_FD || op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>);
   auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(64), lds, x.stream, x.dm, x.L, x.a, args...); return 0; };
   const PhysLaunch& ph = x.ph;
   const bool ap = ph.ap.xfrc != nullptr;     // applied forces on
   // the two launches of rsr_physics_trajectory_fd (rsr_trajectory.hpp)
   if (op == OP_TRAJ_NOMINAL) return ap ? go(nominal_kernel<C, WAVES, Applied>, ph.p, ph.tj, ph.ap) : go(nominal_kernel<C, WAVES>, ph.p, ph.tj);
   if (op == OP_TRAJ_FD) return ap ? go(trajectory_fd_kernel<C, WAVES, Applied>, ph.p, ph.tj, ph.ap) : go(trajectory_fd_kernel<C, WAVES>, ph.p, ph.tj);
+  if (op == OP_LQR_BACKWARD) return go(lqr_kernel<C, WAVES>, ph.lq);      // rsr_physics_lqr_backward (rsr_lqr.hpp)
   switch (op) {
     case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, ph.p, ph.ap) : go(physics_kernel<C, true, WAVES>, ph.p);
     case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, ph.p, ph.ap) : go(physics_kernel<C, false, WAVES>, ph.p);

@@ -53,8 +53,12 @@ __device__ __forceinline__ void perturb_state(const Hot& h, Smem<C>& s, int lane
 // mj_differentiatePos(yq, s.qpos) with dt = 1, this dof lane's component: yq (-) s.qpos in the tangent space.  yq: lane t holds
 // the minuend's qpos[t]; the subtrahend is in LDS.  A free joint's rotation: the rotation vector of conj(q-) q+ (mju_subQuat,
 // mju_quat2Vel), in the frame the perturbation was made in.  Called by all lanes (cross-lane reads in uniform code).
+// zero_at_equal: where the two quaternions are equal bit for bit the rotation's difference is 0, as in MuJoCo.  Without it it is
+// the rounding residue of the product's contracted fmas, about 1e-8, which the finite differences have always carried: their
+// callers leave it off and compile to the code they had.  A caller that multiplies the difference by a gain and closes a loop
+// on it asks for the exact zero.
 template <class C>
-__device__ __forceinline__ float differentiate_pos(const Hot& h, const Smem<C>& s, int lane, float yq) {
+__device__ __forceinline__ float differentiate_pos(const Hot& h, const Smem<C>& s, int lane, float yq, bool zero_at_equal = false) {
   const int lr = lrec_lane(lane);
   const int4 rd_ids = lrec<C>(h, LQ_D_IDS, lr), rd_act = lrec<C>(h, LQ_D_ACT, lr);     // (-, -, joint type, k); (-, -, qposadr, -)
   const bool fr = lane < C::NV && rd_ids.z == JNT_FREE, rot = fr && rd_ids.w >= 3;
@@ -64,6 +68,7 @@ __device__ __forceinline__ float differentiate_pos(const Hot& h, const Smem<C>& 
   for (int c = 0; c < 4; ++c) pq[c] = __shfl(yq, qa + c < 64 ? qa + c : 63);
   if (!rot) return pq[0] - s.qpos[qa];
   const Q4 qm = ld4(&s.qpos[qa]);
+  if (zero_at_equal && qm.w == pq[0] && qm.x == pq[1] && qm.y == pq[2] && qm.z == pq[3]) return 0.0f;
   const Q4 dq = qmul(Q4{qm.w, -qm.x, -qm.y, -qm.z}, Q4{pq[0], pq[1], pq[2], pq[3]});
   const float sn = fsqrt(dq.x * dq.x + dq.y * dq.y + dq.z * dq.z);
   float speed = 2.0f * atan2f(sn, dq.w);

@@ -27,6 +27,10 @@
     mjd_transitionFD along a nominal rollout     ->  Physics.trajectory_fd(ctrl [M, T, nu]) (A_t, B_t, C_t, D_t at every control
                                                                                            step of the trajectory ctrl gives from
                                                                                            the current state; the record stays)
+    the Riccati recursion of iLQR / TV-LQR      ->  Physics.lqr_backward(columns, lx, lu, lxx, luu)
+                                                                                          (A_t, B_t and a quadratic cost model in,
+                                                                                           the gains of feedback_rollouts out; one
+                                                                                           launch, nothing of the env is read)
     mj_inverse / mjx.inverse (data.qfrc_inverse)  ->  Physics.inverse(qacc)               (the force behind a given acceleration,
                                                                                            no solve: qfrc_inverse)
 
@@ -105,6 +109,7 @@ class Physics:
         self._param_in = None                      # the control sequences and leaf tensors of param_rollouts()'s last launch
         self._feedback_in = None                   # the inputs of feedback_rollouts()'s last launch
         self._trajectory_in = None                 # the control sequences of trajectory_fd()'s last launches
+        self._lqr_in = None                        # the inputs of lqr_backward()'s last launch
         # the env-id tensor of each entry point's last launch (_call_envs)
         self._ids_in: Dict[str, Any] = {}
         if sensors is not None:
@@ -717,6 +722,74 @@ class Physics:
         col, x, u, sn = res["columns"], slice(0, 2 * nv), slice(2 * nv, ncol), slice(2 * nv, w)
         res.update(A=col[:, :, x, x].transpose(2, 3), B=col[:, :, u, x].transpose(2, 3), C=col[:, :, x, sn].transpose(2, 3),
                    D=col[:, :, u, sn].transpose(2, 3))
+        return res
+
+    def lqr_backward(self, columns, lx, lu, lxx, luu, lux=None, mu=0.0, state_reg: bool = False, values: bool = False,
+                     out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """The backward pass of iLQR / time-varying LQR, the step between trajectory_fd and feedback_rollouts: the Riccati
+        recursion of Tassa et al. 2012 (the unregularised Q in the value update) on M independent problems, one launch with one
+        wave per slot and T steps inside it.  Nothing of the env is read: the handle gives nv and nu, and M is whatever the
+        buffers hold.  All float32 tensors on the env's device, contiguous, nx = 2 nv, ncol = nx + nu:
+        columns [M, T, ncol, w], w >= nx: trajectory_fd(...)["columns"] as it is (w = 2 nv + nsensordata; the sensor entries of
+        a row are never read), i.e. A_t = columns[:, t, :nx, :nx]^T, B_t = columns[:, t, nx:, :nx]^T in the tangent space;
+        lx [M, T+1, nx], lxx [M, T+1, nx, nx] (row T: the terminal cost), lu [M, T, nu], luu [M, T, nu, nu], lux [M, T, nu, nx] or
+        None (zero); lxx and luu symmetric.  mu: a float or a tensor [M], the regularisation of each slot: Quu + mu I, or with
+        `state_reg` Quu + mu B^T B and Qux + mu B^T A.  Returns gain [M, T, nu, nx] (what feedback_rollouts takes as `gain`),
+        k [M, T, nu] (an iLQR line search passes ctrl + alpha * k per sample), dV [M, 2] (the expected cost change at step alpha
+        is alpha dV[0] + alpha^2 dV[1]), status [M] (-1, or the step t whose Quu~ had a Cholesky pivot <= 0 or not finite: that
+        slot stopped there with dV = 0, its rows t' > t written and its rows t' <= t left alone; raise its mu and call again)
+        and, with `values`, Vx [M, T+1, nx] and Vxx [M, T+1, nx, nx].  `out`: caller-owned float32 tensors under those names to
+        fill instead of new ones.  A slot's result depends on that slot's inputs alone, bit for bit.  Writes nothing else."""
+        import torch
+        who = "lqr_backward"
+        d, dev = self.dims, self.qvel.device
+        nv, nu = int(d.nv), int(d.nu)
+        nx, ncol = 2 * nv, 2 * nv + nu
+
+        def f32(name, t, shape_txt, ok):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or not ok(t) or not t.is_contiguous():
+                raise ValueError(f"{who} expects {name} as a contiguous float32 tensor of shape {shape_txt} on {dev}")
+
+        f32("columns", columns, f"(M >= 1, T >= 1, {ncol}, w >= {nx})",
+            lambda t: t.dim() == 4 and t.shape[0] >= 1 and t.shape[1] >= 1 and t.shape[2] == ncol and t.shape[3] >= nx)
+        M, T, w = int(columns.shape[0]), int(columns.shape[1]), int(columns.shape[3])
+        if M * (T + 1) >= 2 ** 31:
+            raise ValueError(f"{who}: M * (T + 1) must stay below 2^31")
+        shapes = dict(lx=(M, T + 1, nx), lu=(M, T, nu), lxx=(M, T + 1, nx, nx), luu=(M, T, nu, nu), lux=(M, T, nu, nx))
+        given = dict(lx=lx, lu=lu, lxx=lxx, luu=luu, lux=lux)
+        for name, t in given.items():
+            if t is None and name == "lux":
+                continue
+            f32(name, t, f"{shapes[name]} (M and T as columns has them)", lambda t, name=name: tuple(t.shape) == shapes[name])
+        if torch.is_tensor(mu):
+            f32("mu", mu, f"({M},), or a float", lambda t: tuple(t.shape) == (M,))
+            mu_t = mu
+        else:
+            try:
+                mu_t = torch.full((M,), float(mu), dtype=torch.float32, device=dev)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who} expects mu as a float or a float32 tensor of shape ({M},) on {dev}") from None
+        oshapes = dict(gain=(M, T, nu, nx), k=(M, T, nu), dV=(M, 2), status=(M,))
+        if values:
+            oshapes.update(Vx=(M, T + 1, nx), Vxx=(M, T + 1, nx, nx))
+        out = dict(out or {})
+        unknown = sorted(set(out) - set(oshapes))
+        if unknown:
+            raise ValueError(f"{who}: out has {unknown}; it may hold {tuple(oshapes)}" + ("" if values else " (values=False)"))
+        res, ptrs = {}, _lib.LqrOut()
+        for f, shape in oshapes.items():
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            elif not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{who}: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {dev}")
+            res[f] = t
+            setattr(ptrs, dict(dV="dv", Vx="vx", Vxx="vxx").get(f, f), t.data_ptr())
+        cost = _lib.LqrCost(lx.data_ptr(), lu.data_ptr(), lxx.data_ptr(), luu.data_ptr(), None if lux is None else lux.data_ptr())
+        self._lqr_in = (columns, lx, lu, lxx, luu, lux, mu_t)       # kept alive until the next call (the launch is asynchronous)
+        _lib.check(_lib.lib().rsr_physics_lqr_backward(self._h, M, T, C.c_void_p(columns.data_ptr()), w, C.byref(cost),
+                                                       C.c_void_p(mu_t.data_ptr()), _lib.LQR_REG_STATE if state_reg else 0,
+                                                       C.byref(ptrs), self._stream()))
         return res
 
     def forward(self) -> None:
