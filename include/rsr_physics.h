@@ -26,6 +26,8 @@
  *   rsr_physics_lqr_backward <- the backward pass of iLQR / time-varying LQR (the Riccati recursion over lax.scan(reverse=True)):
  *                          A_t, B_t and a quadratic cost model in, the gains K_t, k_t of rsr_physics_feedback_rollouts out, one
  *                          launch; neither the model nor the record is read.
+ *   rsr_physics_ik      <- an IK library on top of mj_jacSite (damped least squares on site pose targets): M problems, one launch,
+ *                          every iteration on the device; the record is read only.
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
@@ -380,6 +382,46 @@ typedef struct rsr_lqr_out  { float* gain; float* k; float* dv; float* status; f
 int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const float* columns, int row_stride,
                              const rsr_lqr_cost* cost, const float* mu, int flags,
                              const rsr_lqr_out* out, void* hip_stream);
+
+/* Inverse kinematics on site pose targets: which qpos puts these sites there.  Damped least squares (Levenberg-Marquardt with a
+ * fixed damping) on M independent problems, one launch with one wavefront per slot and every iteration inside it.  Slot s takes
+ * its model, its per-env leaves (the Go2 qpos0 leaf moves the kinematics) and its default start from env env_ids[s] (env_ids
+ * NULL: M = the batch's envs, env s); an env may be listed more than once, and an id out of range leaves its slot's rows alone.
+ * task (host memory, shared by every slot, passed to the kernel by value: no device table, no state in the handle, independent of
+ * rsr_physics_set_jac_sites): nsite sites in [1, RSR_MAX_JAC_SITES], pos_weight[k] >= 0 and rot_weight[k] >= 0 (0: that row is
+ * off; not all zero), dofs: bit i set = dof i may move (free-joint dofs allowed; nv <= 32).
+ * in (device float32): target_pos [M, nsite, 3]; target_quat [M, nsite, 4] (w, x, y, z; normalised on the device as the
+ * kinematics normalises a free joint's quaternion) or NULL, then every rot_weight must be 0; qpos0 [M, nq] or NULL: the record's
+ * qpos of the slot's env; damping [M], lambda per slot, read on the device.
+ * opt: iters >= 0, tol_pos >= 0, tol_rot >= 0 (0: every iteration runs), max_step >= 0 (0: no cap), limits 0 or 1.
+ *   q = start
+ *   for it = 0, 1, ...:
+ *     kinematics(q)                          (it normalises free-joint quaternions in q, as MJX does)
+ *     e_k = p*_k - p_k, r_k = the rotation vector of R*_k R_k^T (world frame, the short way round; R_k: the site's frame)
+ *     perr = max_k |e_k| over pos_weight_k > 0, rerr = max_k |r_k| over rot_weight_k > 0
+ *     if it == iters or (perr <= tol_pos and rerr <= tol_rot): stop, status 0 if the tolerances hold, else 1
+ *     J = rows pos_weight_k jacp_k, rot_weight_k jacr_k (mj_jacSite, as rsr_physics_dynamics), the columns of dofs outside
+ *         `dofs` zeroed; b = rows pos_weight_k e_k, rot_weight_k r_k
+ *     dq = (J^T J + lambda I)^-1 J^T b       (L D L^T; a zeroed column gives dq = 0 exactly)
+ *     if max|dq| > max_step > 0: dq *= max_step / max|dq|
+ *     q = mj_integratePos(q, dq)             (a free joint's rotation dofs are a body-frame rotation vector: q (x) exp(dq / 2),
+ *                                             normalised; a dof outside `dofs` is not touched)
+ *     if limits: clamp hinge / slide q to jnt_range where jnt_limited
+ * A lambda that is not finite and positive, or a dq that is not finite, ends the slot with status 2 at the last q; the other
+ * slots are unaffected.  A slot's result depends on that slot's inputs alone, bit for bit.
+ * out (device): qpos [M, nq] float32; err [M, 2] float32: perr, rerr of the last kinematics pass, i.e. at the returned qpos;
+ * info [M, 2] int32: iterations taken, status.  iters = 0 is a forward-kinematics query: the start and its error.
+ * Only the buffers of out are written: the record, every buffer of the handle, the batch's own leaf tensors and the PRNG keys are
+ * untouched; the handle owns no buffer for this call.  RSR_ERR_ARG, checked before any device work: null handle, task, in, opt or
+ * out; a NULL target_pos, damping, qpos, err or info; count < 1 with env_ids; nsite outside [1, RSR_MAX_JAC_SITES]; a site id out
+ * of range; a weight that is negative or not finite; all weights zero; a positive rot_weight without target_quat; dofs with a bit
+ * at or above nv; iters < 0; a tolerance or max_step that is negative or not finite; limits not 0 or 1. */
+typedef struct rsr_ik_task { int32_t nsite; int32_t sites[RSR_MAX_JAC_SITES]; float pos_weight[RSR_MAX_JAC_SITES]; float rot_weight[RSR_MAX_JAC_SITES]; uint32_t dofs; } rsr_ik_task;
+typedef struct rsr_ik_in   { const float* target_pos; const float* target_quat; const float* qpos0; const float* damping; } rsr_ik_in;
+typedef struct rsr_ik_opt  { int32_t iters; float tol_pos; float tol_rot; float max_step; int32_t limits; } rsr_ik_opt;
+typedef struct rsr_ik_out  { float* qpos; float* err; int32_t* info; } rsr_ik_out;
+int rsr_physics_ik(rsr_physics* p, const int32_t* env_ids, int count, const rsr_ik_task* task, const rsr_ik_in* in,
+                   const rsr_ik_opt* opt, const rsr_ik_out* out, void* hip_stream);
 
 /* Inverse dynamics (mj_inverse / mjx.inverse): given an acceleration per env, the generalised force that must have acted
  * (data.qfrc_inverse).  One launch evaluates the record's current state -- its qpos / qvel / ctrl with the batch's per-env

@@ -45,7 +45,7 @@ PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step",
                 "rsr_physics_applied_view", "rsr_physics_set_jac_sites", "rsr_physics_dynamics", "rsr_physics_dynamics_view",
                 "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
                 "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts",
-                "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd", "rsr_physics_lqr_backward"]
+                "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd", "rsr_physics_lqr_backward", "rsr_physics_ik"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -119,6 +119,29 @@ class LqrOut(C.Structure):
 LQR_REG_STATE = 1
 
 
+class IkTask(C.Structure):
+    """struct rsr_ik_task (include/rsr_physics.h): the site table, shared by every slot and passed by value: nsite, the site ids,
+    the position and orientation weights (0 = off) and the dof mask (bit i: dof i may move)."""
+    _fields_ = [("nsite", C.c_int32), ("sites", C.c_int32 * MAX_JAC_SITES), ("pos_weight", C.c_float * MAX_JAC_SITES),
+                ("rot_weight", C.c_float * MAX_JAC_SITES), ("dofs", C.c_uint32)]
+
+
+class IkIn(C.Structure):
+    """struct rsr_ik_in (include/rsr_physics.h): device pointers, target_pos [M, nsite, 3], target_quat [M, nsite, 4] (NULL = no
+    orientation rows), qpos0 [M, nq] (NULL = the record's qpos), damping [M]."""
+    _fields_ = [(n, C.c_void_p) for n in ("target_pos", "target_quat", "qpos0", "damping")]
+
+
+class IkOpt(C.Structure):
+    """struct rsr_ik_opt (include/rsr_physics.h)"""
+    _fields_ = [("iters", C.c_int32), ("tol_pos", C.c_float), ("tol_rot", C.c_float), ("max_step", C.c_float), ("limits", C.c_int32)]
+
+
+class IkOut(C.Structure):
+    """struct rsr_ik_out (include/rsr_physics.h): device pointers, qpos [M, nq] and err [M, 2] float32, info [M, 2] int32."""
+    _fields_ = [(n, C.c_void_p) for n in ("qpos", "err", "info")]
+
+
 SYMBOLS = [
     "rsr_model_create", "rsr_model_dims", "rsr_model_destroy", "rsr_batch_create", "rsr_batch_destroy",
     "rsr_batch_set_dr", "rsr_batch_set_dr_field", "rsr_batch_set_schedule", "rsr_batch_set_whole_envs", "rsr_batch_set_priority", "rsr_batch_set_action_repeat", "rsr_batch_check", "rsr_batch_set_fault_injection", "rsr_rollout_metrics", "rsr_reset", "rsr_step", "rsr_view", "rsr_batch_set_debug",
@@ -177,6 +200,7 @@ def lib() -> C.CDLL:
     L.rsr_physics_feedback_rollouts.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.rsr_physics_trajectory_fd.argtypes = [vp, vp, i32, vp, i32, i32, C.c_float, i32, vp, vp]
     L.rsr_physics_lqr_backward.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
+    L.rsr_physics_ik.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

@@ -7,6 +7,18 @@
 
 namespace rsr {
 
+// Column `dof` of mj_jacSite for a site of body b (rsr_physics_dynamics and rsr_physics_ik), after kinematics and com_crb_mass:
+// cdof_i is dof i's spatial velocity about the subtree COM of its tree's root (ang, lin), so at the site jacr = ang and
+// jacp = lin + ang x (site - com[root]), as smooth_forces takes slinvel from cvel; zero off the body's chain.  dof < NV.
+struct SiteJac { V3 p, r; };
+template <class C>
+__device__ __forceinline__ SiteJac site_jac(const DModel& m, const Smem<C>& s, int site, int b, int dof) {
+  const bool on = (m.body_dofmask[b] >> dof) & 1;
+  const V3 dif = ld3(&s.spos[3 * site]) - ld3(&s.com[3 * m.body_rootid[b]]);
+  const V3 ang = ld3(&s.cdof[6 * dof]), lin = ld3(&s.cdof[6 * dof + 3]) + cross(ang, dif);
+  return SiteJac{V3{on ? lin.x : 0.0f, on ? lin.y : 0.0f, on ? lin.z : 0.0f}, V3{on ? ang.x : 0.0f, on ? ang.y : 0.0f, on ? ang.z : 0.0f}};
+}
+
 // One wave per env, a plain launch.  d.ids: the envs to run or null (env = workgroup index); an id out of range runs nothing.
 template <class C, int WAVES>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
@@ -52,19 +64,16 @@ void dynamics_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, DynArg
     if (rd_frc.y) act = clampf(act, asf(rd_frc.z), asf(rd_frc.w));      // the joint's actfrcrange
     o[DL.bias + i] = bias; o[DL.passive + i] = passive; o[DL.actuator + i] = act;
   }
-  // mj_jacSite: cdof_i is dof i's spatial velocity about the subtree COM of its tree's root (ang, lin), so at the site
-  // jacr = ang and jacp = lin + ang x (site - com[root]), as smooth_forces takes slinvel from cvel; zero off the body's chain
+  // mj_jacSite (site_jac)
   const int nsite = d.nsite;
   if (lane < 3 * nsite) o[DL.sxpos + lane] = s.spos[3 * d.sites[lane / 3] + lane % 3];
   for (int k = 0; k < nsite; ++k) {
     const int site = d.sites[k], b = m.site_bodyid[site];
     if (lane < C::NV) {
-      const bool on = (m.body_dofmask[b] >> lane) & 1;
-      const V3 dif = ld3(&s.spos[3 * site]) - ld3(&s.com[3 * m.body_rootid[b]]);
-      const V3 ang = ld3(&s.cdof[6 * lane]), lin = ld3(&s.cdof[6 * lane + 3]) + cross(ang, dif);
+      const SiteJac J = site_jac<C>(m, s, site, b, lane);
       float* j = o + DL.jac + k * 6 * C::NV + lane;
-      j[0] = on ? lin.x : 0.0f; j[C::NV] = on ? lin.y : 0.0f; j[2 * C::NV] = on ? lin.z : 0.0f;
-      j[3 * C::NV] = on ? ang.x : 0.0f; j[4 * C::NV] = on ? ang.y : 0.0f; j[5 * C::NV] = on ? ang.z : 0.0f;
+      j[0] = J.p.x; j[C::NV] = J.p.y; j[2 * C::NV] = J.p.z;
+      j[3 * C::NV] = J.r.x; j[4 * C::NV] = J.r.y; j[5 * C::NV] = J.r.z;
     }
   }
 }

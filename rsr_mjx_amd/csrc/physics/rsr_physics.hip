@@ -3,7 +3,8 @@
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse), sampled rollouts (rsr_physics_sample_rollouts), parameter
 // rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts), the transition Jacobians along a
-// trajectory (rsr_physics_trajectory_fd) and the LQR backward pass (rsr_physics_lqr_backward).  Every launch is a physics op
+// trajectory (rsr_physics_trajectory_fd), the LQR backward pass (rsr_physics_lqr_backward) and inverse kinematics on site pose
+// targets (rsr_physics_ik).  Every launch is a physics op
 // (rsr::PhysOp) sent through physics_launch; the kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
@@ -509,6 +510,44 @@ extern "C" int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const floa
   x.ph.lq = rsr::LqrArgs{columns, row_stride, T, cost->lx, cost->lu, cost->lxx, cost->luu, cost->lux, mu, flags,
                          out->gain, out->k, out->dv, out->status, out->vx, out->vxx};
   return physics_launch(p, rsr::OP_LQR_BACKWARD, x, "rsr_physics_lqr_backward");
+}
+
+// One launch, one wave per slot (rsr_ik.hpp).  The task table goes by value; none of the handle's buffers is used.
+extern "C" int rsr_physics_ik(rsr_physics* p, const int32_t* env_ids, int count, const rsr_ik_task* task, const rsr_ik_in* in,
+                              const rsr_ik_opt* opt, const rsr_ik_out* out, void* hip_stream) {
+  const char* who = "rsr_physics_ik";
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_ik: null handle");
+  if (!task || !in || !opt || !out) return fail(RSR_ERR_ARG, "rsr_physics_ik: null task, in, opt or out");
+  if (!in->target_pos || !in->damping) return fail(RSR_ERR_ARG, "rsr_physics_ik: in needs target_pos and damping (target_quat and qpos0 may be null)");
+  if (!out->qpos || !out->err || !out->info) return fail(RSR_ERR_ARG, "rsr_physics_ik: out needs qpos, err and info");
+  int n;
+  if (const int rc = env_count(p, env_ids, count, who, &n)) return rc;
+  const rsr_dims& d = p->b->model->dims;
+  if (task->nsite < 1 || task->nsite > RSR_MAX_JAC_SITES)
+    return fail(RSR_ERR_ARG, "rsr_physics_ik: nsite must lie in [1, " + std::to_string(RSR_MAX_JAC_SITES) + "]");
+  bool any = false, rot = false;
+  for (int k = 0; k < task->nsite; ++k) {
+    if (task->sites[k] < 0 || task->sites[k] >= d.nsite) return fail(RSR_ERR_ARG, "rsr_physics_ik: site " + std::to_string(k) + ": site id out of range");
+    const float wp = task->pos_weight[k], wr = task->rot_weight[k];
+    if (!std::isfinite(wp) || !std::isfinite(wr) || wp < 0.0f || wr < 0.0f) return fail(RSR_ERR_ARG, "rsr_physics_ik: site " + std::to_string(k) + ": weights must be finite and >= 0");
+    any = any || wp > 0.0f || wr > 0.0f;
+    rot = rot || wr > 0.0f;
+  }
+  if (!any) return fail(RSR_ERR_ARG, "rsr_physics_ik: every weight is zero");
+  if (rot && !in->target_quat) return fail(RSR_ERR_ARG, "rsr_physics_ik: a positive rot_weight needs target_quat");
+  if (d.nv < 32 && (task->dofs >> d.nv) != 0u) return fail(RSR_ERR_ARG, "rsr_physics_ik: dofs has a bit at or above nv");
+  if (opt->iters < 0) return fail(RSR_ERR_ARG, "rsr_physics_ik: iters must be >= 0");
+  if (!std::isfinite(opt->tol_pos) || !std::isfinite(opt->tol_rot) || !std::isfinite(opt->max_step) || opt->tol_pos < 0.0f || opt->tol_rot < 0.0f || opt->max_step < 0.0f)
+    return fail(RSR_ERR_ARG, "rsr_physics_ik: tol_pos, tol_rot and max_step must be finite and >= 0");
+  if (opt->limits != 0 && opt->limits != 1) return fail(RSR_ERR_ARG, "rsr_physics_ik: limits must be 0 or 1");
+  rsr::Launch x = physics_args(p, nullptr, nullptr, n, 1, hip_stream);
+  rsr::IkArgs& q = x.ph.ik = rsr::IkArgs{};
+  q.target_pos = in->target_pos; q.target_quat = in->target_quat; q.qpos0 = in->qpos0; q.damping = in->damping; q.ids = env_ids;
+  q.qpos = out->qpos; q.err = out->err; q.info = out->info;
+  for (int k = 0; k < task->nsite; ++k) { q.sites[k] = task->sites[k]; q.wp[k] = task->pos_weight[k]; q.wr[k] = task->rot_weight[k]; }
+  q.dofs = task->dofs; q.nsite = task->nsite; q.iters = opt->iters; q.limits = opt->limits;
+  q.tol_pos = opt->tol_pos; q.tol_rot = opt->tol_rot; q.max_step = opt->max_step;
+  return physics_launch(p, rsr::OP_IK, x, who);
 }
 
 // the inverse buffer, on first use

@@ -149,6 +149,24 @@ struct LqrArgs {
   float *gain, *k, *dv, *status;      // [M][T][nu][nx], [M][T][nu], [M][2], [M]
   float *vx, *vxx;      // [M][T+1][nx], [M][T+1][nx][nx], each null = not recorded
 };
+// rsr_physics_ik (rsr_ik.hpp): the caller's buffers, every row indexed by slot, and the task table by value (PhysLaunch::ik): the
+// op has no device table and no state in the handle.
+struct IkArgs {
+  const float* target_pos;   // [M][nsite][3]
+  const float* target_quat;  // [M][nsite][4] (w, x, y, z), or null: no orientation row
+  const float* qpos0;        // [M][nq] the starts, or null: the record's qpos of the slot's env
+  const float* damping;      // [M]
+  const int* ids;            // [M] the env of every slot, or null: env = slot
+  float* qpos;               // [M][nq]
+  float* err;                // [M][2] perr, rerr at the returned qpos
+  int* info;                 // [M][2] iterations taken, status
+  int sites[RSR_MAX_JAC_SITES];
+  float wp[RSR_MAX_JAC_SITES], wr[RSR_MAX_JAC_SITES];   // row weights, 0 = off
+  unsigned dofs;             // bit i: dof i may move
+  int nsite, iters, limits;
+  float tol_pos, tol_rot, max_step;
+};
+static_assert(sizeof(IkArgs) == 64 + 12 * RSR_MAX_JAC_SITES + 32, "ik_kernel's kernel-argument block");
 
 // The physics ops of a family unit's launch entry (launch_physics, rsr_physics_kernels.hpp).  An entry takes its op as an int, of
 // enum Op (rsr_launch.hpp) or of this enum: these start above enum Op's, so that no value names two ops.  A new op is a member
@@ -168,6 +186,7 @@ enum PhysOp {
   OP_TRAJ_NOMINAL,       // rsr_physics_trajectory_fd, first launch (p, tj): grid = envs or listed envs (p.ids)
   OP_TRAJ_FD,            // rsr_physics_trajectory_fd, second launch (p, tj): grid = envs x T x columns, or listed envs (p.ids) x T x columns
   OP_LQR_BACKWARD,       // rsr_physics_lqr_backward (lq): grid = slots; reads neither the model nor the record
+  OP_IK,                 // rsr_physics_ik (ik): grid = slots, the env of a slot from ik.ids
 };
 // The physics ops' arguments (Launch::ph), one field per op that needs its own
 struct PhysLaunch {
@@ -181,6 +200,7 @@ struct PhysLaunch {
   SweepArgs sw;         // OP_PHYS_SWEEP
   TrajArgs tj;          // OP_TRAJ_NOMINAL, OP_TRAJ_FD
   LqrArgs lq;           // OP_LQR_BACKWARD
+  IkArgs ik;            // OP_IK
   Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
 };
 

@@ -31,6 +31,10 @@
                                                                                           (A_t, B_t and a quadratic cost model in,
                                                                                            the gains of feedback_rollouts out; one
                                                                                            launch, nothing of the env is read)
+    an IK library on top of mj_jacSite          ->  Physics.ik(sites, target_pos, target_quat=None)
+                                                                                          (which qpos puts these sites there:
+                                                                                           damped least squares, M problems in one
+                                                                                           launch; the record stays)
     mj_inverse / mjx.inverse (data.qfrc_inverse)  ->  Physics.inverse(qacc)               (the force behind a given acceleration,
                                                                                            no solve: qfrc_inverse)
 
@@ -110,6 +114,7 @@ class Physics:
         self._feedback_in = None                   # the inputs of feedback_rollouts()'s last launch
         self._trajectory_in = None                 # the control sequences of trajectory_fd()'s last launches
         self._lqr_in = None                        # the inputs of lqr_backward()'s last launch
+        self._ik_in = None                         # the inputs of ik()'s last launch
         # the env-id tensor of each entry point's last launch (_call_envs)
         self._ids_in: Dict[str, Any] = {}
         if sensors is not None:
@@ -790,6 +795,145 @@ class Physics:
         _lib.check(_lib.lib().rsr_physics_lqr_backward(self._h, M, T, C.c_void_p(columns.data_ptr()), w, C.byref(cost),
                                                        C.c_void_p(mu_t.data_ptr()), _lib.LQR_REG_STATE if state_reg else 0,
                                                        C.byref(ptrs), self._stream()))
+        return res
+
+    def ik(self, sites, target_pos, target_quat=None, pos_weight=1.0, rot_weight=None, dofs=None, qpos0=None, damping=1e-3,
+           iters: int = 20, tol_pos: float = 1e-4, tol_rot: float = 1e-3, max_step: float = 0.3, limits: bool = True,
+           env_ids=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """Inverse kinematics on site pose targets: which qpos puts these sites there.  Damped least squares (Levenberg-Marquardt
+        with a fixed damping) on M independent problems, one launch with one wave per slot and every iteration inside it.
+        M = len(env_ids) (default: every env; an env may be listed more than once): slot s takes its model, its per-env leaves
+        and its default start from env env_ids[s].  All tensors float32, contiguous, on the env's device.
+        sites: 1 to _lib.MAX_JAC_SITES site names or ids, K of them, one table for every slot (independent of set_jac_sites);
+        target_pos [M, K, 3]; target_quat [M, K, 4] (w, x, y, z; normalised on the device) or None; pos_weight, rot_weight: a
+        float or K floats >= 0, 0 = off (rot_weight defaults to 0 without target_quat, to 1 with it; a positive rot_weight
+        without target_quat and all weights zero are errors); dofs: None for every hinge and slide dof, or dof indices, or a
+        bool mask [nv] (free-joint dofs allowed); qpos0 [M, nq] or None: the record's qpos; damping: a float > 0 or a tensor
+        [M] read on the device; iters >= 0; tol_pos, tol_rot >= 0 (0: every iteration runs); max_step >= 0 (0: no cap on
+        max|dq|); limits: clamp hinge / slide joints to jnt_range where jnt_limited, after every step.
+            q = start
+            for it = 0, 1, ...:
+                kinematics(q)                       # normalises free-joint quaternions in q
+                e_k = p*_k - p_k;  r_k = rotation vector of R*_k R_k^T (world frame, the short way round)
+                perr = max_k |e_k| (pos_weight_k > 0);  rerr = max_k |r_k| (rot_weight_k > 0)
+                if it == iters or (perr <= tol_pos and rerr <= tol_rot): stop     # status 0 if the tolerances hold, else 1
+                J = rows pos_weight_k jacp_k, rot_weight_k jacr_k, columns outside dofs zeroed;  b = the weighted errors
+                dq = (J^T J + damping I)^-1 J^T b;  if max|dq| > max_step > 0: dq *= max_step / max|dq|
+                q = mj_integratePos(q, dq);  if limits: clamp
+        Returns qpos [M, nq], err [M, 2] (perr, rerr at the returned qpos), info [M, 2] int32 (iterations taken, status; status
+        2: the damping was not finite and positive or dq was not finite, the slot stopped at its last q, the other slots are
+        unaffected).  iters=0 is a forward-kinematics query: the start and its error.  `out`: caller-owned tensors under those
+        names to fill instead of new ones.  A slot's result depends on that slot's inputs alone, bit for bit.  Nothing else is
+        written, not the record and no buffer of the handle: adopt a result with set_state(qpos=res["qpos"], ...)."""
+        import math
+        import numpy as np
+        import torch
+        who = "ik"
+        d, dev = self.dims, self.qvel.device
+        nv, nq, nsite = int(d.nv), int(d.nq), int(d.nsite)
+        ids = None if env_ids is None else self._ids(env_ids, who, repeats=True)
+        M = self.num_envs if ids is None else int(ids.numel())
+        site_ids = []
+        for s_ in ([sites] if isinstance(sites, (str, int)) else list(sites)):
+            if isinstance(s_, str):
+                try:
+                    sid = int(self.env.sys.id("site", s_))
+                except Exception:
+                    raise ValueError(f"{who}: no site {s_!r}") from None
+            else:
+                sid = int(s_)
+            if not 0 <= sid < nsite:
+                raise ValueError(f"{who}: site ids must lie in [0, {nsite}), got {sid}")
+            site_ids.append(sid)
+        K = len(site_ids)
+        if not 1 <= K <= _lib.MAX_JAC_SITES:
+            raise ValueError(f"{who} expects 1 to {_lib.MAX_JAC_SITES} sites, got {K}")
+
+        def f32(name, t, shape):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+                got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"{who} expects {name} as a contiguous float32 tensor of shape {shape} on {dev}, got {got}")
+
+        f32("target_pos", target_pos, (M, K, 3))
+        if target_quat is not None:
+            f32("target_quat", target_quat, (M, K, 4))
+        if qpos0 is not None:
+            f32("qpos0", qpos0, (M, nq))
+
+        def weights(name, w):
+            try:
+                v = np.asarray(w, dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who} expects {name} as a float or {K} floats") from None
+            v = np.full(K, v[0]) if v.size == 1 else v
+            if v.shape != (K,) or not np.isfinite(v).all() or (v < 0).any():
+                raise ValueError(f"{who} expects {name} as a float or {K} floats, finite and >= 0")
+            return v
+
+        wp = weights("pos_weight", pos_weight)
+        wr = weights("rot_weight", (0.0 if target_quat is None else 1.0) if rot_weight is None else rot_weight)
+        if (wr > 0).any() and target_quat is None:
+            raise ValueError(f"{who}: a positive rot_weight needs target_quat")
+        if not ((wp > 0).any() or (wr > 0).any()):
+            raise ValueError(f"{who}: every weight is zero")
+        if dofs is None:
+            A = self.env.sys.arrays
+            sel = [int(A["jnt_dofadr"][j]) for j in range(len(A["jnt_type"])) if int(A["jnt_type"][j]) in (2, 3)]
+        else:
+            dd = np.asarray(dofs.cpu() if torch.is_tensor(dofs) else dofs)
+            if dd.dtype == np.bool_:
+                if dd.shape != (nv,):
+                    raise ValueError(f"{who} expects dofs as dof indices or a bool mask of shape ({nv},)")
+                sel = [int(i) for i in np.nonzero(dd)[0]]
+            else:
+                if dd.ndim != 1 or not np.issubdtype(dd.dtype, np.integer) or ((dd < 0) | (dd >= nv)).any():
+                    raise ValueError(f"{who} expects dofs as dof indices in [0, {nv}) or a bool mask of shape ({nv},)")
+                sel = [int(i) for i in dd]
+        mask = 0
+        for i in sel:
+            mask |= 1 << i
+        if torch.is_tensor(damping):
+            f32("damping", damping, (M,))
+            lam = damping
+        else:
+            try:
+                lam_f = float(damping)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who} expects damping as a float > 0 or a float32 tensor of shape ({M},) on {dev}") from None
+            if not (math.isfinite(lam_f) and lam_f > 0.0):
+                raise ValueError(f"{who} expects damping as a float > 0 or a float32 tensor of shape ({M},) on {dev}")
+            lam = torch.full((M,), lam_f, dtype=torch.float32, device=dev)
+        iters = int(iters)
+        if iters < 0:
+            raise ValueError(f"{who}: iters must be >= 0, got {iters}")
+        tol_pos, tol_rot, max_step = float(tol_pos), float(tol_rot), float(max_step)
+        for name, v in (("tol_pos", tol_pos), ("tol_rot", tol_rot), ("max_step", max_step)):
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{who}: {name} must be finite and >= 0, got {v}")
+        oshapes = dict(qpos=((M, nq), torch.float32), err=((M, 2), torch.float32), info=((M, 2), torch.int32))
+        out = dict(out or {})
+        unknown = sorted(set(out) - set(oshapes))
+        if unknown:
+            raise ValueError(f"{who}: out has {unknown}; it may hold {tuple(oshapes)}")
+        res, ptrs = {}, _lib.IkOut()
+        for f, (shape, dt) in oshapes.items():
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=dev)
+            elif not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{who}: out[{f!r}] must be a contiguous {str(dt).split('.')[-1]} tensor of shape {shape} on {dev}")
+            res[f] = t
+            setattr(ptrs, f, t.data_ptr())
+        task = _lib.IkTask(nsite=K, dofs=mask)
+        for k in range(K):
+            task.sites[k], task.pos_weight[k], task.rot_weight[k] = site_ids[k], float(wp[k]), float(wr[k])
+        ins = _lib.IkIn(target_pos.data_ptr(), None if target_quat is None else target_quat.data_ptr(),
+                        None if qpos0 is None else qpos0.data_ptr(), lam.data_ptr())
+        opt = _lib.IkOpt(iters, tol_pos, tol_rot, max_step, 1 if limits else 0)
+        self._ik_in = (target_pos, target_quat, qpos0, lam)       # kept alive until the next call (the launch is asynchronous)
+        if M == 0:
+            return res
+        self._call_envs("rsr_physics_ik", who, ids, C.byref(task), C.byref(ins), C.byref(opt), C.byref(ptrs), checked=True)
         return res
 
     def forward(self) -> None:
