@@ -64,6 +64,15 @@ class _DevArray:
                                              strides=tuple(4 * int(s) for s in strides_elems))
 
 
+def _eps(who: str, eps) -> float:
+    """a finite-difference step as a float, finite and > 0"""
+    import math
+    eps = float(eps)
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"{who}: eps must be finite and > 0, got {eps}")
+    return eps
+
+
 def _view(ptr, shape, stride, device):
     import torch
     if shape[1] == 0:                              # (sensordata while no sensors are set)
@@ -108,15 +117,10 @@ class Physics:
         self._fd: Dict[str, Any] = {}
         # the inverse buffer's views (inverse): likewise
         self._inv: Optional[Dict[str, Any]] = None
-        self._qacc_in = None                       # the accelerations of inverse()'s last launch
-        self._sample_ctrl_in = None                # the control sequences of sample_rollouts()'s last launch
-        self._param_in = None                      # the control sequences and leaf tensors of param_rollouts()'s last launch
-        self._feedback_in = None                   # the inputs of feedback_rollouts()'s last launch
-        self._trajectory_in = None                 # the control sequences of trajectory_fd()'s last launches
-        self._lqr_in = None                        # the inputs of lqr_backward()'s last launch
-        self._ik_in = None                         # the inputs of ik()'s last launch
-        # the env-id tensor of each entry point's last launch (_call_envs)
-        self._ids_in: Dict[str, Any] = {}
+        # {method name: the tensors its last launch reads, the int32 env ids included}.  The launches are asynchronous, so an entry
+        # is written ahead of the C call and replaced by that method's next launch only: another method's launch may follow at
+        # once, and must not drop what the one in flight still reads.
+        self._held: Dict[str, tuple] = {}
         if sensors is not None:
             self.set_sensors(sensors)
 
@@ -190,20 +194,85 @@ class Physics:
             raise ValueError(f"{who}: env_ids must not repeat")
         return ids
 
-    def _call_envs(self, fn: str, who: str, env_ids, *args, checked: bool = False) -> None:
-        """The library's env-list entry point `fn`(handle, ids, count, *args, stream) for the method `who`: env_ids None runs every
-        env (null, 0), an empty list nothing.  checked: env_ids already went through _ids.  The int32 ids stay alive in `who`'s
-        own slot until its next call: the launch is asynchronous, and another entry point's may follow it at once."""
+    def _env_list(self, who: str, env_ids, checked: bool = False):
+        """env_ids as the library's entry points take a list: (pointer, count, the int32 tensor behind the pointer).  None is every
+        env: (null, 0, None).  An empty list gives None, and the caller makes no call.  checked: env_ids already went through _ids."""
         import torch
-        ptr, k = None, 0
-        if env_ids is not None:
-            ids = env_ids if checked else self._ids(env_ids, who)
-            k = ids.numel()
-            if k == 0:
-                return
-            ids32 = self._ids_in[who] = ids.to(torch.int32).contiguous()
-            ptr = C.c_void_p(ids32.data_ptr())
+        if env_ids is None:
+            return None, 0, None
+        ids = env_ids if checked else self._ids(env_ids, who)
+        k = ids.numel()
+        if k == 0:
+            return None
+        ids32 = ids.to(torch.int32).contiguous()
+        return C.c_void_p(ids32.data_ptr()), k, ids32
+
+    def _call_envs(self, fn: str, who: str, env_ids, *args, checked: bool = False, hold: tuple = ()) -> None:
+        """The library's env-list entry point `fn`(handle, ids, count, *args, stream) for the method `who`: env_ids None runs every
+        env, an empty list nothing.  `hold`: the tensors `args` point into; with the ids they are `who`'s held inputs."""
+        lst = self._env_list(who, env_ids, checked)
+        if lst is None:
+            return
+        ptr, k, ids32 = lst
+        self._held[who] = (*hold, ids32)
         _lib.check(getattr(_lib.lib(), fn)(self._h, ptr, k, *args, self._stream()))
+
+    def _steps(self, who: str, nsteps, below_2_30: bool = False) -> int:
+        """nsteps (None: n_substeps) as an int >= 1"""
+        nsteps = self.n_substeps if nsteps is None else int(nsteps)
+        if below_2_30 and not 1 <= nsteps < 2 ** 30:
+            raise ValueError(f"{who}: nsteps must lie in [1, 2^30), got {nsteps}")
+        if nsteps < 1:
+            raise ValueError(f"{who}: nsteps must be >= 1, got {nsteps}")
+        return nsteps
+
+    def _f32(self, what: str, t, shape_txt: str, ok, contiguous: bool, got: bool = False) -> None:
+        """Refuses `t` unless it is a float32 tensor on the env's device that `ok` takes (a shape, or a predicate of the tensor)
+        and, if asked, contiguous.  what: how the message opens ("<method> expects <name> as"); got: it ends with what `t` is."""
+        import torch
+        dev = self.qvel.device
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or not (ok(t) if callable(ok) else tuple(t.shape) == ok) \
+                or (contiguous and not t.is_contiguous()):
+            is_ = "" if not got else f", got {tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else f", got {type(t).__name__}"
+            raise ValueError(f"{what} a {'contiguous ' if contiguous else ''}float32 tensor of shape {shape_txt} on {dev}{is_}")
+
+    def _site_ids(self, who: str, sites) -> list:
+        """site names or ids as ids, checked"""
+        ids = []
+        for s_ in sites:
+            if isinstance(s_, str):
+                try:
+                    sid = int(self.env.sys.id("site", s_))
+                except Exception:
+                    raise ValueError(f"{who}: no site {s_!r}") from None
+            else:
+                sid = int(s_)
+            if not 0 <= sid < self.dims.nsite:
+                raise ValueError(f"{who}: site ids must lie in [0, {self.dims.nsite}), got {sid}")
+            ids.append(sid)
+        return ids
+
+    def _outputs(self, who: str, shapes: Dict[str, Any], out, strict: bool, note: str = "") -> Dict[str, Any]:
+        """{name: tensor} for `shapes` {name: shape, or (shape, dtype) where it is not float32}, on the env's device: out[name] where
+        the caller gave one (refused unless it is a contiguous tensor of that shape, dtype and device), else a new one.  strict: a
+        key of `out` that `shapes` does not have is refused (`note` ends that message), else ignored."""
+        import torch
+        dev = self.qvel.device
+        out = out or {}
+        if strict and not out.keys() <= shapes.keys():
+            raise ValueError(f"{who}: out has {sorted(set(out) - set(shapes))}; it may hold {tuple(shapes)}{note}")
+        res = {}
+        for f, shape in shapes.items():
+            dt = torch.float32
+            if type(shape[-1]) is torch.dtype:
+                shape, dt = shape
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=dev)
+            elif not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{who}: out[{f!r}] must be a contiguous {str(dt).split('.')[-1]} tensor of shape {shape} on {dev}")
+            res[f] = t
+        return res
 
     def set_applied(self, xfrc=None, qfrc=None, env_ids=None) -> None:
         """data.replace(xfrc_applied=..., qfrc_applied=...): turns applied forces on (zero everywhere the first time) and writes
@@ -266,18 +335,7 @@ class Physics:
         """The sites whose Jacobians dynamics() evaluates (mj_jacSite): names or ids, at most _lib.MAX_JAC_SITES; None or []
         clears the table (jacp / jacr get K = 0).  Earlier jacp / jacr / jac_site_xpos views keep their old K: read them again."""
         import numpy as np
-        ids = []
-        for s_ in list(sites or []):
-            if isinstance(s_, str):
-                try:
-                    sid = int(self.env.sys.id("site", s_))
-                except Exception:
-                    raise ValueError(f"set_jac_sites: no site {s_!r}") from None
-            else:
-                sid = int(s_)
-            if not 0 <= sid < self.dims.nsite:
-                raise ValueError(f"set_jac_sites: site ids must lie in [0, {self.dims.nsite}), got {sid}")
-            ids.append(sid)
+        ids = self._site_ids("set_jac_sites", list(sites or []))
         if len(ids) > _lib.MAX_JAC_SITES:
             raise ValueError(f"set_jac_sites expects at most {_lib.MAX_JAC_SITES} sites, got {len(ids)}")
         table = np.asarray(ids, dtype=np.int32)
@@ -366,13 +424,7 @@ class Physics:
         friction loss, limits and contacts make the step piecewise smooth, and the result depends on eps.  keep_states also
         records the runs' inputs and end states (fd_x, fd_y).  Writes nothing else: not the record, the side buffer, sensordata,
         the dynamics or the constraint buffer."""
-        import math
-        nsteps = self.n_substeps if nsteps is None else int(nsteps)
-        if nsteps < 1:
-            raise ValueError(f"transition_fd: nsteps must be >= 1, got {nsteps}")
-        eps = float(eps)
-        if not (math.isfinite(eps) and eps > 0.0):
-            raise ValueError(f"transition_fd: eps must be finite and > 0, got {eps}")
+        nsteps, eps = self._steps("transition_fd", nsteps), _eps("transition_fd", eps)
         flags = (_lib.FD_CENTERED if centered else 0) | (_lib.FD_STATES if keep_states else 0)
         self._call_envs("rsr_physics_transition_fd", "transition_fd", env_ids, nsteps, eps, flags)
 
@@ -403,20 +455,13 @@ class Physics:
         by the row stiffness on every active contact or limit row, so differenced fp32 velocities give noisy forces there.
         Like dynamics() it describes the state after the last integration and writes nothing else; applied forces enter none of
         the outputs."""
-        import torch
         shape = (self.num_envs, self.dims.nv)
-        if not torch.is_tensor(qacc) or qacc.dtype != torch.float32 or tuple(qacc.shape) != shape or not qacc.is_contiguous() \
-                or qacc.device != self.qvel.device:
-            raise ValueError(f"inverse expects qacc as a contiguous float32 tensor of shape {shape} on {self.qvel.device}")
-        ptr, k = None, 0
-        if env_ids is not None:
-            ids = self._ids(env_ids, "inverse")
-            k = ids.numel()
-            if k == 0:
-                return
-            ids32 = self._ids_in["inverse"] = ids.to(torch.int32).contiguous()
-            ptr = C.c_void_p(ids32.data_ptr())
-        self._qacc_in = qacc                       # kept alive until the next call (the launch is asynchronous)
+        self._f32("inverse expects qacc as", qacc, shape, shape, True)
+        lst = self._env_list("inverse", env_ids)
+        if lst is None:
+            return
+        ptr, k, ids32 = lst
+        self._held["inverse"] = (qacc, ids32)
         _lib.check(_lib.lib().rsr_physics_inverse(self._h, C.c_void_p(qacc.data_ptr()), ptr, k, _lib.INV_DISCRETE if discrete else 0,
                                                   self._stream()))
 
@@ -428,36 +473,16 @@ class Physics:
         pass.  `out`: caller-owned float32 tensors to fill instead of new ones.  Afterwards the record and the side buffer hold
         what T calls of step would leave."""
         import torch
-        nsteps = self.n_substeps if nsteps is None else int(nsteps)
-        if nsteps < 1:
-            raise ValueError(f"rollout: nsteps must be >= 1, got {nsteps}")
+        nsteps = self._steps("rollout", nsteps)
         c = torch.as_tensor(ctrl, dtype=torch.float32, device=self.device)
         if c.dim() != 3 or c.shape[0] != self.num_envs or c.shape[2] != self.dims.nu or c.shape[1] < 1:
             raise ValueError(f"rollout expects ctrl of shape ({self.num_envs}, T >= 1, {self.dims.nu}), got {tuple(c.shape)}")
         T = int(c.shape[1])
-        fields = tuple(fields)
-        bad = [f for f in fields if f not in ROLLOUT_FIELDS]
-        if bad:
-            raise ValueError(f"rollout: unknown fields {bad}; recordable: {ROLLOUT_FIELDS}")
-        if "sensordata" in fields and self.nsensordata == 0:
-            raise ValueError("rollout: sensordata requested but no sensors are set (set_sensors)")
-        d = self.dims
-        width = dict(qpos=d.nq, qvel=d.nv, time=1, actuator_force=d.nu, ncon=1, sensordata=self.nsensordata)
-        res, ptrs = {}, _lib.RolloutOut()
-        out = out or {}
-        for f in fields:
-            shape = (self.num_envs, T, width[f])
-            t = out.get(f)
-            if t is None:
-                t = torch.empty(shape, dtype=torch.float32, device=self.device)
-            elif (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != c.device):
-                raise ValueError(f"rollout: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {c.device}")
-            res[f] = t
-            setattr(ptrs, f, t.data_ptr())
+        res, ptrs = self._trajectory_out("rollout", fields, (self.num_envs, T), out, none_ok=True)
         if qpos0 is not None or qvel0 is not None or ctrl0 is not None:
             self.set_state(qpos0, qvel0, ctrl0)
         c = c.contiguous()
-        self._ctrl_in = c                          # kept alive until the next call (the launch is asynchronous)
+        self._held["rollout"] = (c,)
         _lib.check(_lib.lib().rsr_physics_rollout(self._h, C.c_void_p(c.data_ptr()), T, nsteps, C.byref(ptrs), self._stream()))
         return res
 
@@ -473,39 +498,16 @@ class Physics:
         side buffer, sensordata and every other buffer of the handle stay as they are, so step() goes on from where the batch
         stood.  A field takes 4 * M * K * T * w bytes: asking for fewer fields is the only lever (a cost on sensor values needs
         fields=("sensordata",) alone)."""
-        import torch
-        nsteps = self.n_substeps if nsteps is None else int(nsteps)
-        if nsteps < 1:
-            raise ValueError(f"sample_rollouts: nsteps must be >= 1, got {nsteps}")
-        ids = None if env_ids is None else self._ids(env_ids, "sample_rollouts")
+        who = "sample_rollouts"
+        nsteps = self._steps(who, nsteps)
+        ids = None if env_ids is None else self._ids(env_ids, who)
         M, nu = self.num_envs if ids is None else int(ids.numel()), self.dims.nu
-        if not torch.is_tensor(ctrl) or ctrl.dtype != torch.float32 or ctrl.dim() != 4 or ctrl.shape[0] != M or ctrl.shape[3] != nu \
-                or ctrl.shape[1] < 1 or ctrl.shape[2] < 1 or ctrl.device != self.qvel.device:
-            raise ValueError(f"sample_rollouts expects ctrl as a float32 tensor of shape ({M}, K >= 1, T >= 1, {nu}) on {self.qvel.device}")
+        self._f32(f"{who} expects ctrl as", ctrl, f"({M}, K >= 1, T >= 1, {nu})",
+                  lambda t: t.dim() == 4 and t.shape[0] == M and t.shape[3] == nu and t.shape[1] >= 1 and t.shape[2] >= 1, False)
         K, T = int(ctrl.shape[1]), int(ctrl.shape[2])
-        fields = tuple(fields)
-        bad = [f for f in fields if f not in ROLLOUT_FIELDS]
-        if bad or not fields:
-            raise ValueError(f"sample_rollouts: unknown or no fields {bad}; recordable: {ROLLOUT_FIELDS}")
-        if "sensordata" in fields and self.nsensordata == 0:
-            raise ValueError("sample_rollouts: sensordata requested but no sensors are set (set_sensors)")
-        d = self.dims
-        width = dict(qpos=d.nq, qvel=d.nv, time=1, actuator_force=d.nu, ncon=1, sensordata=self.nsensordata)
-        res, ptrs = {}, _lib.RolloutOut()
-        out = out or {}
-        for f in fields:
-            shape = (M, K, T, width[f])
-            t = out.get(f)
-            if t is None:
-                t = torch.empty(shape, dtype=torch.float32, device=ctrl.device)
-            elif (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != ctrl.device):
-                raise ValueError(f"sample_rollouts: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {ctrl.device}")
-            res[f] = t
-            setattr(ptrs, f, t.data_ptr())
+        res, ptrs = self._trajectory_out(who, fields, (M, K, T), out)
         c = ctrl.contiguous()
-        self._sample_ctrl_in = c                   # kept alive until the next call (the launch is asynchronous)
-        self._call_envs("rsr_physics_sample_rollouts", "sample_rollouts", ids, C.c_void_p(c.data_ptr()), K, T, nsteps, C.byref(ptrs),
-                        checked=True)
+        self._call_envs("rsr_physics_sample_rollouts", who, ids, C.c_void_p(c.data_ptr()), K, T, nsteps, C.byref(ptrs), checked=True, hold=(c,))
         return res
 
     def _leaf_shapes(self) -> Dict[str, tuple]:
@@ -517,9 +519,7 @@ class Physics:
     def _sampled_leaves(self, who: str, params, M: int, K: Optional[int]):
         """(_lib.ParamSamples, the tensors it points to, K) of `params` {leaf name: [M, K, ...]}, checked for the method `who`; K:
         what the caller's other inputs say, or None"""
-        import torch
         from .envs import config as cfg
-        dev = self.qvel.device
         params = dict(params or {})
         unknown = sorted(set(params) - set(_lib.DR_FIELDS))
         if unknown:
@@ -532,10 +532,9 @@ class Physics:
                 continue
             if fid >= _lib.DR_FIELDS.index("body_ipos") and int(self.dims.env_kind) not in (cfg.ENV_GO2, cfg.ENV_GO2_HANDSTAND):
                 raise ValueError(f"{who}: {name} is a per-sample leaf on the Go2 models only")
-            want = f"({M}, K >= 1, {', '.join(str(int(w)) for w in shapes[name])})"
-            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 + len(shapes[name]) or t.shape[0] != M or t.shape[1] < 1 \
-                    or tuple(t.shape[2:]) != tuple(int(w) for w in shapes[name]) or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"{who}: params[{name!r}] must be a contiguous float32 tensor of shape {want} on {dev}")
+            tail = tuple(int(w) for w in shapes[name])
+            self._f32(f"{who}: params[{name!r}] must be", t, f"({M}, K >= 1, {', '.join(map(str, tail))})",
+                      lambda t: t.dim() == 2 + len(tail) and t.shape[0] == M and t.shape[1] >= 1 and tuple(t.shape[2:]) == tail, True)
             if K is not None and int(t.shape[1]) != K:
                 raise ValueError(f"{who}: params[{name!r}] has K = {int(t.shape[1])}, the others (or ctrl) K = {K}")
             K = int(t.shape[1])
@@ -543,29 +542,21 @@ class Physics:
             leaves.append(t)
         return ps, leaves, K
 
-    def _trajectory_out(self, who: str, fields, lead: tuple, out, extra: Optional[Dict[str, int]] = None):
+    def _trajectory_out(self, who: str, fields, lead: tuple, out, extra: Optional[Dict[str, int]] = None, none_ok: bool = False):
         """({field: tensor lead + (w,)}, _lib.RolloutOut) for `fields` of ROLLOUT_FIELDS (and of `extra` {name: width}, which
-        RolloutOut does not hold), checked for the method `who`; `out`: caller-owned tensors to use instead of new ones"""
-        import torch
+        RolloutOut does not hold), checked for the method `who`; `out`: caller-owned tensors to use instead of new ones (its other
+        keys are ignored); none_ok: no field at all is a request too"""
         extra = extra or {}
         fields = tuple(fields)
         bad = [f for f in fields if f not in ROLLOUT_FIELDS and f not in extra]
-        if bad or not fields:
-            raise ValueError(f"{who}: unknown or no fields {bad}; recordable: {ROLLOUT_FIELDS + tuple(extra)}")
+        if bad or not (fields or none_ok):
+            raise ValueError(f"{who}: unknown{'' if none_ok else ' or no'} fields {bad}; recordable: {ROLLOUT_FIELDS + tuple(extra)}")
         if "sensordata" in fields and self.nsensordata == 0:
             raise ValueError(f"{who}: sensordata requested but no sensors are set (set_sensors)")
-        d, dev = self.dims, self.qvel.device
+        d = self.dims
         width = dict(qpos=d.nq, qvel=d.nv, time=1, actuator_force=d.nu, ncon=1, sensordata=self.nsensordata, **extra)
-        res, ptrs = {}, _lib.RolloutOut()
-        out = out or {}
-        for f in fields:
-            shape = tuple(lead) + (width[f],)
-            t = out.get(f)
-            if t is None:
-                t = torch.empty(shape, dtype=torch.float32, device=dev)
-            elif (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
-                raise ValueError(f"{who}: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {dev}")
-            res[f] = t
+        res, ptrs = self._outputs(who, {f: tuple(lead) + (width[f],) for f in fields}, out, False), _lib.RolloutOut()
+        for f, t in res.items():
             if f not in extra:
                 setattr(ptrs, f, t.data_ptr())
         return res, ptrs
@@ -586,25 +577,21 @@ class Physics:
         `fields` (ROLLOUT_FIELDS, as rollout), rows in env_ids order.  `out`: caller-owned float32 tensors to fill instead of new
         ones.  Writes nothing else: the record, the side buffer, sensordata, every other buffer of the handle and the batch's own
         leaf tensors stay as they are.  A field takes 4 * M * K * T * w bytes: ask for what the loss reads."""
-        import torch
-        nsteps = self.n_substeps if nsteps is None else int(nsteps)
-        if nsteps < 1:
-            raise ValueError(f"param_rollouts: nsteps must be >= 1, got {nsteps}")
-        ids = None if env_ids is None else self._ids(env_ids, "param_rollouts")
-        M, nu, dev = self.num_envs if ids is None else int(ids.numel()), self.dims.nu, self.qvel.device
-        if not torch.is_tensor(ctrl) or ctrl.dtype != torch.float32 or ctrl.dim() not in (3, 4) or ctrl.shape[0] != M or ctrl.shape[-1] != nu \
-                or min(ctrl.shape[1:-1]) < 1 or ctrl.device != dev:
-            raise ValueError(f"param_rollouts expects ctrl as a float32 tensor of shape ({M}, T >= 1, {nu}) or ({M}, K >= 1, T >= 1, {nu}) on {dev}")
+        who = "param_rollouts"
+        nsteps = self._steps(who, nsteps)
+        ids = None if env_ids is None else self._ids(env_ids, who)
+        M, nu = self.num_envs if ids is None else int(ids.numel()), self.dims.nu
+        self._f32(f"{who} expects ctrl as", ctrl, f"({M}, T >= 1, {nu}) or ({M}, K >= 1, T >= 1, {nu})",
+                  lambda t: t.dim() in (3, 4) and t.shape[0] == M and t.shape[-1] == nu and min(t.shape[1:-1]) >= 1, False)
         per_sample = ctrl.dim() == 4
         T, K = int(ctrl.shape[-2]), int(ctrl.shape[1]) if per_sample else None
-        ps, leaves, K = self._sampled_leaves("param_rollouts", params, M, K)
+        ps, leaves, K = self._sampled_leaves(who, params, M, K)
         if K is None:
-            raise ValueError("param_rollouts: K is not given: pass sampled leaves in params, or a 4-D ctrl [M, K, T, nu]")
-        res, ptrs = self._trajectory_out("param_rollouts", fields, (M, K, T), out)
+            raise ValueError(f"{who}: K is not given: pass sampled leaves in params, or a 4-D ctrl [M, K, T, nu]")
+        res, ptrs = self._trajectory_out(who, fields, (M, K, T), out)
         c = ctrl.contiguous()
-        self._param_in = (c, leaves)               # kept alive until the next call (the launch is asynchronous)
-        self._call_envs("rsr_physics_param_rollouts", "param_rollouts", ids, C.c_void_p(c.data_ptr()), C.byref(ps), K, T, nsteps,
-                        _lib.PR_CTRL_PER_SAMPLE if per_sample else 0, C.byref(ptrs), checked=True)
+        self._call_envs("rsr_physics_param_rollouts", who, ids, C.c_void_p(c.data_ptr()), C.byref(ps), K, T, nsteps,
+                        _lib.PR_CTRL_PER_SAMPLE if per_sample else 0, C.byref(ptrs), checked=True, hold=(c, *leaves))
         return res
 
     def feedback_rollouts(self, ctrl, gain, qpos_ref, qvel_ref, params=None, nsteps: Optional[int] = None,
@@ -625,21 +612,17 @@ class Physics:
         [M, K, T, nu] (fed to sample_rollouts they reproduce the trajectories bit for bit).  `out`: caller-owned float32 tensors
         to fill instead of new ones.  Writes nothing else: the record, every buffer of the handle and the batch's own leaf
         tensors stay as they are.  A field takes 4 * M * K * T * w bytes: ask for what the cost reads."""
-        import torch
         who = "feedback_rollouts"
-        nsteps = self.n_substeps if nsteps is None else int(nsteps)
-        if nsteps < 1:
-            raise ValueError(f"{who}: nsteps must be >= 1, got {nsteps}")
+        nsteps = self._steps(who, nsteps)
         ids = None if env_ids is None else self._ids(env_ids, who)
-        d, dev = self.dims, self.qvel.device
+        d = self.dims
         M, nu, nv, nq = self.num_envs if ids is None else int(ids.numel()), int(d.nu), int(d.nv), int(d.nq)
 
         def rows(name, t, tail, ranks):
             """(K or None, T) of a [M, (K,) T, *tail] input"""
-            want = f"({M}, T >= 1, {', '.join(map(str, tail))}) or ({M}, K >= 1, T >= 1, {', '.join(map(str, tail))})"
-            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() not in ranks or t.shape[0] != M \
-                    or tuple(t.shape[t.dim() - len(tail):]) != tail or min(t.shape[1:t.dim() - len(tail)]) < 1 or t.device != dev:
-                raise ValueError(f"{who} expects {name} as a float32 tensor of shape {want} on {dev}")
+            self._f32(f"{who} expects {name} as", t, f"({M}, T >= 1, {', '.join(map(str, tail))}) or ({M}, K >= 1, T >= 1, {', '.join(map(str, tail))})",
+                      lambda t: t.dim() in ranks and t.shape[0] == M and tuple(t.shape[t.dim() - len(tail):]) == tail
+                      and min(t.shape[1:t.dim() - len(tail)]) >= 1, False)
             per = t.dim() == len(tail) + 3
             return (int(t.shape[1]) if per else None), int(t.shape[-len(tail) - 1])
 
@@ -662,11 +645,10 @@ class Physics:
         res, ptrs = self._trajectory_out(who, fields, (M, K, T), out, extra=dict(ctrl=nu))
         c, g, qr, vr = ctrl.contiguous(), gain.contiguous(), qpos_ref.contiguous(), qvel_ref.contiguous()
         fb = _lib.Feedback(g.data_ptr(), qr.data_ptr(), vr.data_ptr())
-        self._feedback_in = (c, g, qr, vr, leaves)  # kept alive until the next call (the launch is asynchronous)
         flags = (_lib.FB_CTRL_PER_SAMPLE if Kc is not None else 0) | (_lib.FB_PER_SAMPLE if Kg is not None else 0) | (_lib.FB_CLAMP if clamp else 0)
         applied = C.c_void_p(res["ctrl"].data_ptr()) if "ctrl" in res else None
         self._call_envs("rsr_physics_feedback_rollouts", who, ids, C.c_void_p(c.data_ptr()), C.byref(fb), C.byref(ps), K, T, nsteps, flags,
-                        C.byref(ptrs), applied, checked=True)
+                        C.byref(ptrs), applied, checked=True, hold=(c, g, qr, vr, *leaves))
         return res
 
     def trajectory_fd(self, ctrl, nsteps: Optional[int] = None, eps: float = 1e-3, centered: bool = True, env_ids=None,
@@ -685,44 +667,24 @@ class Physics:
         after control step t.  `out`: caller-owned float32 tensors ("columns", "qpos", "qvel") to fill instead of new ones.
         Writes nothing else but a scratch buffer of the handle: the record, the side buffer, sensordata and every other buffer
         of the handle stay as they are.  Two calls on one Physics must not overlap on different streams (they share the scratch)."""
-        import math
-        import torch
         who = "trajectory_fd"
-        nsteps = self.n_substeps if nsteps is None else int(nsteps)
-        if not 1 <= nsteps < 2 ** 30:
-            raise ValueError(f"{who}: nsteps must lie in [1, 2^30), got {nsteps}")
-        eps = float(eps)
-        if not (math.isfinite(eps) and eps > 0.0):
-            raise ValueError(f"{who}: eps must be finite and > 0, got {eps}")
+        nsteps, eps = self._steps(who, nsteps, below_2_30=True), _eps(who, eps)
         ids = None if env_ids is None else self._ids(env_ids, who, repeats=True)
-        d, dev = self.dims, self.qvel.device
+        d = self.dims
         M, nu, nv, nq, nsd = self.num_envs if ids is None else int(ids.numel()), int(d.nu), int(d.nv), int(d.nq), self.nsensordata
-        if not torch.is_tensor(ctrl) or ctrl.dtype != torch.float32 or ctrl.dim() != 3 or ctrl.shape[0] != M or ctrl.shape[2] != nu \
-                or ctrl.shape[1] < 1 or ctrl.device != dev:
-            raise ValueError(f"{who} expects ctrl as a float32 tensor of shape ({M}, T >= 1, {nu}) on {dev}")
+        self._f32(f"{who} expects ctrl as", ctrl, f"({M}, T >= 1, {nu})",
+                  lambda t: t.dim() == 3 and t.shape[0] == M and t.shape[2] == nu and t.shape[1] >= 1, False)
         T, ncol, w = int(ctrl.shape[1]), 2 * nv + nu, 2 * nv + nsd
         if T * nsteps >= 2 ** 31 or M * T * ncol >= 2 ** 31:
             raise ValueError(f"{who}: T * nsteps and M * T * ncol must stay below 2^31")
         shapes = dict(columns=(M, T, ncol, w))
         if nominal:
             shapes.update(qpos=(M, T + 1, nq), qvel=(M, T + 1, nv))
-        out = dict(out or {})
-        unknown = sorted(set(out) - set(shapes))
-        if unknown:
-            raise ValueError(f"{who}: out has {unknown}; it may hold {tuple(shapes)}" + ("" if nominal else " (nominal=False)"))
-        res, ptrs = {}, _lib.TrajectoryFdOut()
-        for f, shape in shapes.items():
-            t = out.get(f)
-            if t is None:
-                t = torch.empty(shape, dtype=torch.float32, device=dev)
-            elif not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"{who}: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {dev}")
-            res[f] = t
-            setattr(ptrs, f, t.data_ptr())
+        res = self._outputs(who, shapes, out, True, "" if nominal else " (nominal=False)")
+        ptrs = _lib.TrajectoryFdOut(**{f: t.data_ptr() for f, t in res.items()})
         c = ctrl.contiguous()
-        self._trajectory_in = c                    # kept alive until the next call (the launches are asynchronous)
         self._call_envs("rsr_physics_trajectory_fd", who, ids, C.c_void_p(c.data_ptr()), T, nsteps, eps, _lib.FD_CENTERED if centered else 0,
-                        C.byref(ptrs), checked=True)
+                        C.byref(ptrs), checked=True, hold=(c,))
         # the buffer holds one row per column of [A B; C D]: the blocks are transposed views, as fd_A .. fd_D
         col, x, u, sn = res["columns"], slice(0, 2 * nv), slice(2 * nv, ncol), slice(2 * nv, w)
         res.update(A=col[:, :, x, x].transpose(2, 3), B=col[:, :, u, x].transpose(2, 3), C=col[:, :, x, sn].transpose(2, 3),
@@ -751,23 +713,17 @@ class Physics:
         nv, nu = int(d.nv), int(d.nu)
         nx, ncol = 2 * nv, 2 * nv + nu
 
-        def f32(name, t, shape_txt, ok):
-            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or not ok(t) or not t.is_contiguous():
-                raise ValueError(f"{who} expects {name} as a contiguous float32 tensor of shape {shape_txt} on {dev}")
-
-        f32("columns", columns, f"(M >= 1, T >= 1, {ncol}, w >= {nx})",
-            lambda t: t.dim() == 4 and t.shape[0] >= 1 and t.shape[1] >= 1 and t.shape[2] == ncol and t.shape[3] >= nx)
+        self._f32(f"{who} expects columns as", columns, f"(M >= 1, T >= 1, {ncol}, w >= {nx})",
+                  lambda t: t.dim() == 4 and t.shape[0] >= 1 and t.shape[1] >= 1 and t.shape[2] == ncol and t.shape[3] >= nx, True)
         M, T, w = int(columns.shape[0]), int(columns.shape[1]), int(columns.shape[3])
         if M * (T + 1) >= 2 ** 31:
             raise ValueError(f"{who}: M * (T + 1) must stay below 2^31")
         shapes = dict(lx=(M, T + 1, nx), lu=(M, T, nu), lxx=(M, T + 1, nx, nx), luu=(M, T, nu, nu), lux=(M, T, nu, nx))
-        given = dict(lx=lx, lu=lu, lxx=lxx, luu=luu, lux=lux)
-        for name, t in given.items():
-            if t is None and name == "lux":
-                continue
-            f32(name, t, f"{shapes[name]} (M and T as columns has them)", lambda t, name=name: tuple(t.shape) == shapes[name])
+        for name, t in dict(lx=lx, lu=lu, lxx=lxx, luu=luu, lux=lux).items():
+            if t is not None or name != "lux":
+                self._f32(f"{who} expects {name} as", t, f"{shapes[name]} (M and T as columns has them)", shapes[name], True)
         if torch.is_tensor(mu):
-            f32("mu", mu, f"({M},), or a float", lambda t: tuple(t.shape) == (M,))
+            self._f32(f"{who} expects mu as", mu, f"({M},), or a float", (M,), True)
             mu_t = mu
         else:
             try:
@@ -777,21 +733,10 @@ class Physics:
         oshapes = dict(gain=(M, T, nu, nx), k=(M, T, nu), dV=(M, 2), status=(M,))
         if values:
             oshapes.update(Vx=(M, T + 1, nx), Vxx=(M, T + 1, nx, nx))
-        out = dict(out or {})
-        unknown = sorted(set(out) - set(oshapes))
-        if unknown:
-            raise ValueError(f"{who}: out has {unknown}; it may hold {tuple(oshapes)}" + ("" if values else " (values=False)"))
-        res, ptrs = {}, _lib.LqrOut()
-        for f, shape in oshapes.items():
-            t = out.get(f)
-            if t is None:
-                t = torch.empty(shape, dtype=torch.float32, device=dev)
-            elif not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"{who}: out[{f!r}] must be a contiguous float32 tensor of shape {shape} on {dev}")
-            res[f] = t
-            setattr(ptrs, dict(dV="dv", Vx="vx", Vxx="vxx").get(f, f), t.data_ptr())
+        res = self._outputs(who, oshapes, out, True, "" if values else " (values=False)")
+        ptrs = _lib.LqrOut(**{dict(dV="dv", Vx="vx", Vxx="vxx").get(f, f): t.data_ptr() for f, t in res.items()})
         cost = _lib.LqrCost(lx.data_ptr(), lu.data_ptr(), lxx.data_ptr(), luu.data_ptr(), None if lux is None else lux.data_ptr())
-        self._lqr_in = (columns, lx, lu, lxx, luu, lux, mu_t)       # kept alive until the next call (the launch is asynchronous)
+        self._held[who] = (columns, lx, lu, lxx, luu, lux, mu_t)
         _lib.check(_lib.lib().rsr_physics_lqr_backward(self._h, M, T, C.c_void_p(columns.data_ptr()), w, C.byref(cost),
                                                        C.c_void_p(mu_t.data_ptr()), _lib.LQR_REG_STATE if state_reg else 0,
                                                        C.byref(ptrs), self._stream()))
@@ -830,35 +775,16 @@ class Physics:
         import torch
         who = "ik"
         d, dev = self.dims, self.qvel.device
-        nv, nq, nsite = int(d.nv), int(d.nq), int(d.nsite)
+        nv, nq = int(d.nv), int(d.nq)
         ids = None if env_ids is None else self._ids(env_ids, who, repeats=True)
         M = self.num_envs if ids is None else int(ids.numel())
-        site_ids = []
-        for s_ in ([sites] if isinstance(sites, (str, int)) else list(sites)):
-            if isinstance(s_, str):
-                try:
-                    sid = int(self.env.sys.id("site", s_))
-                except Exception:
-                    raise ValueError(f"{who}: no site {s_!r}") from None
-            else:
-                sid = int(s_)
-            if not 0 <= sid < nsite:
-                raise ValueError(f"{who}: site ids must lie in [0, {nsite}), got {sid}")
-            site_ids.append(sid)
+        site_ids = self._site_ids(who, [sites] if isinstance(sites, (str, int)) else list(sites))
         K = len(site_ids)
         if not 1 <= K <= _lib.MAX_JAC_SITES:
             raise ValueError(f"{who} expects 1 to {_lib.MAX_JAC_SITES} sites, got {K}")
-
-        def f32(name, t, shape):
-            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
-                got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
-                raise ValueError(f"{who} expects {name} as a contiguous float32 tensor of shape {shape} on {dev}, got {got}")
-
-        f32("target_pos", target_pos, (M, K, 3))
-        if target_quat is not None:
-            f32("target_quat", target_quat, (M, K, 4))
-        if qpos0 is not None:
-            f32("qpos0", qpos0, (M, nq))
+        for name, t, shape in (("target_pos", target_pos, (M, K, 3)), ("target_quat", target_quat, (M, K, 4)), ("qpos0", qpos0, (M, nq))):
+            if t is not None or name == "target_pos":
+                self._f32(f"{who} expects {name} as", t, shape, shape, True, got=True)
 
         def weights(name, w):
             try:
@@ -893,7 +819,7 @@ class Physics:
         for i in sel:
             mask |= 1 << i
         if torch.is_tensor(damping):
-            f32("damping", damping, (M,))
+            self._f32(f"{who} expects damping as", damping, (M,), (M,), True, got=True)
             lam = damping
         else:
             try:
@@ -911,29 +837,18 @@ class Physics:
             if not (math.isfinite(v) and v >= 0.0):
                 raise ValueError(f"{who}: {name} must be finite and >= 0, got {v}")
         oshapes = dict(qpos=((M, nq), torch.float32), err=((M, 2), torch.float32), info=((M, 2), torch.int32))
-        out = dict(out or {})
-        unknown = sorted(set(out) - set(oshapes))
-        if unknown:
-            raise ValueError(f"{who}: out has {unknown}; it may hold {tuple(oshapes)}")
-        res, ptrs = {}, _lib.IkOut()
-        for f, (shape, dt) in oshapes.items():
-            t = out.get(f)
-            if t is None:
-                t = torch.empty(shape, dtype=dt, device=dev)
-            elif not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"{who}: out[{f!r}] must be a contiguous {str(dt).split('.')[-1]} tensor of shape {shape} on {dev}")
-            res[f] = t
-            setattr(ptrs, f, t.data_ptr())
+        res = self._outputs(who, oshapes, out, True)
+        ptrs = _lib.IkOut(**{f: t.data_ptr() for f, t in res.items()})
         task = _lib.IkTask(nsite=K, dofs=mask)
         for k in range(K):
             task.sites[k], task.pos_weight[k], task.rot_weight[k] = site_ids[k], float(wp[k]), float(wr[k])
         ins = _lib.IkIn(target_pos.data_ptr(), None if target_quat is None else target_quat.data_ptr(),
                         None if qpos0 is None else qpos0.data_ptr(), lam.data_ptr())
         opt = _lib.IkOpt(iters, tol_pos, tol_rot, max_step, 1 if limits else 0)
-        self._ik_in = (target_pos, target_quat, qpos0, lam)       # kept alive until the next call (the launch is asynchronous)
         if M == 0:
             return res
-        self._call_envs("rsr_physics_ik", who, ids, C.byref(task), C.byref(ins), C.byref(opt), C.byref(ptrs), checked=True)
+        self._call_envs("rsr_physics_ik", who, ids, C.byref(task), C.byref(ins), C.byref(opt), C.byref(ptrs), checked=True,
+                        hold=(target_pos, target_quat, qpos0, lam))
         return res
 
     def forward(self) -> None:
@@ -944,16 +859,14 @@ class Physics:
     def step(self, ctrl=None, nsteps: Optional[int] = None) -> None:
         """Writes `ctrl` [num_envs, nu] (None: keep the record's) and runs `nsteps` (default n_substeps) x mjx.step."""
         import torch
-        nsteps = self.n_substeps if nsteps is None else int(nsteps)
-        if nsteps < 1:
-            raise ValueError(f"step: nsteps must be >= 1, got {nsteps}")
+        nsteps = self._steps("step", nsteps)
         ptr = None
         if ctrl is not None:
             c = torch.as_tensor(ctrl, dtype=torch.float32, device=self.device)
             if c.shape != (self.num_envs, self.dims.nu):
                 raise ValueError(f"step expects ctrl of shape ({self.num_envs}, {self.dims.nu}), got {tuple(c.shape)}")
             c = c.contiguous()
-            self._ctrl_in = c                      # kept alive until the next call (the launch is asynchronous)
+            self._held["step"] = (c,)
             ptr = C.c_void_p(c.data_ptr())
         _lib.check(_lib.lib().rsr_physics_step(self._h, ptr, nsteps, self._stream()))
 

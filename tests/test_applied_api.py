@@ -4,15 +4,11 @@ import ctypes as C
 import os
 import re
 
-from conftest import ROOT
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+from api_support import ROOT, header
 
 
 def test_header_declares_the_applied_api():
-    h = _header()
+    h = header()
     for sig in ("int rsr_physics_set_applied(rsr_physics* p, int on);",
                 "int rsr_physics_applied_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);"):
         assert sig in h, sig
@@ -29,7 +25,7 @@ def test_header_declares_the_applied_api():
 def test_library_exports_and_argument_checks():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     for sym in ("rsr_physics_set_applied", "rsr_physics_applied_view"):
         assert sym in _lib.PHYS_SYMBOLS and getattr(L, sym) is not None
         assert getattr(L, sym).argtypes is not None

@@ -6,17 +6,11 @@ import inspect
 import os
 import re
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+from api_support import CSRC, HANDLE, STREAM, header, ints, record, standin
 
 
 def test_header_declares_the_constraint_api():
-    h = _header()
+    h = header()
     for sig in ("int rsr_physics_constraint(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream);",
                 "int rsr_physics_constraint_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);"):
         assert sig in h, sig
@@ -36,7 +30,7 @@ def test_header_declares_the_constraint_api():
 def test_library_exports_and_argument_checks():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     for sym in ("rsr_physics_constraint", "rsr_physics_constraint_view"):
         assert sym in _lib.PHYS_SYMBOLS and getattr(L, sym) is not None
         assert getattr(L, sym).argtypes is not None
@@ -118,7 +112,7 @@ def test_the_kernel_lives_in_the_physics_layer():
     assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     from rsr_mjx_amd.physics import Physics
     for m in ("constraint_forces", "contact_forces"):
         assert callable(getattr(Physics, m))
@@ -129,5 +123,9 @@ def test_physics_module_surface():
     src = inspect.getsource(Physics.contact_forces)
     for key in ("ncon=", "dist=", "pos=", "normal=", "geom1=", "geom2=", "normal_force=", "force=", "torque="):
         assert key in src, key
-    assert 'self._call_envs("rsr_physics_constraint", "constraint_forces", env_ids)' in inspect.getsource(Physics.constraint_forces)
-    assert "getattr(_lib.lib(), fn)(self._h, ptr, k, *args, self._stream())" in inspect.getsource(Physics._call_envs)
+    # the env-list calling convention: (handle, ids, count, stream), null and 0 for every env
+    p, rec = standin(), record(monkeypatch)
+    p.constraint_forces()
+    p.constraint_forces([2, 0])
+    (s0, a0), (s1, (h, ids, k, stream)) = rec.calls
+    assert s0 == s1 == "rsr_physics_constraint" and a0 == (HANDLE, None, 0, STREAM) and (h, k, stream) == (HANDLE, 2, STREAM) and ints(ids, 2) == [2, 0]

@@ -6,15 +6,11 @@ import inspect
 import os
 import re
 
-from conftest import ROOT
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+from api_support import ROOT, header, refused, standin
 
 
 def test_header_declares_the_dynamics_api():
-    h = _header()
+    h = header()
     for sig in ("int rsr_physics_set_jac_sites(rsr_physics* p, const int32_t* site_ids, int nsite);",
                 "int rsr_physics_dynamics(rsr_physics* p, const int32_t* env_ids, int count, void* hip_stream);",
                 "int rsr_physics_dynamics_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);"):
@@ -35,7 +31,7 @@ def test_header_declares_the_dynamics_api():
 def test_library_exports_and_argument_checks():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     for sym in ("rsr_physics_set_jac_sites", "rsr_physics_dynamics", "rsr_physics_dynamics_view"):
         assert sym in _lib.PHYS_SYMBOLS and getattr(L, sym) is not None
         assert getattr(L, sym).argtypes is not None
@@ -138,7 +134,7 @@ def test_the_dynamics_op_is_an_ordinary_op():
         assert absent not in kern, absent
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     from rsr_mjx_amd.physics import Physics
     for m in ("set_jac_sites", "dynamics"):
         assert callable(getattr(Physics, m))
@@ -146,5 +142,6 @@ def test_physics_module_surface():
     assert list(inspect.signature(Physics.set_jac_sites).parameters) == ["self", "sites"]
     for view in ("qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "jacp", "jacr", "jac_site_xpos"):
         assert isinstance(getattr(Physics, view), property), view
-    src = inspect.getsource(Physics.set_jac_sites)
-    assert "ValueError" in src and "set_jac_sites expects at most" in src
+    refused(monkeypatch, standin().set_jac_sites, [(dict(sites=[0, 1, 2, 3] * 3), "set_jac_sites expects at most 8 sites, got 12"),
+                                                   (dict(sites=["tip", "nose"]), "set_jac_sites: no site 'nose'"),
+                                                   (dict(sites=[0, 4]), r"set_jac_sites: site ids must lie in \[0, 4\), got 4")])

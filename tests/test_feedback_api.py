@@ -5,28 +5,18 @@ import ctypes as C
 import inspect
 import os
 import re
-import types
 
 import pytest
 
-from conftest import ROOT
+from api_support import CSRC, ROOT, body as _body, header, read as _read, record, refused, standin
 
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
 SIG = ("int rsr_physics_feedback_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, "
        "const rsr_feedback* fb, const rsr_param_samples* params, int K, int T, int nsteps, "
        "int flags, const rsr_rollout_out* out, float* ctrl_out, void* hip_stream);")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
-
-
-def _read(*parts):
-    return open(os.path.join(CSRC, *parts)).read()
-
-
 def test_header_declares_the_call_the_struct_and_the_flags():
-    h = _header()
+    h = header()
     flat = re.sub(r"\s+", " ", h)
     assert SIG in flat                                             # (the declaration may break its lines)
     assert "typedef struct rsr_feedback { const float* gain; const float* qpos_ref; const float* qvel_ref; } rsr_feedback;" in flat
@@ -44,7 +34,7 @@ def test_header_declares_the_call_the_struct_and_the_flags():
 def test_library_exports_and_null_handle():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     assert "rsr_physics_feedback_rollouts" in _lib.PHYS_SYMBOLS
     fn = L.rsr_physics_feedback_rollouts
     assert fn.argtypes is not None and len(fn.argtypes) == 13
@@ -60,11 +50,6 @@ def test_library_exports_and_null_handle():
             for applied in (None, ctrl):
                 assert fn(None, table, k, ctrl, C.byref(fb), params, 1, 1, 1, 0, C.byref(o), applied, None) == -1
                 assert b"rsr_physics_feedback_rollouts: null handle" in L.rsr_last_error()
-
-
-def _body(src, name):
-    b = src[src.index(name + "("):]
-    return b[:b.index("\n}\n")]
 
 
 def test_refusals_come_before_device_work():
@@ -139,7 +124,7 @@ def test_the_stage_is_a_header_of_its_own_called_twice():
         assert word in sec, word
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     import torch
     from rsr_mjx_amd import physics
     from rsr_mjx_amd.physics import Physics
@@ -149,21 +134,12 @@ def test_physics_module_surface():
     assert d == dict(params=None, nsteps=None, fields=("qpos", "qvel", "time"), env_ids=None, clamp=False, out=None, K=None)
     assert "Physics.feedback_rollouts(ctrl, gain, qpos_ref, qvel_ref)" in physics.__doc__
     assert "4 * M * K * T * w bytes" in Physics.feedback_rollouts.__doc__ and '"ctrl"' in Physics.feedback_rollouts.__doc__
-    src = inspect.getsource(Physics.feedback_rollouts)
-    assert 'self._call_envs("rsr_physics_feedback_rollouts", who, ' in src and "_lib.lib()" not in src
-    assert src.rindex("raise ValueError") < src.index("self._call_envs(")
-    assert "self._feedback_in = (c, g, qr, vr, leaves)" in src
     # the siblings are as they were
     assert list(inspect.signature(Physics.param_rollouts).parameters) == ["self", "ctrl", "params", "nsteps", "fields", "env_ids", "out"]
     assert list(inspect.signature(Physics.sample_rollouts).parameters) == ["self", "ctrl", "nsteps", "fields", "env_ids", "out"]
-    # every bad input is refused before the C call (the stand-in has no handle to call with)
-    p = Physics.__new__(Physics)
-    p._h = None
+    # every bad input is refused before the C call: the recording library sees none
     nu, nq, nv = 3, 5, 4
-    dims = types.SimpleNamespace(nu=nu, nq=nq, nv=nv, n_frames=2, ngeom=6, nbody=3, env_kind=0)          # (kind 0: an Airbot model)
-    p.num_envs, p.dims, p.qvel, p.device = 4, dims, torch.zeros((4, 4)), torch.device("cpu")
-    p.sensordata = torch.zeros((4, 0))                      # no sensors set
-    p.env = types.SimpleNamespace(_stream=lambda: None)
+    p = standin(handle=None, nq=nq, nv=nv)                  # (kind 0: an Airbot model; no sensors set)
     z = lambda *s, **kw: torch.zeros(s, **kw)
     M, K, T = 4, 2, 3
     c3, c4 = z(M, T, nu), z(M, K, T, nu)
@@ -221,11 +197,16 @@ def test_physics_module_surface():
              (dict(sh, fields=("sensordata",)), "no sensors are set"),
              (dict(sh, nsteps=0), "nsteps must be >= 1"),
              (dict(sh, out={"qpos": z(M, K, T, nv)}), "out\\['qpos'\\]"),
-             (dict(sh, fields=("ctrl",), out={"ctrl": z(M, T, nu)}), "out\\['ctrl'\\]")]
-    for kw, msg in cases:
-        with pytest.raises(ValueError, match=msg):
-            p.feedback_rollouts(**kw)
+             (dict(sh, fields=("ctrl",), out={"ctrl": z(M, T, nu)}), "out\\['ctrl'\\]"),
+             (dict(sh, out={"qpos": z(M, K, T, nq).numpy()}), "out\\['qpos'\\]")]                       # (once an AttributeError)
+    refused(monkeypatch, p.feedback_rollouts, cases)
     # the good calls get as far as the C call: the stand-in has no handle, and the library refuses it
     for kw in (sh, ps, dict(sh, ctrl=c3, K=2), dict(sh, fields=("ctrl",)), dict(sh, params=dict(body_mass=mass), clamp=True)):
         with pytest.raises(RuntimeError, match="rsr_physics_feedback_rollouts: null handle"):
             p.feedback_rollouts(**kw)
+    # ... as the one library call, with the inputs kept in the method's own slot, not copied
+    rec = record(monkeypatch)
+    p.feedback_rollouts(**dict(sh, params=dict(body_mass=mass)))
+    (sym, args), = rec.calls
+    assert sym == "rsr_physics_feedback_rollouts" and len(args) == 13 and args[3] == c4.data_ptr()
+    assert all(any(t is x for x in p._held["feedback_rollouts"]) for t in (c4, g4, q3, v3, mass))

@@ -5,33 +5,17 @@ import ctypes as C
 import inspect
 import os
 import re
-import types
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
+from api_support import CSRC, ROOT, body as _body, header, ints, read as _read, record, refused, standin
 SIG = ("int rsr_physics_ik(rsr_physics* p, const int32_t* env_ids, int count, const rsr_ik_task* task, const rsr_ik_in* in, "
        "const rsr_ik_opt* opt, const rsr_ik_out* out, void* hip_stream);")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
-
-
-def _read(*parts):
-    return open(os.path.join(CSRC, *parts)).read()
-
-
-def _body(src, name):
-    b = src[src.index(name + "("):]
-    return b[:b.index("\n}\n")]
-
-
 def test_header_declares_the_call_and_the_structs():
-    h = _header()
+    h = header()
     flat = re.sub(r"\s+", " ", h)
     assert SIG in flat
     assert ("typedef struct rsr_ik_task { int32_t nsite; int32_t sites[RSR_MAX_JAC_SITES]; float pos_weight[RSR_MAX_JAC_SITES]; "
@@ -53,7 +37,7 @@ def test_header_declares_the_call_and_the_structs():
 def test_library_exports_structs_and_null_handle():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     assert "rsr_physics_ik" in _lib.PHYS_SYMBOLS
     fn = L.rsr_physics_ik
     assert fn.argtypes is not None and len(fn.argtypes) == 8
@@ -141,7 +125,7 @@ def test_the_kernel_is_a_header_of_its_own_and_shares_the_site_jacobian():
     assert "Physics.ik(" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     import torch
     from rsr_mjx_amd import physics
     from rsr_mjx_amd.physics import Physics
@@ -153,22 +137,10 @@ def test_physics_module_surface():
     for word in ("[M, K, 3]", "[M, K, 4]", "[M, nq]", "err [M, 2]", "info [M, 2]", "status", "damping", "jnt_range", "set_state", "bit for bit",
                  "more than once", "forward-kinematics query"):
         assert word in doc, word
-    src = inspect.getsource(Physics.ik)
-    assert src.rindex("raise ValueError") < src.index("_call_envs(") and src.count("_call_envs(") == 1 and "_lib.lib()" not in src
-    assert "self._ik_in = (target_pos, target_quat, qpos0, lam)" in src and ".contiguous()" not in src and ".clone()" not in src
-    assert "set_jac_sites" not in src.split('"""')[2] and "_dyn" not in src
-    # every bad input is refused before the C call (the stand-in has no handle to call with)
-    p = Physics.__new__(Physics)
-    p._h = None
-    nu, nq, nv, nsite = 3, 6, 5, 4
-    dims = types.SimpleNamespace(nu=nu, nq=nq, nv=nv, nsite=nsite, n_frames=2, ngeom=6, nbody=3, env_kind=0)
-    p.num_envs, p.dims, p.qvel, p.device, p._ids_in = 4, dims, torch.zeros((4, nv)), torch.device("cpu"), {}
-    arrays = dict(jnt_type=np.array([3, 2, 0]), jnt_dofadr=np.array([0, 1, 2]))           # (the stand-in's nv does not matter here)
-    names = {"tip": 2}
-
-    def site_id(kind, name):
-        return names[name]
-    p.env = types.SimpleNamespace(_stream=lambda: None, sys=types.SimpleNamespace(arrays=arrays, id=site_id))
+    # every bad input is refused before the C call: the recording library sees none
+    nq, nv, nsite = 6, 5, 4
+    p = standin(handle=None)
+    p._dyn = before = {}                                     # (the site table of set_jac_sites and its views are not this call's)
     z = lambda *s, **kw: torch.zeros(s, **kw)
     M, K = 4, 2
     good = dict(sites=["tip", 1], target_pos=z(M, K, 3))
@@ -192,9 +164,7 @@ def test_physics_module_surface():
              (dict(good, max_step=-0.1), "max_step must be"), (dict(good, env_ids=[0, 4], target_pos=z(2, K, 3)), "env_ids must lie"),
              (dict(good, out={"qpos": z(M, nq + 1)}), "out\\['qpos'\\]"), (dict(good, out={"err": z(M, 2).double()}), "out\\['err'\\]"),
              (dict(good, out={"info": z(M, 2)}), "out\\['info'\\]"), (dict(good, out={"status": z(M)}), "out has \\['status'\\]")]
-    for kw, msg in cases:
-        with pytest.raises(ValueError, match=msg):
-            p.ik(**kw)
+    refused(monkeypatch, p.ik, cases)
     # the good calls get as far as the C call: the stand-in has no handle, and the library refuses it
     for kw in (good, dict(good, target_quat=z(M, K, 4), rot_weight=[0.2, 0.0], dofs=np.array([True, False, True, True, False])),
                dict(good, sites="tip", target_pos=z(M, 1, 3), damping=torch.full((M,), 1e-2), iters=0, limits=False),
@@ -202,3 +172,12 @@ def test_physics_module_surface():
                     out={"qpos": z(3, nq), "err": z(3, 2), "info": z(3, 2, dtype=torch.int32)})):
         with pytest.raises(RuntimeError, match="rsr_physics_ik: null handle"):
             p.ik(**kw)
+    # ... as the one library call in the env-list convention (repeats allowed), on the caller's very tensors: they are kept in the
+    # method's own slot, none of them copied; set_jac_sites' table is not touched
+    rec = record(monkeypatch)
+    kw = dict(target_pos=z(3, K, 3), target_quat=z(3, K, 4), qpos0=z(3, nq), damping=torch.full((3,), 1e-2))
+    p.ik(["tip", 1], env_ids=[3, 3, 0], **kw)
+    (sym, args), = rec.calls
+    assert sym == "rsr_physics_ik" and len(args) == 8 and args[2] == 3 and ints(args[1], 3) == [3, 3, 0] and p._dyn is before
+    assert [getattr(args[4], n) for n, _ in args[4]._fields_] == [kw[n].data_ptr() for n in ("target_pos", "target_quat", "qpos0", "damping")]
+    assert all(any(t is x for x in p._held["ik"]) for t in kw.values()) and p._held["ik"][-1].data_ptr() == args[1]

@@ -4,21 +4,14 @@ import ctypes as C
 import inspect
 import os
 import re
-import types
 
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+from api_support import CSRC, ROOT, header, refused, standin
 
 
 def test_header_declares_the_inverse_api():
-    h = _header()
+    h = header()
     for sig in ("int rsr_physics_inverse(rsr_physics* p, const float* qacc, const int32_t* env_ids, int count, int flags, void* hip_stream);",
                 "int rsr_physics_inverse_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);"):
         assert sig in h, sig
@@ -41,7 +34,7 @@ def test_header_declares_the_inverse_api():
 def test_library_exports_and_null_arguments():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     for sym in ("rsr_physics_inverse", "rsr_physics_inverse_view"):
         assert sym in _lib.PHYS_SYMBOLS and getattr(L, sym).argtypes is not None
     ids = (C.c_int32 * 2)(0, 1)
@@ -123,7 +116,7 @@ def test_the_kernel_restates_the_pass_without_the_solve():
             assert "inverse_kernel" not in text and "rsr_inverse" not in text and "OP_PHYS_INVERSE" not in text and "InvArgs" not in text, f
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     import torch
     from rsr_mjx_amd import physics
     from rsr_mjx_amd.physics import Physics
@@ -134,16 +127,13 @@ def test_physics_module_surface():
                  "inverse_efc_counts"):
         assert isinstance(getattr(Physics, view), property), view
     assert "Physics.inverse(qacc)" in physics.__doc__ and "mj_inverse" in physics.__doc__
-    # a wrong shape, dtype, layout or device is refused before the C call (the stand-in has no handle to call with)
-    p = Physics.__new__(Physics)
-    p._h = None
-    p.num_envs, p.dims, p.qvel = 4, types.SimpleNamespace(nv=6), torch.zeros((4, 6))
+    # a wrong shape, dtype, layout or device is refused before the C call: the recording library sees none
+    p = standin(nv=6)
     good = torch.zeros((4, 6), dtype=torch.float32)
-    for bad in (torch.zeros((4, 5)), torch.zeros((3, 6)), torch.zeros(24), torch.zeros((4, 6), dtype=torch.float64),
-                torch.zeros((6, 4)).t(), torch.zeros((4, 6), device="meta"), good.numpy(), None):
-        with pytest.raises(ValueError, match="inverse expects qacc"):
-            p.inverse(bad)
-        with pytest.raises(ValueError, match="inverse expects qacc"):
-            p.inverse(bad, env_ids=[0], discrete=True)
-    src = inspect.getsource(Physics.inverse)
-    assert src.index("raise ValueError") < src.index("rsr_physics_inverse")
+    bads = (torch.zeros((4, 5)), torch.zeros((3, 6)), torch.zeros(24), torch.zeros((4, 6), dtype=torch.float64),
+            torch.zeros((6, 4)).t(), torch.zeros((4, 6), device="meta"), good.numpy(), None)
+    msg = r"inverse expects qacc as a contiguous float32 tensor of shape \(4, 6\) on cpu"
+    refused(monkeypatch, p.inverse, [(dict(qacc=bad, **kw), msg) for bad in bads for kw in ({}, dict(env_ids=[0], discrete=True))])
+    # a good one gets as far as the C call: a stand-in without a handle, and the library refuses it
+    with pytest.raises(RuntimeError, match="rsr_physics_inverse: null handle"):
+        standin(handle=None, nv=6).inverse(good, env_ids=[1, 3])

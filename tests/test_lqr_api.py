@@ -5,32 +5,16 @@ import ctypes as C
 import inspect
 import os
 import re
-import types
 
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
+from api_support import CSRC, ROOT, body as _body, header, read as _read, record, refused, standin
 SIG = ("int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const float* columns, int row_stride, const rsr_lqr_cost* cost, "
        "const float* mu, int flags, const rsr_lqr_out* out, void* hip_stream);")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
-
-
-def _read(*parts):
-    return open(os.path.join(CSRC, *parts)).read()
-
-
-def _body(src, name):
-    b = src[src.index(name + "("):]
-    return b[:b.index("\n}\n")]
-
-
 def test_header_declares_the_call_and_the_structs():
-    h = _header()
+    h = header()
     flat = re.sub(r"\s+", " ", h)
     assert SIG in flat                                             # (the declaration may break its lines)
     assert ("typedef struct rsr_lqr_cost { const float* lx; const float* lu; const float* lxx; const float* luu; const float* lux; } "
@@ -51,7 +35,7 @@ def test_header_declares_the_call_and_the_structs():
 def test_library_exports_and_null_handle():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     assert "rsr_physics_lqr_backward" in _lib.PHYS_SYMBOLS
     fn = L.rsr_physics_lqr_backward
     assert fn.argtypes is not None and len(fn.argtypes) == 10
@@ -141,7 +125,7 @@ def test_the_kernel_is_a_header_of_its_own():
         assert word in sub, word
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     import torch
     from rsr_mjx_amd import physics
     from rsr_mjx_amd.physics import Physics
@@ -154,18 +138,11 @@ def test_physics_module_surface():
     for word in ("[M, T, ncol, w]", "[M, T+1, nx]", "[M, T+1, nx, nx]", "[M, T, nu, nu]", "[M, T, nu, nx]", "trajectory_fd", "feedback_rollouts",
                  "dV [M, 2]", "status [M]", "state_reg", "Tassa", "bit for bit"):
         assert word in doc, word
-    src = inspect.getsource(Physics.lqr_backward)
-    assert src.rindex("raise ValueError") < src.index("_lib.lib()") and src.count("_lib.lib()") == 1
-    assert "self._lqr_in = (columns, lx, lu, lxx, luu, lux, mu_t)" in src and ".contiguous()" not in src and ".clone()" not in src
     # the neighbours are as they were
     assert list(inspect.signature(Physics.trajectory_fd).parameters) == ["self", "ctrl", "nsteps", "eps", "centered", "env_ids", "nominal", "out"]
-    # every bad input is refused before the C call (the stand-in has no handle to call with)
-    p = Physics.__new__(Physics)
-    p._h = None
+    # every bad input is refused before the C call: the recording library sees none
     nu, nq, nv = 3, 5, 4
-    dims = types.SimpleNamespace(nu=nu, nq=nq, nv=nv, n_frames=2, ngeom=6, nbody=3, env_kind=0)
-    p.num_envs, p.dims, p.qvel, p.device = 4, dims, torch.zeros((4, 4)), torch.device("cpu")
-    p.env = types.SimpleNamespace(_stream=lambda: None)
+    p = standin(handle=None, nq=nq, nv=nv)
     z = lambda *s, **kw: torch.zeros(s, **kw)
     M, T, nx = 6, 3, 2 * nv                                      # (M is the buffers', not num_envs)
     ncol, w = nx + nu, nx + 2
@@ -204,9 +181,7 @@ def test_physics_module_surface():
              (dict(good, values=True, out={"Vx": z(M, T + 1, nx + 1)[..., :nx]}), "out\\['Vx'\\]"),
              (dict(good, out={"Vx": z(M, T + 1, nx)}), "out has \\['Vx'\\]"),                            # (values=False)
              (dict(good, out={"K": z(M, T, nu, nx)}), "out has \\['K'\\]")]
-    for kw, msg in cases:
-        with pytest.raises(ValueError, match=msg):
-            p.lqr_backward(**kw)
+    refused(monkeypatch, p.lqr_backward, cases)
     # the good calls get as far as the C call: the stand-in has no handle, and the library refuses it
     for kw in (good, dict(good, lux=z(M, T, nu, nx), mu=0.5, state_reg=True), dict(good, mu=z(M), values=True),
                dict(good, columns=z(M, T, ncol, nx)), dict(good, mu=1),
@@ -214,3 +189,11 @@ def test_physics_module_surface():
                                             "Vxx": z(M, T + 1, nx, nx)})):
         with pytest.raises(RuntimeError, match="rsr_physics_lqr_backward: null handle"):
             p.lqr_backward(**kw)
+    # ... as the one library call, on the caller's very tensors: they are kept in the method's own slot, none of them copied
+    rec = record(monkeypatch)
+    kw = dict(good, lux=z(M, T, nu, nx), mu=z(M))
+    p.lqr_backward(**kw)
+    (sym, args), = rec.calls
+    assert sym == "rsr_physics_lqr_backward" and len(args) == 10 and (args[3], args[6]) == (kw["columns"].data_ptr(), kw["mu"].data_ptr())
+    assert [n for n, _ in args[5]._fields_ if getattr(args[5], n) == kw[n].data_ptr()] == ["lx", "lu", "lxx", "luu", "lux"]
+    assert all(any(t is x for x in p._held["lqr_backward"]) for t in kw.values())

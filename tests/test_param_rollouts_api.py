@@ -5,28 +5,18 @@ import ctypes as C
 import inspect
 import os
 import re
-import types
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from api_support import CSRC, ROOT, body as _body, header, read as _read, record, refused, standin
 
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
 SIG = ("int rsr_physics_param_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, "
        "const rsr_param_samples* params, int K, int T, int nsteps, int flags, const rsr_rollout_out* out, void* hip_stream);")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
-
-
-def _read(*parts):
-    return open(os.path.join(CSRC, *parts)).read()
-
-
 def test_header_declares_the_call_and_the_struct():
-    h = _header()
+    h = header()
     flat = re.sub(r"\s+", " ", h)
     assert SIG in flat                                             # (the declaration may break its lines)
     assert "typedef struct rsr_param_samples { const float* leaf[RSR_DR_COUNT]; } rsr_param_samples;" in flat
@@ -43,7 +33,7 @@ def test_header_declares_the_call_and_the_struct():
 def test_library_exports_and_null_handle():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     assert "rsr_physics_param_rollouts" in _lib.PHYS_SYMBOLS
     fn = L.rsr_physics_param_rollouts
     assert fn.argtypes is not None and len(fn.argtypes) == 11
@@ -57,11 +47,6 @@ def test_library_exports_and_null_handle():
         for params in (None, C.byref(ps)):
             assert fn(None, table, k, ctrl, params, 1, 1, 1, 0, C.byref(o), None) == -1
             assert b"null handle" in L.rsr_last_error()
-
-
-def _body(src, name):
-    b = src[src.index(name + "("):]
-    return b[:b.index("\n}\n")]
 
 
 def test_refusals_come_before_device_work():
@@ -170,7 +155,7 @@ def test_the_kernel_is_the_sample_loop_with_one_stage_more():
     assert [ln for ln in sa if ln not in sw and "r.ctrl[" not in ln and "sample_kernel" not in ln and "slot = b / K" not in ln] == []
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     import torch
     from rsr_mjx_amd import physics
     from rsr_mjx_amd.physics import Physics
@@ -180,18 +165,10 @@ def test_physics_module_surface():
     assert d == dict(nsteps=None, fields=("qpos", "qvel", "time"), env_ids=None, out=None)
     assert "Physics.param_rollouts(ctrl [M, T, nu], {leaf: [M, K, ...]})" in physics.__doc__
     assert "4 * M * K * T * w bytes" in Physics.param_rollouts.__doc__
-    src = inspect.getsource(Physics.param_rollouts)
-    assert 'self._call_envs("rsr_physics_param_rollouts", "param_rollouts", ' in src and "_lib.lib()" not in src
-    assert src.rindex("raise ValueError") < src.index("self._call_envs(")
-    assert "self._param_in = (c, leaves)" in src
     # sample_rollouts is as it was
     assert list(inspect.signature(Physics.sample_rollouts).parameters) == ["self", "ctrl", "nsteps", "fields", "env_ids", "out"]
-    # every bad input is refused before the C call (the stand-in has no handle to call with)
-    p = Physics.__new__(Physics)
-    p._h = None
-    dims = types.SimpleNamespace(nu=3, nq=5, nv=4, n_frames=2, ngeom=6, nbody=3, env_kind=0)          # (kind 0: an Airbot model)
-    p.num_envs, p.dims, p.qvel, p.device = 4, dims, torch.zeros((4, 4)), torch.device("cpu")
-    p.sensordata = torch.zeros((4, 0))                      # no sensors set
+    # every bad input is refused before the C call: the recording library sees none
+    p = standin(nq=5, nv=4)                                 # (kind 0: an Airbot model; no sensors set)
     shared, each = torch.zeros((4, 3, 3)), torch.zeros((4, 2, 3, 3))
     mass, fric, damp = torch.zeros((4, 2, 3)), torch.zeros((4, 2, 6, 3)), torch.zeros((4, 2, 4))
     ok = dict(body_mass=mass)
@@ -222,9 +199,14 @@ def test_physics_module_surface():
              (dict(ctrl=shared, params=ok, nsteps=0), "nsteps must be >= 1"),
              (dict(ctrl=shared, params=ok, out={"qpos": torch.zeros((4, 2, 3, 4))}), "out\\['qpos'\\]"),
              (dict(ctrl=each, params=dict(geom_friction=fric, dof_damping=damp), out={"qvel": torch.zeros((4, 3, 3, 4))}), "out\\['qvel'\\]")]
-    for kw, msg in cases:
-        with pytest.raises(ValueError, match=msg):
-            p.param_rollouts(**kw)
+    cases.append((dict(ctrl=shared, params=ok, out={"qvel": np.zeros((4, 2, 3, 4), np.float32)}), "out\\['qvel'\\]"))     # (once an AttributeError)
+    refused(monkeypatch, p.param_rollouts, cases)
+    # a good call is the one library call, and its inputs stay in its own slot, not copied
+    rec = record(monkeypatch)
+    p.param_rollouts(each, dict(geom_friction=fric, dof_damping=damp), env_ids=[0, 1, 2, 3])
+    (sym, args), = rec.calls
+    assert sym == "rsr_physics_param_rollouts" and len(args) == 11 and args[3] == each.data_ptr()
+    assert all(any(t is x for x in p._held["param_rollouts"]) for t in (each, fric, damp))
 
 
 class _FakePhys:

@@ -1,14 +1,13 @@
 """Physics-level C ABI and Python surface (include/rsr_physics.h, rsr_mjx_amd/physics.py), host side only: what can be
 checked without a device.  The kernels themselves are covered by tests/test_physics_gpu.py."""
 import ctypes as C
-import os
 import re
 
-from conftest import ROOT
+from api_support import header
 
 
 def test_header_declares_the_physics_api():
-    h = open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+    h = header()
     assert '#include "rsr_mjx.h"' in h
     for sig in ("int rsr_physics_create(rsr_batch* b, rsr_physics** out);",
                 "void rsr_physics_destroy(rsr_physics* p);",
@@ -27,7 +26,7 @@ def test_header_declares_the_physics_api():
 def test_library_exports_and_argument_checks():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    h = open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+    h = header()
     assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", h)) == set(_lib.PHYS_SYMBOLS)
     for sym in _lib.PHYS_SYMBOLS:
         assert getattr(L, sym) is not None

@@ -2,17 +2,16 @@
 the exports, the argument checks that come before any device work, and the spec -> table conversion.  The kernels are covered
 by tests/test_physics_rollout_gpu.py."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from api_support import header
 
 
 def test_header_declares_rollout_and_sensors():
-    h = open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+    h = header()
     for sig in ("int rsr_physics_set_sensors(rsr_physics* p, const int32_t* table, int nsensor);",
                 "int rsr_physics_rollout(rsr_physics* p, const float* ctrl, int T, int nsteps, const rsr_rollout_out* out, void* hip_stream);"):
         assert sig in h, sig

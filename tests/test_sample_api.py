@@ -4,23 +4,15 @@ import ctypes as C
 import inspect
 import os
 import re
-import types
 
-import pytest
+from api_support import CSRC, HANDLE, ROOT, STREAM, body as _body, header, ints, record, refused, standin
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
 SIG = ("int rsr_physics_sample_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, "
        "int K, int T, int nsteps, const rsr_rollout_out* out, void* hip_stream);")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
-
-
 def test_header_declares_the_sample_api():
-    h = _header()
+    h = header()
     assert SIG in re.sub(r"\s+", " ", h)                          # (the declaration may break its line)
     doc = h[h.index("/* Sampled rollouts"):h.index("int rsr_physics_sample_rollouts(")]
     for word in ("[M, K, T, nu]", "[M, K, T, width]", "bit for bit", "qacc_warmstart", "position in env_ids", "untouched",
@@ -35,7 +27,7 @@ def test_header_declares_the_sample_api():
 def test_library_exports_and_null_handle():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     assert "rsr_physics_sample_rollouts" in _lib.PHYS_SYMBOLS
     fn = L.rsr_physics_sample_rollouts
     assert fn.argtypes is not None and len(fn.argtypes) == 9
@@ -45,11 +37,6 @@ def test_library_exports_and_null_handle():
     for table, k in ((None, 0), (ids, 2), (ids, 0)):
         assert fn(None, table, k, ctrl, 1, 1, 1, C.byref(o), None) == -1
         assert b"null handle" in L.rsr_last_error()
-
-
-def _body(src, name):
-    b = src[src.index(name + "("):]
-    return b[:b.index("\n}\n")]
 
 
 def test_refusals_come_before_device_work():
@@ -129,7 +116,7 @@ def test_nothing_outside_the_physics_layer_knows():
     assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     import torch
     from rsr_mjx_amd import physics
     from rsr_mjx_amd.physics import Physics
@@ -140,17 +127,8 @@ def test_physics_module_surface():
     assert sig.parameters["ctrl"].default is inspect.Parameter.empty
     assert "Physics.sample_rollouts(ctrl [M, K, T, nu])" in physics.__doc__ and "vmap(lax.scan(mjx.step))" in physics.__doc__
     assert "4 * M * K * T * w bytes" in Physics.sample_rollouts.__doc__
-    src = inspect.getsource(Physics.sample_rollouts)
-    assert 'self._call_envs("rsr_physics_sample_rollouts", "sample_rollouts", ' in src and "_lib.lib()" not in src
-    assert src.rindex("raise ValueError") < src.index("self._call_envs(")
-    assert "self._sample_ctrl_in = c" in src
-    assert "self._ids_in: Dict[str, Any] = {}" in inspect.getsource(Physics.__init__)
-    assert not re.search(r"self\._\w*ids_in = ", inspect.getsource(Physics))
-    # every bad input is refused before the C call (the stand-in has no handle to call with)
-    p = Physics.__new__(Physics)
-    p._h = None
-    p.num_envs, p.dims, p.qvel, p.device = 4, types.SimpleNamespace(nu=3, nq=5, nv=4, n_frames=2), torch.zeros((4, 4)), torch.device("cpu")
-    p.sensordata = torch.zeros((4, 0))                      # no sensors set
+    # every bad input is refused before the C call: the recording library sees none
+    p = standin(nq=5, nv=4)
     good = torch.zeros((4, 2, 3, 3), dtype=torch.float32)
     cases = [(dict(ctrl=torch.zeros((4, 3, 3))), "expects ctrl"),                         # 3-D
              (dict(ctrl=torch.zeros((4, 2, 3, 2))), "expects ctrl"),                      # wrong nu
@@ -163,7 +141,15 @@ def test_physics_module_surface():
              (dict(ctrl=good, fields=("qpos", "qacc")), "unknown"),
              (dict(ctrl=good, fields=("sensordata",)), "no sensors are set"),
              (dict(ctrl=good, nsteps=0), "nsteps must be >= 1"),
-             (dict(ctrl=good, out={"qpos": torch.zeros((4, 2, 3, 4))}), "out\\['qpos'\\]")]
-    for kw, msg in cases:
-        with pytest.raises(ValueError, match=msg):
-            p.sample_rollouts(**kw)
+             (dict(ctrl=good, out={"qpos": torch.zeros((4, 2, 3, 4))}), "out\\['qpos'\\]"),
+             (dict(ctrl=good, out={"qpos": torch.zeros((4, 2, 3, 5)).numpy()}), "out\\['qpos'\\]")]      # (once an AttributeError)
+    refused(monkeypatch, p.sample_rollouts, cases)
+    # a good call goes through the env-list convention, ctrl after the count, and its inputs stay in its own slot, not copied
+    rec = record(monkeypatch)
+    part = good[:2]
+    p.sample_rollouts(part, env_ids=[3, 1])
+    (sym, (h, ids, k, ctrl, K, T, nsteps, out, stream)), = rec.calls
+    assert (sym, h, k, ctrl, K, T, nsteps, stream) == ("rsr_physics_sample_rollouts", HANDLE, 2, part.data_ptr(), 2, 3, p.n_substeps, STREAM)
+    assert ints(ids, 2) == [3, 1] and p._held["sample_rollouts"][0] is part and p._held["sample_rollouts"][1].data_ptr() == ids
+    p.dynamics([0])                                                                    # another entry point's launch drops neither
+    assert p._held["sample_rollouts"][0] is part and p._held["sample_rollouts"][1].data_ptr() == ids

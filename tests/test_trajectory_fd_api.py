@@ -5,32 +5,16 @@ import ctypes as C
 import inspect
 import os
 import re
-import types
 
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
+from api_support import CSRC, ROOT, body as _body, header, ints, read as _read, record, refused, standin
 SIG = ("int rsr_physics_trajectory_fd(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, int T, int nsteps, "
        "float eps, int flags, const rsr_trajectory_fd_out* out, void* hip_stream);")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
-
-
-def _read(*parts):
-    return open(os.path.join(CSRC, *parts)).read()
-
-
-def _body(src, name):
-    b = src[src.index(name + "("):]
-    return b[:b.index("\n}\n")]
-
-
 def test_header_declares_the_call_and_the_struct():
-    h = _header()
+    h = header()
     flat = re.sub(r"\s+", " ", h)
     assert SIG in flat                                             # (the declaration may break its lines)
     assert "typedef struct rsr_trajectory_fd_out { float* columns; float* qpos; float* qvel; } rsr_trajectory_fd_out;" in flat
@@ -48,7 +32,7 @@ def test_header_declares_the_call_and_the_struct():
 def test_library_exports_and_null_handle():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     assert "rsr_physics_trajectory_fd" in _lib.PHYS_SYMBOLS
     fn = L.rsr_physics_trajectory_fd
     assert fn.argtypes is not None and len(fn.argtypes) == 10 and fn.argtypes[6] is C.c_float
@@ -146,7 +130,7 @@ def test_the_kernels_are_a_header_of_their_own():
         assert word in sec, word
 
 
-def test_physics_module_surface():
+def test_physics_module_surface(monkeypatch):
     import torch
     from rsr_mjx_amd import physics
     from rsr_mjx_amd.physics import Physics
@@ -159,21 +143,11 @@ def test_physics_module_surface():
     for word in ("[M, T, 2nv, 2nv]", "[M, T, 2nv, nu]", "[M, T, nsensordata, 2nv]", "[M, T, nsensordata, nu]", "[M, T+1, nq]", "[M, T+1, nv]",
                  "fd_A .. fd_D", "sample_rollouts", "must not overlap"):
         assert word in doc, word
-    src = inspect.getsource(Physics.trajectory_fd)
-    assert 'self._call_envs("rsr_physics_trajectory_fd", who, ' in src and "_lib.lib()" not in src
-    assert src.rindex("raise ValueError") < src.index("self._call_envs(")
-    assert "self._trajectory_in = c" in src
     # the sibling is as it was
     assert list(inspect.signature(Physics.transition_fd).parameters) == ["self", "env_ids", "nsteps", "eps", "centered", "keep_states"]
-    # every bad input is refused before the C call (the stand-in has no handle to call with)
-    p = Physics.__new__(Physics)
-    p._h = None
+    # every bad input is refused before the C call: the recording library sees none
     nu, nq, nv, nsd = 3, 5, 4, 2
-    dims = types.SimpleNamespace(nu=nu, nq=nq, nv=nv, n_frames=2, ngeom=6, nbody=3, env_kind=0)
-    p.num_envs, p.dims, p.qvel, p.device = 4, dims, torch.zeros((4, 4)), torch.device("cpu")
-    p.sensordata = torch.zeros((4, nsd))
-    p.env = types.SimpleNamespace(_stream=lambda: None)
-    p._ids_in = {}
+    p = standin(handle=None, nsensordata=nsd, nq=nq, nv=nv)
     z = lambda *s, **kw: torch.zeros(s, **kw)
     M, T, ncol, w = 4, 3, 2 * nv + nu, 2 * nv + nsd
     good = dict(ctrl=z(M, T, nu))
@@ -205,11 +179,16 @@ def test_physics_module_surface():
              (dict(good, out={"qvel": z(M, T + 1, nq)}), "out\\['qvel'\\]"),
              (dict(good, out={"A": z(M, T, 2 * nv, 2 * nv)}), "out has \\['A'\\]"),
              (dict(good, nominal=False, out={"qpos": z(M, T + 1, nq)}), "out has \\['qpos'\\]")]
-    for kw, msg in cases:
-        with pytest.raises(ValueError, match=msg):
-            p.trajectory_fd(**kw)
+    refused(monkeypatch, p.trajectory_fd, cases)
     # the good calls get as far as the C call: the stand-in has no handle, and the library refuses it
     for kw in (good, dict(good, centered=False, nominal=False), dict(ctrl=z(3, T, nu), env_ids=[1, 3, 1]), dict(good, nsteps=1, eps=1e-6),
                dict(good, out={"columns": z(M, T, ncol, w), "qpos": z(M, T + 1, nq), "qvel": z(M, T + 1, nv)})):
         with pytest.raises(RuntimeError, match="rsr_physics_trajectory_fd: null handle"):
             p.trajectory_fd(**kw)
+    # ... as the one library call in the env-list convention (repeats allowed), ctrl kept in the method's own slot, not copied
+    rec = record(monkeypatch)
+    c = z(3, T, nu)
+    p.trajectory_fd(c, env_ids=[1, 3, 1])
+    (sym, args), = rec.calls
+    assert sym == "rsr_physics_trajectory_fd" and len(args) == 10 and args[2:4] == (3, c.data_ptr()) and ints(args[1], 3) == [1, 3, 1]
+    assert p._held["trajectory_fd"][0] is c and p._held["trajectory_fd"][1].data_ptr() == args[1]

@@ -5,17 +5,13 @@ import inspect
 import os
 import re
 
-from conftest import ROOT
+import pytest
 
-CSRC = os.path.join(ROOT, "rsr_mjx_amd", "csrc")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "rsr_physics.h")).read()
+from api_support import CSRC, HANDLE, STREAM, header, ints, record, standin
 
 
 def test_header_declares_the_transition_api():
-    h = _header()
+    h = header()
     for sig in ("int rsr_physics_transition_fd(rsr_physics* p, const int32_t* env_ids, int count, int nsteps, float eps, int flags, void* hip_stream);",
                 "int rsr_physics_transition_view(rsr_physics* p, int field, void** dev_ptr, int64_t shape[2], int64_t stride[2]);"):
         assert sig in h, sig
@@ -36,7 +32,7 @@ def test_header_declares_the_transition_api():
 def test_library_exports_and_argument_checks():
     from rsr_mjx_amd import _lib
     L = _lib.lib()
-    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", _header())) == set(_lib.PHYS_SYMBOLS)
+    assert set(re.findall(r"\b(rsr_physics_[a-z_]+)\s*\(", header())) == set(_lib.PHYS_SYMBOLS)
     for sym in ("rsr_physics_transition_fd", "rsr_physics_transition_view"):
         assert sym in _lib.PHYS_SYMBOLS and getattr(L, sym).argtypes is not None
     assert L.rsr_physics_transition_fd.argtypes[4] is C.c_float
@@ -132,8 +128,8 @@ def test_the_kernel_lives_in_the_physics_layer():
     assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
 
 
-def test_physics_module_surface():
-    from rsr_mjx_amd import physics
+def test_physics_module_surface(monkeypatch):
+    from rsr_mjx_amd import _lib, physics
     from rsr_mjx_amd.physics import Physics
     sig = inspect.signature(Physics.transition_fd)
     assert list(sig.parameters) == ["self", "env_ids", "nsteps", "eps", "centered", "keep_states"]
@@ -141,18 +137,23 @@ def test_physics_module_surface():
     assert d == dict(env_ids=None, nsteps=None, eps=1e-3, centered=True, keep_states=False)
     for view in ("fd_A", "fd_B", "fd_C", "fd_D", "fd_x", "fd_y"):
         assert isinstance(getattr(Physics, view), property), view
-    src = inspect.getsource(Physics.transition_fd)
-    assert 'self._call_envs("rsr_physics_transition_fd", "transition_fd", env_ids, nsteps, eps, flags)' in src
-    assert "n_substeps" in src
-    # one helper carries the env-list calling convention of every entry point that takes one, and keeps each caller's ids alive
-    # in a slot of its own (two entry points' launches can be in flight at once)
-    for method, fn in (("dynamics", "rsr_physics_dynamics"), ("constraint_forces", "rsr_physics_constraint"),
-                       ("transition_fd", "rsr_physics_transition_fd"), ("set_state", "rsr_physics_forward_envs")):
-        text = inspect.getsource(getattr(Physics, method))
-        assert f'self._call_envs("{fn}", "{method}", ' in text and "data_ptr()" not in text and "_lib.lib()" not in text, method
-    helper = inspect.getsource(Physics._call_envs)
-    assert "self._ids(env_ids, who)" in helper and "ids32 = self._ids_in[who] = ids.to(torch.int32).contiguous()" in helper
-    assert helper.index("self._ids_in[who] = ") < helper.index("getattr(_lib.lib(), fn)(self._h, ptr, k, *args, self._stream())")
-    assert "self._ids_in: Dict[str, Any] = {}" in inspect.getsource(Physics.__init__)
-    assert not re.search(r"self\._\w*ids_in = ", inspect.getsource(Physics))      # no single shared attribute
+    # one calling convention for every entry point that takes an env list: (handle, ids, count, ..., stream) with the ids checked,
+    # int32 and in env_ids order, and kept alive in the method's own slot, which is written before the call is made (two entry
+    # points' launches can be in flight at once); nsteps defaults to n_substeps
+    p = standin()
+    rec = record(monkeypatch)
+    for method, fn, own in (("dynamics", "rsr_physics_dynamics", ()), ("constraint_forces", "rsr_physics_constraint", ()),
+                            ("transition_fd", "rsr_physics_transition_fd", (p.n_substeps, 1e-3, _lib.FD_CENTERED)),
+                            ("set_state", "rsr_physics_forward_envs", ())):
+        rec.peek[fn] = lambda *a, method=method: p._held[method]
+        getattr(p, method)(env_ids=[2, 0])
+        sym, (h, ids, k, *rest) = rec.calls.pop()
+        assert sym == fn and (h, k, tuple(rest)) == (HANDLE, 2, own + (STREAM,)) and ints(ids, 2) == [2, 0], method
+        assert [x.data_ptr() for x in rec.peeked.pop() if x is not None] == [ids], method          # held when the library is entered
+        for bad, msg in (([0, 4], "env_ids must lie in"), ([1, 1], "env_ids must not repeat")):
+            with pytest.raises(ValueError, match=f"{method}: {msg}"):
+                getattr(p, method)(env_ids=bad)
+        assert rec.calls == []
+    slots = [p._held[m][-1] for m in ("dynamics", "constraint_forces", "transition_fd", "set_state")]
+    assert len({t.data_ptr() for t in slots}) == 4 and all(t.tolist() == [2, 0] for t in slots)      # no single shared slot
     assert "Physics.transition_fd()" in physics.__doc__ and "mjd_transitionFD" in physics.__doc__
