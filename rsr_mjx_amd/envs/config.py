@@ -128,6 +128,7 @@ GO2_REWARDS = ("tracking_lin_vel", "tracking_ang_vel", "lin_vel_z", "ang_vel_xy"
                "feet_air_time", "all_feet_air", "symmetric_gait", "lr_symmetry", "fb_symmetry", "feet_off_ground_when_still")
 GO2_METRICS = tuple(f"reward/{k}" for k in GO2_REWARDS) + ("swing_peak",)
 GO2_INFO_FLOATS = 144
+GO2_DELAY_SLOTS = 4         # entries of each delay FIFO in the info block (action_buffer [4, 12], gyro / linvel / gravity_buffer [4, 3])
 GO2_DEFAULT_CONFIG = dict(
     ctrl_dt=0.02, sim_dt=0.004, episode_length=1000, Kp=60.0, Kd=3.0, action_repeat=1, action_scale=0.5, history_len=1,
     soft_joint_pos_limit_factor=0.95,
@@ -191,6 +192,13 @@ def go2_env_fields(m: CompiledModel, config: dict, episode_length: int = 0, auto
     ids = np.array([m.id("site", "imu")] + [m.id("site", f) for f in feet] + [m.id("geom", "floor")] +
                    [m.id("geom", f) for f in feet] + [m.id("body", "trunk")], dtype=np.int32)
     nz, rc, cc, pc, dc = (config[k] for k in ("noise_config", "reward_config", "command_config", "pert_config", "delay_config"))
+    for which in ("action", "imu"):
+        # the info block holds GO2_DELAY_SLOTS FIFO entries per buffer and a delay of `steps` uses steps + 1 of them: one more
+        # and the step kernel's FIFO write lands in the buffer behind
+        steps = dc[which]["steps"] if dc[which]["enable"] else 0
+        if int(steps) != steps or not 0 <= steps <= GO2_DELAY_SLOTS - 1:
+            raise ValueError(f"delay_config.{which}.steps = {steps!r}: the delay FIFOs hold {GO2_DELAY_SLOTS} entries, "
+                             f"so steps must be an integer in 0..{GO2_DELAY_SLOTS - 1}")
     f = np.array([config["ctrl_dt"], config["action_scale"], nz["level"], nz["scales"]["joint_pos"], nz["scales"]["joint_vel"],
                   nz["scales"]["gyro"], nz["scales"]["gravity"], nz["scales"]["linvel"], rc["tracking_sigma"], rc["max_foot_height"],
                   *cc["a"], *cc["b"], cc["change_interval"], *pc["kick_wait_times"], *pc["kick_durations"], *pc["velocity_kick"],
