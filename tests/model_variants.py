@@ -243,11 +243,8 @@ def apply(envdef, name):
 
 def envdef_of(kind, variant=None):
     """the env definition of a family (no batch, no device), with a variant applied"""
-    from rsr_mjx_amd.envs import airbot, go2
-    if kind in ("cube", "tshape"):
-        envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-    else:
-        envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind])
+    from rsr_mjx_amd.envs import families
+    envdef = families.envdef(kind)
     if variant is not None:
         assert kind in table_of(variant)[variant][0], (variant, kind)
         apply(envdef, variant)

@@ -1,4 +1,5 @@
-"""What the physics-layer GPU tests (tests/test_*_gpu.py on rsr_mjx_amd/physics.py) share: batches and states, bitwise comparison,
+"""What the physics-layer GPU tests (tests/test_*_gpu.py on rsr_mjx_amd/physics.py) share: batches and states (with the seeded default
+randomisation, the replica batch and the applied forces of the rollout tests; tools/rates_support.py takes them from here), bitwise comparison,
 the error rule, the CPU oracle's reference pass, the row-count exclusion, contact wrenches from the oracle's rows, and snapshots of
 everything a Physics handle owns.  Plain functions; torch is imported inside them, so collection works without a GPU.
 
@@ -12,8 +13,8 @@ import hashlib
 import numpy as np
 
 from rsr_mjx_amd import prng
+from rsr_mjx_amd.envs.families import FAMILIES
 
-FAMILIES = ["cube", "tshape", "go2flat", "go2rough", "footstand"]
 PIPE = ("qpos", "qvel", "ctrl", "qacc_warmstart", "time", "xpos", "site_xpos")
 GO2 = ("go2flat", "go2rough", "footstand")
 IMPLICIT = ("cube", "tshape")
@@ -38,17 +39,29 @@ def sensor_spec(kind, envdef):
 
 # ---- batches and states
 
+def action_scale(kind):
+    """the scale of the random actions that move a family's batch off its reset state"""
+    return 1.0 if kind in IMPLICIT else 0.5
+
+
+def default_dr(kind, envdef, n):
+    """the seeded randomisation of n envs that make(kind, n, True) applies, or None for the T-shape (the Airbot randomisation of
+    domain_randomize.py is the cube scene's)"""
+    from rsr_mjx_amd.envs import airbot, go2
+    if kind == "tshape":
+        return None
+    if kind == "cube":
+        return airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n))
+    return go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n))
+
+
 def make(kind, n, dr_on, variant=None):
     """(envdef, batched env, dr dict or None, action scale); no Episode / AutoReset wrappers, no Go2 kicks.  variant: a name of
     tests/model_variants.py, applied to envdef.sys.arrays before the batch (and its blob) is built."""
     from model_variants import envdef_of
-    from rsr_mjx_amd.envs import airbot, go2
     envdef = envdef_of(kind, variant)
-    if kind in ("cube", "tshape"):
-        dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n)) if dr_on else None
-        return envdef, envdef.batched(n, randomization=dr), dr, 1.0
-    dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n)) if dr_on else None
-    return envdef, envdef.batched(n, randomization=dr), dr, 0.5
+    dr = default_dr(kind, envdef, n) if dr_on else None
+    return envdef, envdef.batched(n, randomization=dr), dr, action_scale(kind)
 
 
 def pair(kind, n, seed=3, steps=3):
@@ -65,6 +78,28 @@ def pair(kind, n, seed=3, steps=3):
     B.record.copy_(A.record)
     torch.cuda.synchronize()
     return envdef, A, B, scale, rng
+
+
+def replica(kind, envdef, A, k, dr="default"):
+    """A.num_envs * k envs: env e * k + j holds env e's record row and per-env leaves.  dr: the randomisation A was built with
+    (the family's default_dr unless given; None: the replica gets no per-env leaves)"""
+    import torch
+    if dr == "default":
+        dr = default_dr(kind, envdef, A.num_envs)
+    R = envdef.batched(A.num_envs * k, randomization=None if dr is None else {f: np.repeat(np.asarray(v), k, 0) for f, v in dr.items()})
+    R.reset(prng.split(prng.PRNGKey(7), A.num_envs * k))
+    R.record.copy_(A.record.repeat_interleave(k, 0))
+    torch.cuda.synchronize()
+    return R
+
+
+def applied_forces(envdef, n, nv, rng):
+    """xfrc of the order of a third of each body's weight on every body, and a qfrc"""
+    m = np.maximum(envdef.sys.arrays["body_mass"], 0.05)[None, :, None]
+    x = rng.normal(size=(n, m.shape[1], 6))
+    x[:, :, :3] *= 9.81 * m * 0.3
+    x[:, :, 3:] *= 0.981 * m * 0.3
+    return x.astype(np.float32), (rng.normal(size=(n, nv)) * 0.5).astype(np.float32)
 
 
 _STATES = {}

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from physics_support import ALL, FAMILIES, assert_bitwise, assert_unchanged, handle_snapshot, pair, sensor_spec
+from tangent_ref import differentiate_pos, moved
 
 N, K, T = 16, 3, 3
 U = 2.0 ** -24
@@ -18,64 +19,6 @@ WITH_CTRL = ALL + ("ctrl",)
 BASE_LEAVES = ("geom_friction", "body_mass", "dof_damping", "dof_frictionloss")
 GO2_LEAVES = ("body_ipos", "qpos0", "dof_armature", "actuator_gainprm", "actuator_biasprm")
 GO2 = ("go2flat", "go2rough", "footstand")
-
-
-# ---- mj_differentiatePos / mj_integratePos in fp64 (the restatement of tests/test_transition_gpu.py)
-
-def _columns(A, nv):
-    """per qpos-tangent column k < nv: (kind, qpos address): 'add' at one address, or 'rot' about axis k' of the quaternion at it"""
-    cols = [None] * nv
-    for j in range(len(A["jnt_type"])):
-        jt, qa, da = int(A["jnt_type"][j]), int(A["jnt_qposadr"][j]), int(A["jnt_dofadr"][j])
-        if jt == 0:
-            for k in range(3):
-                cols[da + k] = ("add", qa + k, 0)
-                cols[da + 3 + k] = ("rot", qa + 3, k)
-        else:
-            assert jt in (2, 3)
-            cols[da] = ("add", qa, 0)
-    assert all(c is not None for c in cols)
-    return cols
-
-
-def _qmul(a, b):
-    w1, x1, y1, z1 = np.moveaxis(a, -1, 0)
-    w2, x2, y2, z2 = np.moveaxis(b, -1, 0)
-    return np.stack([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
-                     w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2], -1)
-
-
-def _differentiate_pos(A, nv, qp, qm):
-    """mj_differentiatePos with dt = 1, fp64: qp (-) qm on [n, nq] -> [n, nv]"""
-    qp, qm = np.asarray(qp, np.float64), np.asarray(qm, np.float64)
-    out = np.zeros((len(qp), nv))
-    for k, (kind, qa, ax) in enumerate(_columns(A, nv)):
-        if kind == "add":
-            out[:, k] = qp[:, qa] - qm[:, qa]
-        elif ax == 0:
-            conj = qm[:, qa:qa + 4] * np.array([1.0, -1.0, -1.0, -1.0])
-            dq = _qmul(conj, qp[:, qa:qa + 4])
-            sn = np.linalg.norm(dq[:, 1:], axis=1)
-            speed = 2.0 * np.arctan2(sn, dq[:, 0])
-            speed = np.where(speed > np.pi, speed - 2.0 * np.pi, speed)
-            out[:, k:k + 3] = dq[:, 1:] * np.where(sn > 0, speed / np.where(sn > 0, sn, 1.0), 0.0)[:, None]
-    return out
-
-
-def _moved(A, nv, qpos, d):
-    """qpos [n, nq] moved by d [n, nv] in the tangent space: joints and free-joint translations add, a free joint's quaternion is
-    multiplied on the right by the rotation vector's quaternion and renormalised"""
-    q = np.array(qpos, dtype=np.float64)
-    for k, (kind, qa, ax) in enumerate(_columns(A, nv)):
-        if kind == "add":
-            q[:, qa] += d[:, k]
-        elif ax == 0:
-            v = d[:, k:k + 3]
-            ang = np.linalg.norm(v, axis=1, keepdims=True)
-            r = np.concatenate([np.cos(0.5 * ang), np.sin(0.5 * ang) * v / np.maximum(ang, 1e-300)], 1)
-            p = _qmul(q[:, qa:qa + 4], r)
-            q[:, qa:qa + 4] = p / np.linalg.norm(p, axis=1, keepdims=True)
-    return q
 
 
 # ---- the shared inputs, computed once per family and left unchanged
@@ -102,7 +45,7 @@ def _base(kind):
     torch.cuda.synchronize()
     q0, v0 = pa.qpos.cpu().numpy().copy(), pa.qvel.cpu().numpy().copy()
     rep = lambda a: np.repeat(a[:, None], K * T, 1).reshape(N * K * T, -1)
-    qref = _moved(arr, nv, rep(q0), rng.normal(scale=0.05, size=(N * K * T, nv))).astype(np.float32).reshape(N, K, T, nq)
+    qref = moved(arr, nv, rep(q0), rng.normal(scale=0.05, size=(N * K * T, nv))).astype(np.float32).reshape(N, K, T, nq)
     vref = (rep(v0) + rng.normal(scale=0.1, size=(N * K * T, nv))).astype(np.float32).reshape(N, K, T, nv)
     t_ctrl = torch.as_tensor(ctrl, device=dev)
     before = handle_snapshot(pa)
@@ -126,7 +69,7 @@ def _dx(arr, nv, q0, v0, qpos, qvel, qref, vref):
     nq = q0.shape[1]
     qs = np.concatenate([np.repeat(q0[:, None, None], K, 1), qpos[:, :, :T - 1]], 2).astype(np.float64)
     vs = np.concatenate([np.repeat(v0[:, None, None], K, 1), qvel[:, :, :T - 1]], 2).astype(np.float64)
-    dq = _differentiate_pos(arr, nv, qs.reshape(-1, nq), qref.reshape(-1, nq)).reshape(N, K, T, nv)
+    dq = differentiate_pos(arr, nv, qs.reshape(-1, nq), qref.reshape(-1, nq)).reshape(N, K, T, nv)
     return np.concatenate([dq, vs - vref.astype(np.float64)], 3)
 
 

@@ -10,7 +10,8 @@ import functools
 import numpy as np
 import pytest
 
-from physics_support import ALL, FAMILIES, assert_bitwise, assert_unchanged, handle_snapshot, make, pair, sensor_spec
+from physics_support import (ALL, FAMILIES, applied_forces, assert_bitwise, assert_unchanged, default_dr, handle_snapshot, make, pair, replica,
+                             sensor_spec)
 from rsr_mjx_amd import prng
 
 N, K, T = 64, 5, 4              # K odd, no divisor of N; N * K = 320 workgroups and replica envs
@@ -21,25 +22,6 @@ GO2 = ("go2flat", "go2rough", "footstand")
 
 def _leaves_of(kind):
     return BASE_LEAVES + (GO2_LEAVES if kind in GO2 else ())
-
-
-def _dr(kind, envdef, n):
-    """the randomisation physics_support.pair gives its batches (same keys), or None"""
-    from rsr_mjx_amd.envs import airbot, go2
-    if kind == "tshape":
-        return None
-    if kind == "cube":
-        return airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n))
-    return go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n))
-
-
-def _forces(envdef, n, nv, rng):
-    """xfrc of the order of a third of each body's weight on every body, and a qfrc"""
-    m = np.maximum(envdef.sys.arrays["body_mass"], 0.05)[None, :, None]
-    x = rng.normal(size=(n, m.shape[1], 6))
-    x[:, :, :3] *= 9.81 * m * 0.3
-    x[:, :, 3:] *= 0.981 * m * 0.3
-    return x.astype(np.float32), (rng.normal(size=(n, nv)) * 0.5).astype(np.float32)
 
 
 def _base(kind, dr_on=True, applied=False):
@@ -55,7 +37,7 @@ def _base_once(kind, dr_on, applied):
     from rsr_mjx_amd.physics import Physics
     if dr_on:
         envdef, A, twin, scale, rng = pair(kind, N)                   # (DR on but for the T-shape, whose batch has none)
-        dr = _dr(kind, envdef, N)
+        dr = default_dr(kind, envdef, N)
     else:                                                             # pair's steps on batches built with no per-env leaves
         envdef, A, _, scale = make(kind, N, False)
         _, twin, _, _ = make(kind, N, False)
@@ -75,7 +57,7 @@ def _base_once(kind, dr_on, applied):
     ctrl = torch.as_tensor((lo + (hi - lo) * rng.uniform(size=(N, T, A.dims.nu))).astype(np.float32), device=A.device)
     forces = None
     if applied:                                                       # (drawn last: plain and applied share ctrl)
-        forces = _forces(envdef, N, A.dims.nv, rng)
+        forces = applied_forces(envdef, N, A.dims.nv, rng)
         pa.set_applied(*forces)
     return dict(kind=kind, envdef=envdef, A=A, twin=twin, pa=pa, scale=scale, spec=spec, dr=dr, own=own, ctrl=ctrl, forces=forces,
                 before=handle_snapshot(pa))
@@ -119,8 +101,7 @@ def _replica_once(kind, dr_on, applied):
     """N * K envs and their handle, built once per case; _ref gives them their rows and leaves"""
     from rsr_mjx_amd.physics import Physics
     c = _base(kind, dr_on, applied)
-    R = c["envdef"].batched(N * K, randomization=None)
-    R.reset(prng.split(prng.PRNGKey(7), N * K))
+    R = replica(kind, c["envdef"], c["A"], K, dr=None)                # (no per-env leaves here: _ref writes them at every use)
     pr = Physics(R, sensors=c["spec"])
     if applied:
         pr.set_applied(np.repeat(c["forces"][0], K, 0), np.repeat(c["forces"][1], K, 0))

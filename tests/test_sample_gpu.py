@@ -9,40 +9,9 @@ import functools
 import numpy as np
 import pytest
 
-from physics_support import ALL, FAMILIES, assert_bitwise, assert_unchanged, handle_snapshot, pair, sensor_spec
-from rsr_mjx_amd import prng
+from physics_support import ALL, FAMILIES, applied_forces, assert_bitwise, assert_unchanged, handle_snapshot, pair, replica, sensor_spec
 
 N, K, T = 64, 5, 4              # K odd, no divisor of N; N * K = 320 workgroups
-
-
-def _dr(kind, envdef, n):
-    """the randomisation _pair gives its batches (same keys), or None"""
-    from rsr_mjx_amd.envs import airbot, go2
-    if kind == "tshape":
-        return None
-    if kind == "cube":
-        return airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n))
-    return go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n))
-
-
-def _replica(kind, envdef, A, k):
-    """N * k envs: env e * k + j holds env e's record row and per-env leaves"""
-    import torch
-    dr = _dr(kind, envdef, A.num_envs)
-    R = envdef.batched(A.num_envs * k, randomization=None if dr is None else {f: np.repeat(np.asarray(v), k, 0) for f, v in dr.items()})
-    R.reset(prng.split(prng.PRNGKey(7), A.num_envs * k))
-    R.record.copy_(A.record.repeat_interleave(k, 0))
-    torch.cuda.synchronize()
-    return R
-
-
-def _forces(envdef, n, nv, rng):
-    """xfrc of the order of a third of each body's weight on every body, and a qfrc"""
-    m = np.maximum(envdef.sys.arrays["body_mass"], 0.05)[None, :, None]
-    x = rng.normal(size=(n, m.shape[1], 6))
-    x[:, :, :3] *= 9.81 * m * 0.3
-    x[:, :, 3:] *= 0.981 * m * 0.3
-    return x.astype(np.float32), (rng.normal(size=(n, nv)) * 0.5).astype(np.float32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -54,10 +23,10 @@ def _case(kind, applied=False):
     envdef, A, twin, scale, rng = pair(kind, N)
     spec = sensor_spec(kind, envdef)
     pa = Physics(A, sensors=spec)
-    R = _replica(kind, envdef, A, K)
+    R = replica(kind, envdef, A, K)
     pr = Physics(R, sensors=spec)
     if applied:
-        x, q = _forces(envdef, N, A.dims.nv, rng)
+        x, q = applied_forces(envdef, N, A.dims.nv, rng)
         pa.set_applied(x, q)
         pr.set_applied(np.repeat(x, K, 0), np.repeat(q, K, 0))
     rng_c = envdef.sys.arrays["actuator_ctrlrange"]

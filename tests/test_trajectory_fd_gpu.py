@@ -9,8 +9,8 @@ import functools
 import numpy as np
 import pytest
 
-from physics_support import (ALL_BUFFERS, FAMILIES, GO2, PIPE, assert_bitwise, assert_unchanged, handle_snapshot, handle_views, make,
-                             sensor_spec)
+from physics_support import (ALL_BUFFERS, FAMILIES, GO2, PIPE, applied_forces, assert_bitwise, assert_unchanged, handle_snapshot, handle_views,
+                             make, sensor_spec)
 from rsr_mjx_amd import prng
 
 N, T, EPS = 8, 3, 1e-3
@@ -21,15 +21,6 @@ SENTINEL = float("nan")
 CONFIGS = {kind: (kind, False, False, True, None) for kind in FAMILIES}
 CONFIGS.update({"cube-dr": ("cube", True, False, True, None), "go2flat-applied": ("go2flat", False, True, True, None),
                 "cube-forward": ("cube", False, False, False, None), "go2flat-nsteps1": ("go2flat", False, False, True, 1)})
-
-
-def _forces(envdef, n, nv, rng):
-    """xfrc of the order of a third of each body's weight on every body, and a qfrc"""
-    m = np.maximum(envdef.sys.arrays["body_mass"], 0.05)[None, :, None]
-    x = rng.normal(size=(n, m.shape[1], 6))
-    x[:, :, :3] *= 9.81 * m * 0.3
-    x[:, :, 3:] *= 0.981 * m * 0.3
-    return x.astype(np.float32), (rng.normal(size=(n, nv)) * 0.5).astype(np.float32)
 
 
 def _raw_call(pa, ids, ctrl, nsteps, flags, bufs):
@@ -79,7 +70,7 @@ def _case(name):
         A.step(None, np.clip(rng.normal(size=(N, A.dims.nu)) * scale, -1, 1).astype(np.float32))
     pa = Physics(A, sensors=sensor_spec(kind, envdef) if kind in GO2 else None)
     if applied:
-        pa.set_applied(*_forces(envdef, N, A.dims.nv, rng))
+        pa.set_applied(*applied_forces(envdef, N, A.dims.nv, rng))
     nsteps = pa.n_substeps if nsteps is None else nsteps
     d, nsd = A.dims, pa.nsensordata
     ncol, w = 2 * d.nv + d.nu, 2 * d.nv + nsd

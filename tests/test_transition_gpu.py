@@ -8,6 +8,7 @@ import pytest
 
 from physics_support import FAMILIES, PIPE, all_but, assert_unchanged, bits, free_states, handle_snapshot, handle_views, make, rel, rule
 from rsr_mjx_amd import prng
+from tangent_ref import columns, differentiate_pos, integrate_pos
 
 N = 64
 EPS = 1e-3
@@ -81,59 +82,6 @@ def _run(cfg):
     return out
 
 
-def _columns(A, nv):
-    """per qpos-tangent column k < nv: (kind, qpos address): 'add' at one address, or 'rot' about axis k' of the quaternion at it"""
-    cols = [None] * nv
-    for j in range(len(A["jnt_type"])):
-        jt, qa, da = int(A["jnt_type"][j]), int(A["jnt_qposadr"][j]), int(A["jnt_dofadr"][j])
-        if jt == 0:
-            for k in range(3):
-                cols[da + k] = ("add", qa + k, 0)
-                cols[da + 3 + k] = ("rot", qa + 3, k)
-        else:
-            assert jt in (2, 3)
-            cols[da] = ("add", qa, 0)
-    assert all(c is not None for c in cols)
-    return cols
-
-
-def _qmul(a, b):
-    w1, x1, y1, z1 = np.moveaxis(a, -1, 0)
-    w2, x2, y2, z2 = np.moveaxis(b, -1, 0)
-    return np.stack([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
-                     w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2], -1)
-
-
-def _integrate_pos(A, nv, qpos, k, dlt):
-    """mj_integratePos(qpos, dlt e_k) in fp64 on [n, nq]"""
-    q = np.array(qpos, dtype=np.float64)
-    kind, qa, ax = _columns(A, nv)[k]
-    if kind == "add":
-        q[:, qa] += dlt
-    else:
-        r = np.zeros(4); r[0] = np.cos(0.5 * dlt); r[1 + ax] = np.sin(0.5 * dlt)
-        p = _qmul(q[:, qa:qa + 4], r[None])
-        q[:, qa:qa + 4] = p / np.linalg.norm(p, axis=1, keepdims=True)
-    return q
-
-
-def _differentiate_pos(A, nv, qp, qm):
-    """mj_differentiatePos with dt = 1, fp64: qp (-) qm on [n, nq] -> [n, nv]"""
-    qp, qm = np.asarray(qp, np.float64), np.asarray(qm, np.float64)
-    out = np.zeros((len(qp), nv))
-    for k, (kind, qa, ax) in enumerate(_columns(A, nv)):
-        if kind == "add":
-            out[:, k] = qp[:, qa] - qm[:, qa]
-        elif ax == 0:
-            conj = qm[:, qa:qa + 4] * np.array([1.0, -1.0, -1.0, -1.0])
-            dq = _qmul(conj, qp[:, qa:qa + 4])
-            sn = np.linalg.norm(dq[:, 1:], axis=1)
-            speed = 2.0 * np.arctan2(sn, dq[:, 0])
-            speed = np.where(speed > np.pi, speed - 2.0 * np.pi, speed)
-            out[:, k:k + 3] = dq[:, 1:] * np.where(sn > 0, speed / np.where(sn > 0, sn, 1.0), 0.0)[:, None]
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", CONFIGS, ids=_ID)
 def test_the_runs_are_the_steppers_bit_for_bit(cfg):
@@ -158,7 +106,7 @@ def test_the_perturbations_are_the_tangent_space_ones(cfg):
     r = _run(cfg)
     nq, nv, nu, ncol, _ = r["dims"]
     rec, x = r["rec"], r["x"]
-    cols = _columns(r["A"], nv)
+    cols = columns(r["A"], nv)
     nrot = 0
     for c in range(ncol):
         for sg, dlt in ((0, np.float32(EPS)), (1, np.float32(-EPS))):
@@ -167,7 +115,7 @@ def test_the_perturbations_are_the_tangent_space_ones(cfg):
             if c < nv and cols[c][0] == "rot":
                 qa = cols[c][1]
                 own[qa:qa + 4] = True
-                ref = _integrate_pos(r["A"], nv, rec[:, :nq], c, float(dlt))[:, qa:qa + 4]
+                ref = integrate_pos(r["A"], nv, rec[:, :nq], c, float(dlt))[:, qa:qa + 4]
                 got = x[:, c, sg, qa:qa + 4].astype(np.float64)
                 assert np.abs(got - ref).max() <= 4 * U, (c, sg, np.abs(got - ref).max())
                 assert np.abs(np.linalg.norm(got, axis=1) - 1.0).max() <= 4 * U
@@ -189,7 +137,7 @@ def _fd_ref(r):
     y = r["y"].astype(np.float64)
     ref = np.zeros((N, ncol, 2 * nv + nsd))
     for c in range(ncol):
-        ref[:, c, :nv] = _differentiate_pos(r["A"], nv, y[:, c, 0, :nq], y[:, c, 1, :nq]) / h
+        ref[:, c, :nv] = differentiate_pos(r["A"], nv, y[:, c, 0, :nq], y[:, c, 1, :nq]) / h
         ref[:, c, nv:2 * nv] = (y[:, c, 0, nq:] - y[:, c, 1, nq:]) / h
         ref[:, c, 2 * nv:] = (r["sd"][:, c, 0] - r["sd"][:, c, 1]) / h
     return ref, h
@@ -252,7 +200,7 @@ def test_against_the_oracle_at_the_same_eps(oracle_mod, kind):
             for dlt in (EPS, -EPS):
                 q, v, u = q0.copy(), v0.copy(), u0.copy()
                 if c < nv:
-                    q = _integrate_pos(A, nv, q, c, dlt)
+                    q = integrate_pos(A, nv, q, c, dlt)
                 elif c < 2 * nv:
                     v[:, c - nv] += dlt
                 else:
@@ -262,7 +210,7 @@ def test_against_the_oracle_at_the_same_eps(oracle_mod, kind):
                     o.forward(q[e], v[e], u[e], warm[e], step=True)
                     yq[e], yv[e] = o.get("qpos"), o.get("qvel")
                 ends.append((yq, yv))
-            J[:, :nv, c] = _differentiate_pos(A, nv, ends[0][0], ends[1][0]) / (2 * EPS)
+            J[:, :nv, c] = differentiate_pos(A, nv, ends[0][0], ends[1][0]) / (2 * EPS)
             J[:, nv:, c] = (ends[0][1] - ends[1][1]) / (2 * EPS)
         ref[prec] = J
     print(kind, "fd [A B]: max |entry| %.3e, hip to the f32 oracle: max rel %.2e" % (np.abs(ref["f64"]).max(), rel(hip, ref["f32"]).max()))

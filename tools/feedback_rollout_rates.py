@@ -10,13 +10,10 @@ Usage: python tools/feedback_rollout_rates.py [--sizes 8x8,128x8] [--T 32] [--re
 from __future__ import annotations
 
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rates_support as R
 
 
 def main() -> None:
@@ -30,30 +27,13 @@ def main() -> None:
     args = ap.parse_args()
     import torch
     import bench
-    from rsr_mjx_amd import prng
-    from rsr_mjx_amd.envs import airbot, go2
     from rsr_mjx_amd.physics import Physics
-    T = args.T
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        open(args.out, "w").close()
+    T, write = args.T, R.row_writer(args.out)
     for m, k in (tuple(int(v) for v in s.split("x")) for s in args.sizes.split(",")):
         for kind in args.families.split(","):
-            if kind in ("cube", "tshape"):
-                envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-                dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), m)) if kind == "cube" else None
-                spec, scale = [("pos", "framepos", "endpoint"), ("linvel", "framelinvel", "endpoint")], 1.0
-            else:
-                envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain",
-                                   "footstand": "Go2Footstand"}[kind])
-                dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), m))
-                spec, scale = envdef.sensors, 0.5
-            env = envdef.batched(m, randomization=dr)
-            env.reset(prng.split(prng.PRNGKey(0), m))
-            rng = np.random.default_rng(0)
-            for _ in range(3):
-                env.step(None, np.clip(rng.normal(size=(m, env.dims.nu)) * scale, -1, 1).astype(np.float32))
-            phys = Physics(env, sensors=spec)
+            b = R.batch(kind, m)
+            envdef, env, rng = b.envdef, b.env, b.rng
+            phys = Physics(env, sensors=b.spec)
             nf, nsd = phys.n_substeps, phys.nsensordata
             nq, nv, nu = int(env.dims.nq), int(env.dims.nv), int(env.dims.nu)
             # one noisy sequence per sample around the ctrl the env steps left
@@ -68,26 +48,18 @@ def main() -> None:
             out_a = {"sensordata": torch.empty((m, k, T, nsd), device=env.device)}
             out_b = {"sensordata": torch.empty((m, k, T, nsd), device=env.device)}
             torch.cuda.synchronize()
-            t_a, t_b = [], []
-            for r in range(args.reps + 1):                        # (the first round warms both arms up)
-                env.timing_begin(); phys.param_rollouts(each, {}, nf, fields=("sensordata",), out=out_a); ms, _ = env.timing_end()
-                if r: t_a.append(ms)
-                torch.cuda.synchronize()
-                env.timing_begin(); phys.feedback_rollouts(each, gain, qref, vref, nsteps=nf, fields=("sensordata",), clamp=True, out=out_b); ms, _ = env.timing_end()
-                if r: t_b.append(ms)
-                torch.cuda.synchronize()
-            med = lambda x: float(np.median(x))
+            t_a, t_b = R.alternate([
+                R.Arm(lambda: phys.param_rollouts(each, {}, nf, fields=("sensordata",), out=out_a), env),
+                R.Arm(lambda: phys.feedback_rollouts(each, gain, qref, vref, nsteps=nf, fields=("sensordata",), clamp=True, out=out_b), env)], args.reps)
+            med = R.median
             row = dict(family=kind, M=m, K=k, T=T, nsteps=nf, nsensordata=nsd, gain=args.gain, clamp=True, csrc_sha16=bench.csrc_sha16(),
                        param_ms=med(t_a), feedback_ms=med(t_b), feedback_over_param=med(t_b) / med(t_a),
                        feedback_env_steps_per_s=m * k * T / (med(t_b) * 1e-3),
-                       spread=[min(t_a), max(t_a), min(t_b), max(t_b)], reps=args.reps,
+                       spread=R.spread(t_a, t_b), reps=args.reps,
                        differ=not bool(torch.equal(out_a["sensordata"], out_b["sensordata"])),
                        finite=bool(torch.isfinite(out_b["sensordata"]).all()))
-            print(json.dumps(row), flush=True)
-            if args.out:
-                with open(args.out, "a") as fh:
-                    fh.write(json.dumps(row) + "\n")
-            del phys, env
+            write(row)
+            del phys, env, b
             torch.cuda.synchronize()
 
 

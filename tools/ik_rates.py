@@ -10,15 +10,10 @@ Usage: python tools/ik_rates.py [--sizes 64,1024] [--iters 20] [--reps 7] [--inn
 from __future__ import annotations
 
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import rates_support as R
 
 TASKS = {"cube": ["endpoint"], "tshape": ["endpoint"], "go2flat": ["FR", "FL", "RR", "RL"]}
 
@@ -56,20 +51,12 @@ def main() -> None:
     import torch
     import bench
     import ik_ref
-    from rsr_mjx_amd import prng
-    from rsr_mjx_amd.envs import airbot, go2
     from rsr_mjx_amd.physics import Physics
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        open(args.out, "w").close()
+    write = R.row_writer(args.out)
     for m in (int(v) for v in args.sizes.split(",")):
         for kind in args.families.split(","):
-            if kind in ("cube", "tshape"):
-                envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-            else:
-                envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind])
-            env = envdef.batched(m)
-            env.reset(prng.split(prng.PRNGKey(0), m))
+            b = R.batch(kind, m, steps=0, dr=False)
+            envdef, env = b.envdef, b.env
             phys = Physics(env)
             A = envdef.sys.arrays
             sites = [int(envdef.sys.id("site", n)) for n in TASKS[kind]]
@@ -89,32 +76,21 @@ def main() -> None:
             kw = dict(sites=sites, target_pos=target, dofs=dadr.tolist(), qpos0=start, damping=lam, iters=args.iters, tol_pos=0.0, tol_rot=0.0,
                       max_step=args.max_step, limits=True, out=out)
             torch.cuda.synchronize()
-            t_a, t_b = [], []
-            for r in range(args.reps + 1):                        # (the first round warms both arms up)
-                env.timing_begin()
-                for _ in range(args.inner):
-                    phys.ik(**kw)
-                ms, _ = env.timing_end()
-                if r: t_a.append(ms / args.inner)
-                torch.cuda.synchronize()
-                env.timing_begin()
-                q_b = torch_loop(phys, start, target, mask, qadr, dadr, lo, hi, args.damping, args.iters, args.max_step)
-                ms, _ = env.timing_end()
-                if r: t_b.append(ms)
-                torch.cuda.synchronize()
-            med = lambda x: float(np.median(x))
+            loop = {}
+
+            def torch_arm():
+                loop["q"] = torch_loop(phys, start, target, mask, qadr, dadr, lo, hi, args.damping, args.iters, args.max_step)
+            t_a, t_b = R.alternate([R.Arm(lambda: phys.ik(**kw), env, args.inner), R.Arm(torch_arm, env)], args.reps)
+            med, q_b = R.median, loop["q"]
             row = dict(family=kind, M=m, iters=args.iters, nsite=len(sites), ndof=len(js), damping=args.damping, max_step=args.max_step,
                        csrc_sha16=bench.csrc_sha16(), ik_ms=med(t_a), torch_loop_ms=med(t_b), torch_loop_over_ik=med(t_b) / med(t_a),
                        problems_per_s=m / (med(t_a) * 1e-3), iterations_per_s=m * args.iters / (med(t_a) * 1e-3),
-                       spread=[min(t_a), max(t_a), min(t_b), max(t_b)], reps=args.reps, inner=args.inner,
+                       spread=R.spread(t_a, t_b), reps=args.reps, inner=args.inner,
                        qpos_max_abs_diff=float((out["qpos"][:, qadr] - q_b[:, qadr]).abs().max()),
                        perr_max=float(out["err"][:, 0].max()), perr_median=float(out["err"][:, 0].median()),
                        ran_all_iterations=float((out["info"][:, 0] == args.iters).float().mean()), finite=bool(torch.isfinite(out["qpos"]).all()))
-            print(json.dumps(row), flush=True)
-            if args.out:
-                with open(args.out, "a") as fh:
-                    fh.write(json.dumps(row) + "\n")
-            del phys, env
+            write(row)
+            del phys, env, b
             torch.cuda.synchronize()
 
 

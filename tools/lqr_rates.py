@@ -9,15 +9,8 @@ Usage: python tools/lqr_rates.py [--sizes 64,1024] [--T 50] [--reps 7] [--inner 
 from __future__ import annotations
 
 import argparse
-import json
-import os
-import sys
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import rates_support as R
 
 
 def torch_backward(col, lx, lu, lxx, luu, lux, mu, nx):
@@ -63,21 +56,12 @@ def main() -> None:
     import torch
     import bench
     import lqr_ref
-    from rsr_mjx_amd import prng
-    from rsr_mjx_amd.envs import airbot, go2
     from rsr_mjx_amd.physics import Physics
-    T = args.T
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        open(args.out, "w").close()
+    T, write = args.T, R.row_writer(args.out)
     for m in (int(v) for v in args.sizes.split(",")):
         for kind in args.families.split(","):
-            if kind in ("cube", "tshape"):
-                envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-            else:
-                envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind])
-            env = envdef.batched(4)
-            env.reset(prng.split(prng.PRNGKey(0), 4))
+            b = R.batch(kind, 4, steps=0, dr=False)
+            env = b.env
             phys = Physics(env)
             nx, nu = 2 * int(env.dims.nv), int(env.dims.nu)
             inp = lqr_ref.inputs(m, T, nx, nu, seed=0)
@@ -88,33 +72,24 @@ def main() -> None:
             out = dict(gain=torch.empty((m, T, nu, nx), device=env.device), k=torch.empty((m, T, nu), device=env.device),
                        dV=torch.empty((m, 2), device=env.device), status=torch.empty((m,), device=env.device))
             torch.cuda.synchronize()
-            t_a, t_b = [], []
-            for r in range(args.reps + 1):                        # (the first round warms both arms up)
-                env.timing_begin()
-                for _ in range(args.inner):
-                    phys.lqr_backward(col, lx, lu, lxx, luu, lux=lux, mu=mu, out=out)
-                ms, _ = env.timing_end()
-                if r: t_a.append(ms / args.inner)
-                torch.cuda.synchronize()
-                env.timing_begin()
-                g_b, k_b, dv_b = torch_backward(col, lx, lu, lxx, luu, lux, mu, nx)
-                ms, _ = env.timing_end()
-                if r: t_b.append(ms)
-                torch.cuda.synchronize()
-            med = lambda x: float(np.median(x))
+            loop = {}
+
+            def torch_arm():
+                loop["gain"], loop["k"], loop["dV"] = torch_backward(col, lx, lu, lxx, luu, lux, mu, nx)
+            t_a, t_b = R.alternate([R.Arm(lambda: phys.lqr_backward(col, lx, lu, lxx, luu, lux=lux, mu=mu, out=out), env, args.inner),
+                                    R.Arm(torch_arm, env)], args.reps)
+            med = R.median
+            g_b, k_b, dv_b = loop["gain"], loop["k"], loop["dV"]
             scale = float(g_b.abs().max())
             row = dict(family=kind, M=m, T=T, nx=nx, nu=nu, mu=args.mu, csrc_sha16=bench.csrc_sha16(),
                        lqr_backward_ms=med(t_a), torch_loop_ms=med(t_b), torch_loop_over_lqr_backward=med(t_b) / med(t_a),
                        problems_per_s=m / (med(t_a) * 1e-3), steps_per_s=m * T / (med(t_a) * 1e-3),
-                       spread=[min(t_a), max(t_a), min(t_b), max(t_b)], reps=args.reps, inner=args.inner,
+                       spread=R.spread(t_a, t_b), reps=args.reps, inner=args.inner,
                        gain_max_rel_diff=float((out["gain"] - g_b).abs().max()) / scale,
                        k_max_abs_diff=float((out["k"] - k_b).abs().max()), dV_max_rel_diff=float(((out["dV"] - dv_b).abs() / dv_b.abs().clamp(min=1)).max()),
                        all_succeeded=bool((out["status"] == -1).all()), finite=bool(torch.isfinite(out["gain"]).all()))
-            print(json.dumps(row), flush=True)
-            if args.out:
-                with open(args.out, "a") as fh:
-                    fh.write(json.dumps(row) + "\n")
-            del phys, env
+            write(row)
+            del phys, env, b
             torch.cuda.synchronize()
 
 

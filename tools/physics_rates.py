@@ -20,26 +20,21 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rates_support as R
+
+BATCH = dict(episode_length=1000, auto_reset=True)
 
 
-def _make_env(kind, n):
-    """(envdef, env batch with the family's randomisation, action scale)"""
-    from rsr_mjx_amd import prng
-    from rsr_mjx_amd.envs import airbot, go2
-    if kind in ("cube", "tshape"):
-        envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-        dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n)) if kind == "cube" else None
-        scale = 1.0
-    else:
-        envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind])
-        dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n))
-        scale = 0.5
-    return envdef, envdef.batched(n, episode_length=1000, auto_reset=True, randomization=dr), scale
+def per_call(env, fn, args, per=1):
+    """ms per call of one arm alone, fn(i) with i the call's index in its phase: args.warmup untimed calls, then one window of
+    args.steps (forward, dynamics and the like do not count as env launches: the window is divided by the calls)"""
+    for i in range(args.warmup):
+        fn(i)
+    calls = iter(range(args.steps))
+    return R.alternate([R.Arm(lambda: fn(next(calls)), env, args.steps)], 1, warmup=0)[0][0] / per
 
 
 def transition_rates(args) -> None:
@@ -47,54 +42,37 @@ def transition_rates(args) -> None:
     from the states 10 env steps reach; blocks alternate (A B A B A B) and the medians are reported."""
     import torch
     from bench import csrc_sha16
-    from rsr_mjx_amd import prng
+    from physics_support import PIPE as pipe
     from rsr_mjx_amd.physics import Physics
-    pipe = ("qpos", "qvel", "ctrl", "qacc_warmstart", "time", "xpos", "site_xpos")
     for n in [int(v) for v in args.transition_envs.split(",")]:
-        rows = []
+        write = R.row_writer(os.path.join(args.out_dir, f"transition_rates_{n}.jsonl"))
         for kind in args.families.split(","):
-            envdef, env, scale = _make_env(kind, n)
-            env.reset(prng.split(prng.PRNGKey(0), n))
-            rng = np.random.default_rng(0)
-            for _ in range(10):
-                env.step(None, np.clip(rng.normal(size=(n, env.dims.nu)) * scale, -1, 1).astype(np.float32))
+            b = R.batch(kind, n, steps=10, **BATCH)
+            env = b.env
             phys = Physics(env)
             ncol = 2 * env.dims.nv + env.dims.nu
             saved = {k: env.view(k).clone() for k in pipe}
             ctrl = saved["ctrl"].clone()
 
+            def restore():
+                for k in pipe:
+                    env.view(k).copy_(saved[k])
+
             def by_steps():
                 for _ in range(2 * ncol):
-                    for k in pipe:
-                        env.view(k).copy_(saved[k])
+                    restore()
                     phys.step(ctrl)
-
-            def block(fn, reps):
-                env.timing_begin()
-                for _ in range(reps):
-                    fn()
-                return env.timing_end()[0] / reps
             phys.transition_fd()
             by_steps()
-            fd, st = [], []
-            for _ in range(3):
-                fd.append(block(phys.transition_fd, args.transition_reps))
-                st.append(block(by_steps, 1))
-            for k in pipe:
-                env.view(k).copy_(saved[k])
+            fd, st = R.alternate([R.Arm(phys.transition_fd, env, args.transition_reps), R.Arm(by_steps, env)], 3, warmup=0)
+            restore()
             torch.cuda.synchronize()
-            row = dict(family=kind, num_envs=n, n_frames=int(env.dims.n_frames), ncol=ncol, eps=1e-3, centered=True,
-                       transition_fd_ms=float(np.median(fd)), step_launches=2 * ncol, steps_ms=float(np.median(st)),
-                       transition_fd_ms_blocks=fd, steps_ms_blocks=st, steps_over_transition_fd=float(np.median(st) / np.median(fd)),
-                       finite=bool(torch.isfinite(phys.fd_A).all() and torch.isfinite(phys.fd_B).all()), csrc_sha16=csrc_sha16())
-            print(json.dumps(row), flush=True)
-            rows.append(row)
-            del phys, env, saved
+            write(dict(family=kind, num_envs=n, n_frames=int(env.dims.n_frames), ncol=ncol, eps=1e-3, centered=True,
+                       transition_fd_ms=R.median(fd), step_launches=2 * ncol, steps_ms=R.median(st),
+                       transition_fd_ms_blocks=fd, steps_ms_blocks=st, steps_over_transition_fd=R.median(st) / R.median(fd),
+                       finite=bool(torch.isfinite(phys.fd_A).all() and torch.isfinite(phys.fd_B).all()), csrc_sha16=csrc_sha16()))
+            del phys, env, saved, b
             torch.cuda.synchronize()
-        os.makedirs(args.out_dir, exist_ok=True)
-        with open(os.path.join(args.out_dir, f"transition_rates_{n}.jsonl"), "w") as fh:
-            for row in rows:
-                fh.write(json.dumps(row) + "\n")
 
 
 def inverse_rates(args) -> None:
@@ -102,46 +80,29 @@ def inverse_rates(args) -> None:
     states 10 env steps reach"""
     import torch
     from bench import csrc_sha16
-    from rsr_mjx_amd import prng
     from rsr_mjx_amd.physics import Physics
     for n in [int(v) for v in args.inverse_envs.split(",")]:
-        rows = []
+        write = R.row_writer(os.path.join(args.out_dir, f"inverse_rates_{n}.jsonl"))
         for kind in args.families.split(","):
-            envdef, env, scale = _make_env(kind, n)
-            env.reset(prng.split(prng.PRNGKey(0), n))
-            rng = np.random.default_rng(0)
-            for _ in range(10):
-                env.step(None, np.clip(rng.normal(size=(n, env.dims.nu)) * scale, -1, 1).astype(np.float32))
+            b = R.batch(kind, n, steps=10, **BATCH)
+            env = b.env
             phys = Physics(env)
             phys.forward()
             qacc = phys.qacc.clone().contiguous()
             phys.set_jac_sites([])
-
-            def per_launch(fn):
-                for _ in range(args.warmup):
-                    fn()
-                env.timing_begin()
-                for _ in range(args.steps):
-                    fn()
-                return env.timing_end()[0] / args.steps
             row = dict(family=kind, num_envs=n, launches=args.steps, warmup=args.warmup)
-            row["inverse_ms"] = per_launch(lambda: phys.inverse(qacc))
-            row["inverse_discrete_ms"] = per_launch(lambda: phys.inverse(qacc, discrete=True))
-            row["constraint_ms"] = per_launch(phys.constraint_forces)
-            row["dynamics_ms"] = per_launch(phys.dynamics)
+            row["inverse_ms"] = per_call(env, lambda i: phys.inverse(qacc), args)
+            row["inverse_discrete_ms"] = per_call(env, lambda i: phys.inverse(qacc, discrete=True), args)
+            row["constraint_ms"] = per_call(env, lambda i: phys.constraint_forces(), args)
+            row["dynamics_ms"] = per_call(env, lambda i: phys.dynamics(), args)
             row["inverse_over_constraint"] = row["inverse_ms"] / row["constraint_ms"]
             row["inverse_over_dynamics"] = row["inverse_ms"] / row["dynamics_ms"]
             row["ordered"] = bool(row["dynamics_ms"] < row["inverse_ms"] < row["constraint_ms"])
             row["finite"] = bool(torch.isfinite(phys.qfrc_inverse).all())
             row["csrc_sha16"] = csrc_sha16()
-            print(json.dumps(row), flush=True)
-            rows.append(row)
-            del phys, env
+            write(row)
+            del phys, env, b
             torch.cuda.synchronize()
-        os.makedirs(args.out_dir, exist_ok=True)
-        with open(os.path.join(args.out_dir, f"inverse_rates_{n}.jsonl"), "w") as fh:
-            for row in rows:
-                fh.write(json.dumps(row) + "\n")
 
 
 def main() -> None:
@@ -160,7 +121,7 @@ def main() -> None:
     ap.add_argument("--transition-reps", type=int, default=5)
     ap.add_argument("--inverse", action="store_true")
     ap.add_argument("--inverse-envs", default="1024,8192")
-    ap.add_argument("--out-dir", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles"))
+    ap.add_argument("--out-dir", default=os.path.join(R.ROOT, "profiles"))
     args = ap.parse_args()
     if args.transition:
         transition_rates(args)
@@ -169,112 +130,66 @@ def main() -> None:
         inverse_rates(args)
         return
     import torch
-    from rsr_mjx_amd import prng
-    from rsr_mjx_amd.envs import airbot, go2
+    from bench import csrc_sha16
+    from physics_support import IMPLICIT
     from rsr_mjx_amd.physics import Physics
     n = args.envs
     rows = []
     for kind in args.families.split(","):
-        if kind in ("cube", "tshape"):
-            envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-            dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n)) if kind == "cube" else None
-            scale = 1.0
-        else:
-            envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain", "footstand": "Go2Footstand"}[kind])
-            dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n))
-            scale = 0.5
-        env = envdef.batched(n, episode_length=1000, auto_reset=True, randomization=dr)
-        env.reset(prng.split(prng.PRNGKey(0), n))
-        rng = np.random.default_rng(0)
-        acts = [torch.as_tensor(np.clip(rng.normal(size=(n, env.dims.nu)) * scale, -1, 1).astype(np.float32), device=env.device)
+        b = R.batch(kind, n, steps=0, **BATCH)
+        envdef, env, rng = b.envdef, b.env, b.rng
+        acts = [torch.as_tensor(np.clip(rng.normal(size=(n, env.dims.nu)) * b.scale, -1, 1).astype(np.float32), device=env.device)
                 for _ in range(8)]
         # fused env step
-        for i in range(args.warmup):
-            env.step(None, acts[i % 8])
-        env.timing_begin()
-        for i in range(args.steps):
-            env.step(None, acts[i % 8])
-        ms_env, launches = env.timing_end()
-        ms_env /= launches
+        ms_env = per_call(env, lambda i: env.step(None, acts[i % 8]), args)
         # physics-only step of n_frames substeps from the states the rollout reached, under the ctrl the env step last wrote
         phys = Physics(env)
         ctrl = env.view("ctrl").clone()
-        for _ in range(args.warmup):
-            phys.step(ctrl)
-        env.timing_begin()
-        for _ in range(args.steps):
-            phys.step(ctrl)
-        ms_phys, launches = env.timing_end()
-        ms_phys /= launches
+        ms_phys = per_call(env, lambda i: phys.step(ctrl), args)
         row = dict(family=kind, num_envs=n, n_frames=int(env.dims.n_frames), env_step_ms=ms_env, physics_step_ms=ms_phys,
                    env_steps_per_s=n / (ms_env * 1e-3), physics_env_steps_per_s=n / (ms_phys * 1e-3),
                    physics_over_env=ms_phys / ms_env)
         if args.applied:
-            def timed(fn, per):
-                for _ in range(args.warmup):
-                    fn()
-                env.timing_begin()
-                for _ in range(args.steps):
-                    fn()
-                ms, launches = env.timing_end()
-                return ms / launches / per
             T = args.rollout_T
             cr = ctrl[:, None, :].expand(n, T, env.dims.nu).contiguous()
-            row["rollout_step_ms"] = timed(lambda: phys.rollout(cr, fields=("qpos", "qvel")), T)
+            rollout = lambda i: phys.rollout(cr, fields=("qpos", "qvel"))
+            row["rollout_step_ms"] = per_call(env, rollout, args, T)
             # small forces (2 % of each body's weight, a matching torque, 0.05 on every dof): the state stays near the plain one
             mass = torch.as_tensor(envdef.sys.arrays["body_mass"], dtype=torch.float32, device=env.device)
             g = torch.Generator(device="cpu").manual_seed(0)
             x = torch.randn((n, env.dims.nbody, 6), generator=g).to(env.device) * 0.02 * 9.81 * mass[None, :, None].clamp(min=0.05)
             q = torch.randn((n, env.dims.nv), generator=g).to(env.device) * 0.05
             phys.set_applied(x, q)
-            row["applied_step_ms"] = timed(lambda: phys.step(ctrl), 1)
-            row["applied_rollout_step_ms"] = timed(lambda: phys.rollout(cr, fields=("qpos", "qvel")), T)
+            row["applied_step_ms"] = per_call(env, lambda i: phys.step(ctrl), args)
+            row["applied_rollout_step_ms"] = per_call(env, rollout, args, T)
             row["applied_over_plain_step"] = row["applied_step_ms"] / ms_phys
             row["applied_over_plain_rollout"] = row["applied_rollout_step_ms"] / row["rollout_step_ms"]
             row["rollout_T"] = T
         if args.dynamics:
-            def per_launch(fn):                     # (forward and dynamics do not count as env launches: divide by the calls)
-                for _ in range(args.warmup):
-                    fn()
-                env.timing_begin()
-                for _ in range(args.steps):
-                    fn()
-                return env.timing_end()[0] / args.steps
-            sites = ["endpoint"] if kind in ("cube", "tshape") else ["imu", "FR", "FL", "RR", "RL"]
-            row["forward_ms"] = per_launch(phys.forward)
+            sites = ["endpoint"] if kind in IMPLICIT else ["imu", "FR", "FL", "RR", "RL"]
+            row["forward_ms"] = per_call(env, lambda i: phys.forward(), args)
             phys.set_jac_sites([])
-            row["dynamics_ms"] = per_launch(phys.dynamics)
+            row["dynamics_ms"] = per_call(env, lambda i: phys.dynamics(), args)
             phys.set_jac_sites(sites)
-            row["dynamics_sites_ms"] = per_launch(phys.dynamics)
+            row["dynamics_sites_ms"] = per_call(env, lambda i: phys.dynamics(), args)
             row["jac_sites"] = len(sites)
             row["dynamics_over_forward"] = row["dynamics_sites_ms"] / row["forward_ms"]
-            from bench import csrc_sha16
             row["csrc_sha16"] = csrc_sha16()
         if args.constraint:
-            # forward and constraint_forces in alternating blocks (A B A B A B), medians of the blocks: a drift of the clocks
-            # over the run falls on both
-            def block(fn):
-                env.timing_begin()
-                for _ in range(args.steps):
-                    fn()
-                return env.timing_end()[0] / args.steps
+            # forward and constraint_forces in alternating blocks (A B A B A B), medians of the blocks
             for _ in range(args.warmup):
                 phys.forward()
                 phys.constraint_forces()
-            fwd, con = [], []
-            for _ in range(3):
-                fwd.append(block(phys.forward))
-                con.append(block(phys.constraint_forces))
-            row["forward_ms"] = float(np.median(fwd))
-            row["constraint_ms"] = float(np.median(con))
+            fwd, con = R.alternate([R.Arm(phys.forward, env, args.steps), R.Arm(phys.constraint_forces, env, args.steps)], 3, warmup=0)
+            row["forward_ms"] = R.median(fwd)
+            row["constraint_ms"] = R.median(con)
             row["forward_ms_blocks"], row["constraint_ms_blocks"] = fwd, con
             row["constraint_over_forward"] = row["constraint_ms"] / row["forward_ms"]
-            from bench import csrc_sha16
             row["csrc_sha16"] = csrc_sha16()
         row["finite"] = bool(torch.isfinite(env.view("qpos")).all())
         print(json.dumps(row), flush=True)
         rows.append(row)
-        del phys, env
+        del phys, env, b
         torch.cuda.synchronize()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

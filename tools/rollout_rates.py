@@ -10,12 +10,11 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rates_support as R
 
 
 def main() -> None:
@@ -28,30 +27,22 @@ def main() -> None:
     args = ap.parse_args()
     import torch
     import bench
-    from rsr_mjx_amd import prng
-    from rsr_mjx_amd.envs import airbot, go2
     from rsr_mjx_amd.physics import Physics
     T, rows = args.T, []
     for n in (int(x) for x in args.envs.split(",")):
         for kind in args.families.split(","):
-            if kind in ("cube", "tshape"):
-                envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-                dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), n)) if kind == "cube" else None
-            else:
-                envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain",
-                                   "footstand": "Go2Footstand"}[kind])
-                dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), n))
-            env = envdef.batched(n, randomization=dr)
-            env.reset(prng.split(prng.PRNGKey(0), n))
+            b = R.batch(kind, n, steps=0)
+            env, rng = b.env, b.rng
             phys = Physics(env)
             nf = phys.n_substeps
             # controls around the state the reset left (the env's home ctrl plus a small perturbation): stays in range for T steps
-            rng = np.random.default_rng(0)
             base = env.view("ctrl").clone()
             ctrl = (base[:, None, :] + torch.as_tensor(rng.normal(scale=0.05, size=(n, T, env.dims.nu)).astype(np.float32),
                                                        device=env.device)).contiguous()
             q0, v0, c0 = phys.qpos.clone(), phys.qvel.clone(), phys.ctrl.clone()
-            restart = lambda: phys.set_state(q0, v0, c0)
+
+            def restart():                                        # ahead of every arm, in no window
+                phys.set_state(q0, v0, c0); torch.cuda.synchronize()
 
             def step_loop(record):
                 qs, vs = [], []
@@ -63,37 +54,31 @@ def main() -> None:
 
             out = {f: torch.empty((n, T, w), device=env.device) for f, w in (("qpos", env.dims.nq), ("qvel", env.dims.nv), ("time", 1))}
             # kernel time: HIP events around the launches only
-            k_roll, k_step = [], []
-            for rep in range(args.reps + 1):
-                restart(); torch.cuda.synchronize()
-                env.timing_begin(); phys.rollout(ctrl, nf, out=out); ms, _ = env.timing_end()
-                if rep: k_roll.append(ms)
-                restart(); torch.cuda.synchronize()
-                env.timing_begin(); step_loop(False); ms, _ = env.timing_end()
-                if rep: k_step.append(ms)
+            k_roll, k_step = R.alternate([restart, R.Arm(lambda: phys.rollout(ctrl, nf, out=out), env),
+                                          restart, R.Arm(lambda: step_loop(False), env)], args.reps)
             # Python level: wall clock of collecting a qpos / qvel trajectory
             p_roll, p_step = [], []
             for rep in range(args.reps + 1):
-                restart(); torch.cuda.synchronize()
+                restart()
                 t0 = time.perf_counter(); tr = phys.rollout(ctrl, nf, fields=("qpos", "qvel")); torch.cuda.synchronize()
                 if rep: p_roll.append((time.perf_counter() - t0) * 1e3)
-                restart(); torch.cuda.synchronize()
+                restart()
                 t0 = time.perf_counter(); ts = step_loop(True); torch.cuda.synchronize()
                 if rep: p_step.append((time.perf_counter() - t0) * 1e3)
             same = bool(torch.equal(tr["qpos"].view(torch.int32), ts[0].view(torch.int32))
                         and torch.equal(tr["qvel"].view(torch.int32), ts[1].view(torch.int32)))
-            med = lambda x: float(np.median(x))
+            med = R.median
             row = dict(family=kind, num_envs=n, T=T, nsteps=nf, csrc_sha16=bench.csrc_sha16(),
                        kernel_rollout_ms=med(k_roll), kernel_steps_ms=med(k_step),
                        kernel_speedup=med(k_step) / med(k_roll),
                        python_rollout_ms=med(p_roll), python_step_loop_ms=med(p_step),
                        python_speedup=med(p_step) / med(p_roll),
                        rollout_env_steps_per_s=n * T / (med(k_roll) * 1e-3),
-                       kernel_spread=[min(k_roll), max(k_roll), min(k_step), max(k_step)],
+                       kernel_spread=R.spread(k_roll, k_step),
                        bitwise_equal=same, finite=bool(torch.isfinite(tr["qpos"]).all()))
             print(json.dumps(row), flush=True)
             rows.append(row)
-            del phys, env
+            del phys, env, b
             torch.cuda.synchronize()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

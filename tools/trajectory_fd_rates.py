@@ -9,13 +9,10 @@ Usage: python tools/trajectory_fd_rates.py [--sizes 1,16,256] [--T 32] [--reps 7
 from __future__ import annotations
 
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rates_support as R
 
 
 def main() -> None:
@@ -29,30 +26,13 @@ def main() -> None:
     args = ap.parse_args()
     import torch
     import bench
-    from rsr_mjx_amd import prng
-    from rsr_mjx_amd.envs import airbot, go2
     from rsr_mjx_amd.physics import Physics
-    T = args.T
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        open(args.out, "w").close()
+    T, write = args.T, R.row_writer(args.out)
     for m in (int(v) for v in args.sizes.split(",")):
         for kind in args.families.split(","):
-            if kind in ("cube", "tshape"):
-                envdef = airbot.AirbotPlayBase() if kind == "cube" else airbot.AirbotTShape()
-                dr = airbot.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(5), m)) if kind == "cube" else None
-                spec, scale = [("pos", "framepos", "endpoint"), ("linvel", "framelinvel", "endpoint")], 1.0
-            else:
-                envdef = go2.load({"go2flat": "Go2JoystickFlatTerrain", "go2rough": "Go2JoystickRoughTerrain",
-                                   "footstand": "Go2Footstand"}[kind])
-                dr = go2.domain_randomize(envdef.sys, prng.split(prng.PRNGKey(12), m))
-                spec, scale = envdef.sensors, 0.5
-            env = envdef.batched(m, randomization=dr)
-            env.reset(prng.split(prng.PRNGKey(0), m))
-            rng = np.random.default_rng(0)
-            for _ in range(3):
-                env.step(None, np.clip(rng.normal(size=(m, env.dims.nu)) * scale, -1, 1).astype(np.float32))
-            phys = Physics(env, sensors=spec)
+            b = R.batch(kind, m)
+            env, rng = b.env, b.rng
+            phys = Physics(env, sensors=b.spec)
             nf, nsd = phys.n_substeps, phys.nsensordata
             nv, nu = int(env.dims.nv), int(env.dims.nu)
             ncol, w = 2 * nv + nu, 2 * nv + nsd
@@ -65,35 +45,25 @@ def main() -> None:
             fd_cols = phys._fd_view("columns")                     # [M, ncol, 2 nv + RSR_MAX_SENSORDATA]
             torch.cuda.synchronize()
             start = env.record.clone()
-            t_a, t_b = [], []
-            for r in range(args.reps + 1):                        # (the first round warms both arms up)
-                env.timing_begin()
-                phys.trajectory_fd(ctrl, nf, eps=args.eps, nominal=False, out=out_a)
-                ms, _ = env.timing_end()
-                if r: t_a.append(ms)
-                torch.cuda.synchronize()
-                env.timing_begin()
+
+            def by_calls():                                       # arm B; putting the record back is part of what it costs
                 for t in range(T):
                     phys.ctrl.copy_(steps[t])
                     phys.transition_fd(nsteps=nf, eps=args.eps)
                     loop[t].copy_(fd_cols[:, :, :w])
                     phys.step(steps[t], nf)
                 env.record.copy_(start)
-                ms, _ = env.timing_end()
-                if r: t_b.append(ms)
-                torch.cuda.synchronize()
-            med = lambda x: float(np.median(x))
+            t_a, t_b = R.alternate([R.Arm(lambda: phys.trajectory_fd(ctrl, nf, eps=args.eps, nominal=False, out=out_a), env),
+                                    R.Arm(by_calls, env)], args.reps)
+            med = R.median
             same = bool(torch.equal(out_a["columns"].view(torch.int32), loop.transpose(0, 1).contiguous().view(torch.int32)))
             row = dict(family=kind, M=m, T=T, nsteps=nf, ncol=ncol, nsensordata=nsd, eps=args.eps, csrc_sha16=bench.csrc_sha16(),
                        trajectory_fd_ms=med(t_a), loop_ms=med(t_b), loop_over_trajectory_fd=med(t_b) / med(t_a),
                        columns_per_s=m * T * ncol / (med(t_a) * 1e-3),
-                       spread=[min(t_a), max(t_a), min(t_b), max(t_b)], reps=args.reps,
+                       spread=R.spread(t_a, t_b), reps=args.reps,
                        bitwise_equal=same, finite=bool(torch.isfinite(out_a["columns"]).all()))
-            print(json.dumps(row), flush=True)
-            if args.out:
-                with open(args.out, "a") as fh:
-                    fh.write(json.dumps(row) + "\n")
-            del phys, env
+            write(row)
+            del phys, env, b
             torch.cuda.synchronize()
 
 
