@@ -12,6 +12,8 @@
  *                          leaves per env (friction, mass, damping, gains, ...), with no replica batch; the record is read only.
  *   rsr_physics_feedback_rollouts <- the same in closed loop: lax.scan of u = ctrl + gain (x (-) x_ref) then mjx.step, the control
  *                          of every control step computed on the device from the sample's own state; the record is read only.
+ *   rsr_physics_cost_rollouts <- the same reduced on the device: vmap(lambda: sum(lax.scan(cost(mjx.step)))), the running cost
+ *                          [M, K] of a weighted least-squares tracking cost per sample, trajectories only on request.
  *   rsr_physics_set_sensors: the site sensors of data.sensordata (RSR_P_SENSORDATA, and a rollout's sensordata rows).
  *   rsr_physics_set_applied / rsr_physics_applied_view: data.xfrc_applied and data.qfrc_applied, per-env inputs of every forward
  *                          pass of these calls (zero until set).
@@ -200,6 +202,59 @@ typedef struct rsr_feedback { const float* gain; const float* qpos_ref; const fl
 int rsr_physics_feedback_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl,
                                   const rsr_feedback* fb, const rsr_param_samples* params, int K, int T, int nsteps,
                                   int flags, const rsr_rollout_out* out, float* ctrl_out, void* hip_stream);
+
+/* Cost rollouts, for MPPI, predictive sampling and CEM (the cost of every control sequence), an iLQR line search (the cost of
+ * every alpha of rsr_physics_feedback_rollouts) and system identification (the loss of every leaf set against a log): the
+ * rollouts above with the running cost of each sample formed on the device, [M, K] numbers out instead of [M, K, T, width]
+ * trajectories.  One launch, one wavefront per (env, sample).
+ * The rollout.  Sample (s, k) runs exactly the rollout of rsr_physics_feedback_rollouts with the same ctrl, fb, params, flags
+ * (RSR_FB_*), K, T and nsteps, or with fb NULL (open loop) exactly that of rsr_physics_param_rollouts, RSR_FB_CTRL_PER_SAMPLE
+ * standing for RSR_PR_CTRL_PER_SAMPLE: the trajectory is the same bit for bit, and so are the rows of traj (NULL or all-NULL:
+ * nothing recorded) and of out->ctrl (the u that was applied: ctrl_out of rsr_physics_feedback_rollouts; open loop, ctrl itself).
+ * The residuals are taken at the end of control step t, from the state after that step's last integration (the state row t of
+ * traj holds), against row [s, t] of the references, which the K samples of a slot share:
+ *   dq = qpos (-) qpos_ref[s, t]      in the tangent space [nv]: mj_differentiatePos as rsr_physics_feedback_rollouts takes it,
+ *                                     exactly 0 where the two are equal bit for bit
+ *   dv = qvel - qvel_ref[s, t]        [nv]
+ *   du = u_t - ctrl_ref[s, t]         [nu]; u_t: the control that was applied in step t, after feedback and clamp
+ *   ds = sensordata_t - sensor_ref[s, t]   [nsensordata]; sensordata_t: the sensordata row t of traj
+ * The cost.  c_t = 1/2 (sum w_qpos dq^2 + sum w_qvel dv^2 + sum w_ctrl du^2 + sum w_sensor ds^2), cost = sum over t of c_t, in
+ * fp32 and in a fixed order: entry i of each term is (w_i d_i) d_i, two roundings; lane i of the wavefront adds its entries of
+ * the four terms in the order qpos, qvel, ctrl, sensor (a term that is off, or that has no entry i, adds +0), no contraction; the
+ * 64 lane sums are added by the kernels' wave_sum (a fixed tree: pairs, quads, eights, rows of 16 lanes, then
+ * (row 3 + row 2) + (row 1 + row 0)) and halved: c_t; cost accumulates c_t from +0 for t = 0 .. T-1.  terms: the same with each term's lane entries alone,
+ * four sums.  A sample's outputs depend on that sample's inputs alone, bit for bit: not on M, K, the slot's position, on which
+ * optional outputs are requested, or on the run.  A terminal cost is a heavier row T-1; time-varying weights are the rows.
+ * Weights are read as given (the sign and size are the caller's; a bound on the rounding error assumes weights >= 0), and
+ * non-finite states propagate into the cost: there is no status word.
+ * cost (struct rsr_cost): device float32, rows by slot.  A NULL weight turns its term off and its reference is not read (qpos_ref
+ * and qvel_ref still are for out->dx); a NULL qvel_ref, ctrl_ref or sensor_ref stands for zeros.
+ * out (struct rsr_cost_out): device float32, rows by (slot, sample); cost is required, the others are written when not NULL.
+ * Nothing but the buffers of traj and out is written: the record, every buffer of the handle, the batch's own leaf tensors and
+ * the PRNG keys are untouched; the handle owns no buffer for this call.  An id outside [0, num_envs) runs nothing and its slot's
+ * rows are left alone, in every output.  Checked before any device work.  RSR_ERR_ARG: everything
+ * rsr_physics_feedback_rollouts refuses, except that fb may be NULL and traj may be NULL or all-NULL; an fb with a NULL member;
+ * RSR_FB_PER_SAMPLE or RSR_FB_CLAMP with fb NULL; a NULL cost, out or out->cost; all four weights NULL; w_qpos, or out->dx,
+ * without qpos_ref; w_sensor or sensor_ref with no sensor table set.  RSR_ERR_UNSUPPORTED: as rsr_physics_param_rollouts. */
+typedef struct rsr_cost {            /* device float32, rows by slot, shared by a slot's K samples */
+  const float *qpos_ref;   /* [M, T, nq]   required when w_qpos is given                 */
+  const float *qvel_ref;   /* [M, T, nv]   NULL: zeros                                   */
+  const float *ctrl_ref;   /* [M, T, nu]   NULL: zeros                                   */
+  const float *sensor_ref; /* [M, T, nsensordata] NULL: zeros                            */
+  const float *w_qpos, *w_qvel, *w_ctrl, *w_sensor;  /* [M, T, nv|nv|nu|nsensordata]; NULL: that term is off and its ref is not read */
+} rsr_cost;
+typedef struct rsr_cost_out {
+  float *cost;       /* [M, K]            required: sum over t of step cost              */
+  float *step_cost;  /* [M, K, T]         optional                                       */
+  float *terms;      /* [M, K, 4]         optional: the four terms' sums over t (qpos, qvel, ctrl, sensor) */
+  float *dx;         /* [M, K, T, 2 nv]   optional: dq | dv of every control step        */
+  float *ctrl;       /* [M, K, T, nu]     optional: the u that was applied (ctrl_out of feedback_rollouts) */
+} rsr_cost_out;
+int rsr_physics_cost_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl,
+                              const rsr_feedback* fb /* NULL: open loop */, const rsr_param_samples* params,
+                              const rsr_cost* cost, int K, int T, int nsteps, int flags /* RSR_FB_* */,
+                              const rsr_rollout_out* traj /* NULL or all-NULL: nothing recorded */,
+                              const rsr_cost_out* out, void* hip_stream);
 
 /* Applied forces (MuJoCo's data.xfrc_applied / data.qfrc_applied): per-env state of the handle, added in every forward pass of
  * rsr_physics_step (each substep), _forward, _forward_envs and _rollout (each substep, held for all T control steps):

@@ -45,7 +45,8 @@ PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step",
                 "rsr_physics_applied_view", "rsr_physics_set_jac_sites", "rsr_physics_dynamics", "rsr_physics_dynamics_view",
                 "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
                 "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts",
-                "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd", "rsr_physics_lqr_backward", "rsr_physics_ik"]
+                "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd", "rsr_physics_lqr_backward", "rsr_physics_ik",
+                "rsr_physics_cost_rollouts"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -94,6 +95,22 @@ class Feedback(C.Structure):
 
 # the RSR_FB_* flags (include/rsr_physics.h)
 FB_CTRL_PER_SAMPLE, FB_PER_SAMPLE, FB_CLAMP = 1, 2, 4
+
+
+COST_REFS = ("qpos_ref", "qvel_ref", "ctrl_ref", "sensor_ref")
+COST_WEIGHTS = ("w_qpos", "w_qvel", "w_ctrl", "w_sensor")
+
+
+class Cost(C.Structure):
+    """struct rsr_cost (include/rsr_physics.h): device pointers, rows by slot: the references [M, T, nq | nv | nu | nsensordata] and
+    the weights [M, T, nv | nv | nu | nsensordata]; a NULL weight = the term is off, a NULL qvel / ctrl / sensor reference = zeros."""
+    _fields_ = [(n, C.c_void_p) for n in COST_REFS + COST_WEIGHTS]
+
+
+class CostOut(C.Structure):
+    """struct rsr_cost_out (include/rsr_physics.h): device pointers, cost [M, K] (required), step_cost [M, K, T], terms [M, K, 4],
+    dx [M, K, T, 2 nv] and ctrl [M, K, T, nu] (NULL = not written)."""
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "step_cost", "terms", "dx", "ctrl")]
 
 
 
@@ -198,6 +215,7 @@ def lib() -> C.CDLL:
     L.rsr_physics_sample_rollouts.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp]
     L.rsr_physics_param_rollouts.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
     L.rsr_physics_feedback_rollouts.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.rsr_physics_cost_rollouts.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.rsr_physics_trajectory_fd.argtypes = [vp, vp, i32, vp, i32, i32, C.c_float, i32, vp, vp]
     L.rsr_physics_lqr_backward.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
     L.rsr_physics_ik.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]

@@ -2,7 +2,7 @@
 // rsr_physics_rollout / rsr_physics_view, the sensor table of rsr_sensors.hpp, the applied forces (rsr_physics_set_applied) and
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse), sampled rollouts (rsr_physics_sample_rollouts), parameter
-// rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts), the transition Jacobians along a
+// rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts), cost rollouts (rsr_physics_cost_rollouts), the transition Jacobians along a
 // trajectory (rsr_physics_trajectory_fd), the LQR backward pass (rsr_physics_lqr_backward) and inverse kinematics on site pose
 // targets (rsr_physics_ik).  Every launch is a physics op
 // (rsr::PhysOp) sent through physics_launch; the kernels are in the family units (physics/rsr_physics_kernels.hpp).
@@ -293,6 +293,46 @@ extern "C" int rsr_physics_feedback_rollouts(rsr_physics* p, const int32_t* env_
   sw.fb_per_sample = (flags & RSR_FB_PER_SAMPLE) != 0;
   sw.fb_clamp = (flags & RSR_FB_CLAMP) != 0;
   return sweep_rollouts(p, env_ids, count, ctrl, params, sw, T, nsteps, out, hip_stream, "rsr_physics_feedback_rollouts");
+}
+
+// Cost rollouts: the sweep's launch shape with the cost stage (rsr_cost.hpp), an op of its own.  Its own checks, sample_grid's,
+// the leaves' as sweep_rollouts makes them, then the one launch; nothing is allocated and no buffer of the handle is used.
+extern "C" int rsr_physics_cost_rollouts(rsr_physics* p, const int32_t* env_ids, int count, const float* ctrl, const rsr_feedback* fb,
+                                         const rsr_param_samples* params, const rsr_cost* cost, int K, int T, int nsteps, int flags,
+                                         const rsr_rollout_out* traj, const rsr_cost_out* out, void* hip_stream) {
+  const char* who = "rsr_physics_cost_rollouts";
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: null handle");
+  if (!ctrl) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: null ctrl");
+  if (fb && (!fb->gain || !fb->qpos_ref || !fb->qvel_ref)) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: an fb with a null member");
+  if (!fb && (flags & (RSR_FB_PER_SAMPLE | RSR_FB_CLAMP))) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: RSR_FB_PER_SAMPLE or RSR_FB_CLAMP with a null fb");
+  if (!cost || !out || !out->cost) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: null cost, out or out->cost");
+  if (!(cost->w_qpos || cost->w_qvel || cost->w_ctrl || cost->w_sensor)) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: all four weights are null");
+  if (cost->w_qpos && !cost->qpos_ref) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: w_qpos without qpos_ref");
+  if (out->dx && !cost->qpos_ref) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: out->dx without qpos_ref");
+  if (K < 1 || T < 1 || nsteps < 1) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: K, T and nsteps must be >= 1");
+  if (flags & ~(RSR_FB_CTRL_PER_SAMPLE | RSR_FB_PER_SAMPLE | RSR_FB_CLAMP)) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: unknown flag bits");
+  if ((cost->w_sensor || cost->sensor_ref) && p->nsd == 0) return fail(RSR_ERR_ARG, "rsr_physics_cost_rollouts: w_sensor or sensor_ref with no sensor table set");
+  const rsr_rollout_out none{};
+  const rsr_rollout_out* tr = traj ? traj : &none;
+  int grid;
+  if (const int rc = sample_grid(p, env_ids, count, K, T, nsteps, tr, who, &grid)) return rc;
+  rsr::SweepArgs sw{};
+  for (int f = 0; params && f < RSR_DR_COUNT; ++f) {
+    if (params->leaf[f] && f >= RSR_DR_BODY_IPOS && p->b->model->spec->family != rsr::FAMILY_GO2)
+      return fail(RSR_ERR_UNSUPPORTED, std::string(who) + ": this leaf is per-env only in the Go2 kernels (rsr_batch_set_dr_field); the Airbot kernels take the first four");
+    sw.leaf[f] = params->leaf[f];
+  }
+  sw.K = K;
+  sw.ctrl_per_sample = (flags & RSR_FB_CTRL_PER_SAMPLE) != 0;
+  if (fb) { sw.fb_gain = fb->gain; sw.fb_qpos = fb->qpos_ref; sw.fb_qvel = fb->qvel_ref; }
+  sw.fb_per_sample = (flags & RSR_FB_PER_SAMPLE) != 0;
+  sw.fb_clamp = (flags & RSR_FB_CLAMP) != 0;
+  rsr::Launch x = physics_args(p, nullptr, env_ids, grid, nsteps, hip_stream);
+  x.ph.r = rsr::RollArgs{ctrl, T, tr->qpos, tr->qvel, tr->time, tr->actuator_force, tr->ncon, tr->sensordata};
+  x.ph.sw = sw;                                  // (sw.ctrl_out stays null: the cost stage writes out->ctrl)
+  x.ph.cs = rsr::CostArgs{cost->qpos_ref, cost->qvel_ref, cost->ctrl_ref, cost->sensor_ref, cost->w_qpos, cost->w_qvel, cost->w_ctrl, cost->w_sensor,
+                          out->cost, out->step_cost, out->terms, out->dx, out->ctrl};
+  return counted(p, physics_launch(p, rsr::OP_COST_ROLLOUTS, x, who));
 }
 
 // the applied-force buffers, on first use: both or neither

@@ -167,6 +167,18 @@ struct IkArgs {
   float tol_pos, tol_rot, max_step;
 };
 static_assert(sizeof(IkArgs) == 64 + 12 * RSR_MAX_JAC_SITES + 32, "ik_kernel's kernel-argument block");
+// rsr_physics_cost_rollouts (rsr_cost.hpp): what cost_kernel takes beside sweep_kernel's arguments (PhysLaunch::cs).  The
+// references and weights are rows [M][T][w] by slot, shared by a slot's K samples; the outputs are rows by (slot, sample).
+struct CostArgs {
+  const float *qpos_ref, *qvel_ref, *ctrl_ref, *sensor_ref;   // [M][T][nq | nv | nu | nsd]; qvel / ctrl / sensor null: zeros
+  const float *w_qpos, *w_qvel, *w_ctrl, *w_sensor;           // [M][T][nv | nv | nu | nsd]; null: the term is off
+  float* cost;          // [M][K]
+  float* step_cost;     // [M][K][T], or null
+  float* terms;         // [M][K][4] (qpos, qvel, ctrl, sensor), or null
+  float* dx;            // [M][K][T][2 nv] dq | dv, or null
+  float* ctrl_out;      // [M][K][T][nu] the applied ctrl, or null (sw.ctrl_out stays null: the cost stage writes the row)
+};
+static_assert(sizeof(CostArgs) == 13 * sizeof(void*), "cost_kernel's kernel-argument block");
 
 // The physics ops of a family unit's launch entry (launch_physics, rsr_physics_kernels.hpp).  An entry takes its op as an int, of
 // enum Op (rsr_launch.hpp) or of this enum: these start above enum Op's, so that no value names two ops.  A new op is a member
@@ -187,6 +199,7 @@ enum PhysOp {
   OP_TRAJ_FD,            // rsr_physics_trajectory_fd, second launch (p, tj): grid = envs x T x columns, or listed envs (p.ids) x T x columns
   OP_LQR_BACKWARD,       // rsr_physics_lqr_backward (lq): grid = slots; reads neither the model nor the record
   OP_IK,                 // rsr_physics_ik (ik): grid = slots, the env of a slot from ik.ids
+  OP_COST_ROLLOUTS,      // rsr_physics_cost_rollouts (p, r, sw, cs): grid and rows as OP_PHYS_SWEEP's
 };
 // The physics ops' arguments (Launch::ph), one field per op that needs its own
 struct PhysLaunch {
@@ -201,6 +214,7 @@ struct PhysLaunch {
   TrajArgs tj;          // OP_TRAJ_NOMINAL, OP_TRAJ_FD
   LqrArgs lq;           // OP_LQR_BACKWARD
   IkArgs ik;            // OP_IK
+  CostArgs cs;          // OP_COST_ROLLOUTS (with p, r and sw)
   Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
 };
 

@@ -14,6 +14,9 @@
                                                                                           (the same in closed loop: the control of
                                                                                            every control step from the sample's own
                                                                                            state, on the device; [M, K, T, w])
+    vmap of sum(lax.scan(cost(mjx.step)))        ->  Physics.cost_rollouts(ctrl, cost)    (either of the two with the running cost
+                                                                                           of a weighted tracking cost formed on
+                                                                                           the device: [M, K], no trajectory read)
     mjx_env.get_sensor_data(model, data, name)  ->  Physics.sensor(name)                 (site sensors, Physics.set_sensors)
     data.replace(xfrc_applied=..., qfrc_applied=...) ->  Physics.set_applied(xfrc, qfrc)  (held by every later step / forward /
                                                                                            rollout, like a Data field)
@@ -561,6 +564,14 @@ class Physics:
                 setattr(ptrs, f, t.data_ptr())
         return res, ptrs
 
+    def _rows(self, who: str, name: str, t, M: int, tail: tuple, ranks: tuple):
+        """(K or None, T) of the input `name` of the method `who`, a [M, (K,) T, *tail] tensor of one of the ranks `ranks`, checked"""
+        self._f32(f"{who} expects {name} as", t, f"({M}, T >= 1, {', '.join(map(str, tail))}) or ({M}, K >= 1, T >= 1, {', '.join(map(str, tail))})",
+                  lambda t: t.dim() in ranks and t.shape[0] == M and tuple(t.shape[t.dim() - len(tail):]) == tail
+                  and min(t.shape[1:t.dim() - len(tail)]) >= 1, False)
+        per = t.dim() == len(tail) + 3
+        return (int(t.shape[1]) if per else None), int(t.shape[-len(tail) - 1])
+
     def param_rollouts(self, ctrl, params, nsteps: Optional[int] = None, fields: Sequence[str] = ("qpos", "qvel", "time"), env_ids=None,
                        out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """What system identification, domain-randomised planning and CEM over model parameters ask: from the state each env is
@@ -617,15 +628,7 @@ class Physics:
         ids = None if env_ids is None else self._ids(env_ids, who)
         d = self.dims
         M, nu, nv, nq = self.num_envs if ids is None else int(ids.numel()), int(d.nu), int(d.nv), int(d.nq)
-
-        def rows(name, t, tail, ranks):
-            """(K or None, T) of a [M, (K,) T, *tail] input"""
-            self._f32(f"{who} expects {name} as", t, f"({M}, T >= 1, {', '.join(map(str, tail))}) or ({M}, K >= 1, T >= 1, {', '.join(map(str, tail))})",
-                      lambda t: t.dim() in ranks and t.shape[0] == M and tuple(t.shape[t.dim() - len(tail):]) == tail
-                      and min(t.shape[1:t.dim() - len(tail)]) >= 1, False)
-            per = t.dim() == len(tail) + 3
-            return (int(t.shape[1]) if per else None), int(t.shape[-len(tail) - 1])
-
+        rows = lambda name, t, tail, ranks: self._rows(who, name, t, M, tail, ranks)
         Kc, T = rows("ctrl", ctrl, (nu,), (3, 4))
         Kg, Tg = rows("gain", gain, (nu, 2 * nv), (4, 5))
         fb_rank = gain.dim() - 1                         # the refs' rank: [M, T, w] or [M, K, T, w]
@@ -650,6 +653,95 @@ class Physics:
         self._call_envs("rsr_physics_feedback_rollouts", who, ids, C.c_void_p(c.data_ptr()), C.byref(fb), C.byref(ps), K, T, nsteps, flags,
                         C.byref(ptrs), applied, checked=True, hold=(c, g, qr, vr, *leaves))
         return res
+
+    def cost_rollouts(self, ctrl, cost, feedback=None, params=None, nsteps: Optional[int] = None, fields: Sequence[str] = (),
+                      env_ids=None, clamp: bool = False, out: Optional[Dict[str, Any]] = None, K: Optional[int] = None,
+                      step_cost: bool = False, terms: bool = False, residual: bool = False) -> Dict[str, Any]:
+        """What every sampling planner, an iLQR line search and system identification end in: the rollouts of param_rollouts
+        (`feedback` None: open loop) or feedback_rollouts (`feedback` a dict with gain, qpos_ref, qvel_ref as that method takes
+        them), with the running cost of every sample formed on the device, [M, K] numbers instead of [M, K, T, w] trajectories.
+        ctrl, params, nsteps, env_ids (here an env may be listed more than once), clamp and K are feedback_rollouts'; the
+        trajectories are the same bit for bit.  `cost` is a dict of float32 tensors on the env's device, rows by env and control
+        step, shared by an env's K samples: the weights
+        w_qpos [M, T, nv], w_qvel [M, T, nv], w_ctrl [M, T, nu], w_sensor [M, T, nsensordata] (a weight not given: that term is
+        off; at least one must be) and the references qpos_ref [M, T, nq] (needed by w_qpos and by `residual`), qvel_ref
+        [M, T, nv], ctrl_ref [M, T, nu], sensor_ref [M, T, nsensordata] (not given: zeros).  At the end of control step t
+            c_t = 1/2 (w_qpos . dq^2 + w_qvel . dv^2 + w_ctrl . du^2 + w_sensor . ds^2),
+        dq = qpos (-) qpos_ref[., t] in the tangent space (exactly 0 on the reference), dv = qvel - qvel_ref[., t], du = the
+        control that was applied - ctrl_ref[., t], ds = that step's sensordata - sensor_ref[., t]; a terminal cost is a heavier
+        row T - 1.  fp32 in a fixed order (include/rsr_physics.h): a sample's numbers do not depend on M, K, its slot or on what
+        else is asked for.  Returns {"cost": [M, K]} and, when asked, "step_cost" [M, K, T], "terms" [M, K, 4] (the sums over t
+        of the qpos, qvel, ctrl and sensor terms), "dx" [M, K, T, 2 nv] (`residual`: dq | dv, what the cost expansion of
+        lqr_backward takes) and `fields` (ROLLOUT_FIELDS and "ctrl", as feedback_rollouts; default none).  `out`: caller-owned
+        float32 tensors to fill instead of new ones, by those names.  Writes nothing else: the record, every buffer of the handle
+        and the batch's own leaf tensors stay as they are."""
+        who = "cost_rollouts"
+        nsteps = self._steps(who, nsteps)
+        ids = None if env_ids is None else self._ids(env_ids, who, repeats=True)       # (an env may be listed more than once)
+        d, nsd = self.dims, self.nsensordata
+        M, nu, nv, nq = self.num_envs if ids is None else int(ids.numel()), int(d.nu), int(d.nv), int(d.nq)
+        Kc, T = self._rows(who, "ctrl", ctrl, M, (nu,), (3, 4))
+        # the cost rows: [M, T, w], by slot
+        if not isinstance(cost, dict):
+            raise ValueError(f"{who}: cost must be a dict with some of {_lib.COST_WEIGHTS + _lib.COST_REFS}, got {type(cost).__name__}")
+        unknown = sorted(set(cost) - set(_lib.COST_WEIGHTS + _lib.COST_REFS))
+        if unknown:
+            raise ValueError(f"{who}: cost has {unknown}; it may hold {_lib.COST_WEIGHTS + _lib.COST_REFS}")
+        cost = {k: v for k, v in cost.items() if v is not None}
+        if not any(w in cost for w in _lib.COST_WEIGHTS):
+            raise ValueError(f"{who}: cost gives no weight: at least one of {_lib.COST_WEIGHTS} is needed")
+        if "qpos_ref" not in cost and ("w_qpos" in cost or residual):
+            raise ValueError(f"{who}: cost['qpos_ref'] is needed by {'w_qpos' if 'w_qpos' in cost else 'residual=True'}")
+        if nsd == 0 and ("w_sensor" in cost or "sensor_ref" in cost):
+            raise ValueError(f"{who}: cost['w_sensor'] / cost['sensor_ref'] given but no sensors are set (set_sensors)")
+        width = dict(qpos_ref=nq, qvel_ref=nv, ctrl_ref=nu, sensor_ref=nsd, w_qpos=nv, w_qvel=nv, w_ctrl=nu, w_sensor=nsd)
+        cs, rows = _lib.Cost(), []
+        for name, t in cost.items():
+            shape = (M, T, width[name])
+            self._f32(f"{who} expects cost[{name!r}] as", t, str(shape), shape, False)
+            t = t.contiguous()
+            setattr(cs, name, t.data_ptr())
+            rows.append(t)
+        # the gain rows, as feedback_rollouts takes them
+        fb, Kg = None, None
+        if feedback is not None:
+            if not isinstance(feedback, dict) or set(feedback) != {"gain", "qpos_ref", "qvel_ref"} or any(v is None for v in feedback.values()):
+                raise ValueError(f"{who}: feedback must be None or a dict with gain, qpos_ref and qvel_ref")
+            Kg, Tg = self._rows(who, "feedback['gain']", feedback["gain"], M, (nu, 2 * nv), (4, 5))
+            fb_rank = feedback["gain"].dim() - 1
+            Kq, Tq = self._rows(who, "feedback['qpos_ref']", feedback["qpos_ref"], M, (nq,), (fb_rank,))
+            Kv, Tv = self._rows(who, "feedback['qvel_ref']", feedback["qvel_ref"], M, (nv,), (fb_rank,))
+            if (Tg, Tq, Tv) != (T, T, T):
+                raise ValueError(f"{who}: feedback's gain, qpos_ref and qvel_ref have T = {Tg}, {Tq}, {Tv}, ctrl T = {T}")
+            if (Kq, Kv) != (Kg, Kg):
+                raise ValueError(f"{who}: feedback's gain, qpos_ref and qvel_ref have K = {Kg}, {Kq}, {Kv}")
+            g, qr, vr = (feedback[k].contiguous() for k in ("gain", "qpos_ref", "qvel_ref"))
+            fb = _lib.Feedback(g.data_ptr(), qr.data_ptr(), vr.data_ptr())
+            rows += [g, qr, vr]
+        elif clamp:
+            raise ValueError(f"{who}: clamp=True needs feedback")
+        for name, k in (("ctrl", Kc), ("feedback", Kg)):
+            if k is not None and K is not None and k != int(K):
+                raise ValueError(f"{who}: {name} has K = {k}, the others (or the K given) K = {int(K)}")
+            K = k if k is not None else K
+        if K is not None and int(K) < 1:
+            raise ValueError(f"{who}: K must be >= 1, got {K}")
+        ps, leaves, K = self._sampled_leaves(who, params, M, None if K is None else int(K))
+        if K is None:
+            raise ValueError(f"{who}: K is not given: pass it, or a per-sample ctrl, gain or leaf")
+        res, ptrs = self._trajectory_out(who, fields, (M, K, T), out, extra=dict(ctrl=nu), none_ok=True)
+        shapes = dict(cost=(M, K))
+        shapes.update({k: s for k, s, on in (("step_cost", (M, K, T), step_cost), ("terms", (M, K, 4), terms),
+                                             ("dx", (M, K, T, 2 * nv), residual)) if on})
+        mine = self._outputs(who, shapes, out, False)
+        co = _lib.CostOut(**{k: t.data_ptr() for k, t in mine.items()})
+        if "ctrl" in res:
+            co.ctrl = res["ctrl"].data_ptr()
+        c = ctrl.contiguous()
+        flags = (_lib.FB_CTRL_PER_SAMPLE if Kc is not None else 0) | (_lib.FB_PER_SAMPLE if Kg is not None else 0) | (_lib.FB_CLAMP if clamp else 0)
+        self._call_envs("rsr_physics_cost_rollouts", who, ids, C.c_void_p(c.data_ptr()), None if fb is None else C.byref(fb), C.byref(ps),
+                        C.byref(cs), K, T, nsteps, flags, C.byref(ptrs), C.byref(co), checked=True, hold=(c, *rows, *leaves))
+        return {**mine, **res}
 
     def trajectory_fd(self, ctrl, nsteps: Optional[int] = None, eps: float = 1e-3, centered: bool = True, env_ids=None,
                       nominal: bool = True, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
