@@ -30,6 +30,9 @@
  *                          launch; neither the model nor the record is read.
  *   rsr_physics_ik      <- an IK library on top of mj_jacSite (damped least squares on site pose targets): M problems, one launch,
  *                          every iteration on the device; the record is read only.
+ *   rsr_physics_kalman  <- a Kalman filter and RTS smoother over a log (lax.scan over A_t, C_t forwards, then reverse=True): the
+ *                          linearised / error-state EKF about the nominal run of rsr_physics_trajectory_fd, M problems, one launch;
+ *                          neither the model nor the record is read.
  *
  * A physics handle shares its batch with rsr_step: same model, same per-env leaves of rsr_batch_set_dr / rsr_batch_set_dr_field,
  * same record.  The calls read and write only the pipeline fields qpos, qvel, ctrl, qacc_warmstart, time, xpos, site_xpos (a
@@ -437,6 +440,51 @@ typedef struct rsr_lqr_out  { float* gain; float* k; float* dv; float* status; f
 int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const float* columns, int row_stride,
                              const rsr_lqr_cost* cost, const float* mu, int flags,
                              const rsr_lqr_out* out, void* hip_stream);
+
+/* Kalman filter and smoother, the estimation dual of rsr_physics_lqr_backward: a linear time-varying Kalman filter with a
+ * Rauch-Tung-Striebel smoother on M independent problems, one launch with one wavefront per slot and all T steps inside it.  The
+ * state is the deviation dx_t from a nominal trajectory in the tangent space (mj_differentiatePos), nx = 2 nv: an error-state /
+ * linearised EKF.  The handle supplies nv, nu, the device and the family's launch entry only: the call reads neither the model nor
+ * the record, takes no env_ids, and the M slots are whatever the caller's buffers hold.  All pointers are device float32.
+ * columns: [M, T, ncol, row_stride], ncol = nx + nu: the buffer rsr_physics_trajectory_fd writes, passed as it is.  Of row j < nx of
+ * block (s, t), entry i < nx is A_t[i][j] and entry nx + r, r < ny, is C_t[r][j]; rows j >= nx (B, D) and entries at or beyond
+ * nx + ny are never read.  1 <= ny <= RSR_MAX_SENSORDATA and nx + ny <= row_stride.  C_t is the Jacobian of step t's sensordata
+ * with respect to the state before step t, so the model is dx_{t+1} = A_t dx_t + w_t, dy_t = C_t dx_t + v_t.
+ * in: dy [M, T, ny], the measured sensordata minus the nominal run's (rsr_physics_sample_rollouts with K = 1 on the same record);
+ * r [M, T, ny], the measurement variances (R_t diagonal; +inf: that sample is missing and is skipped exactly); q [M, T, nx], the
+ * process-noise variances (Q_t diagonal, finite and >= 0); x0 [M, nx], may be NULL (zeros); P0 [M, nx, nx], read as given: the
+ * caller passes it symmetric.  Because R_t is diagonal the update takes one sensor entry at a time, ascending:
+ *   x = x0, P = P0
+ *   for t = 0 .. T-1:
+ *     for j = 0 .. ny-1 with r_tj != +inf:
+ *       w = P c_j (c_j: row j of C_t);  s = c_j . w + r_tj;  nu = dy_tj - c_j . x
+ *       x += w (nu / s);  P[i][k] = fma(-(w_i w_k), 1 / s, P[i][k])          (P stays symmetric bit for bit)
+ *       nll += 1/2 (nu^2 / s + logf(s) + log 2 pi)
+ *     xf[t] = x, pf[t] = P
+ *     x = A_t x;  P = (S + S^T) / 2 + diag(q_t) with S = A_t P A_t^T
+ *   xf[T] = x, pf[T] = P                  (a prediction: there is no measurement at T)
+ * and, if out->xs is given, the smoother: xs[T] = xf[T], ps[T] = pf[T], for t = T-1 .. 0:
+ *   Pm = the predict above on pf[t] (the same code, the same bits);  G = pf[t] A_t^T Pm^-1 (Cholesky of Pm)
+ *   xs[t] = xf[t] + G (xs[t+1] - A_t xf[t]);  ps[t] = pf[t] + (E + E^T) / 2 with E = G (ps[t+1] - Pm) G^T
+ * in fp32, every output element one lane's fma chain in a fixed order: a slot's result depends on that slot's inputs alone, bit for
+ * bit, whatever M is and from run to run; with xs NULL the filter outputs are bit for bit those of the smoothing call; and entries
+ * with r = +inf give bit for bit the result of the same problem with those sensor columns removed and ny smaller.
+ * out: xf [M, T+1, nx] and status [M, 2] (as float) are required; pf [M, T+1, nx, nx] is required when smoothing; xs [M, T+1, nx]
+ * turns the smoother on; ps [M, T+1, nx, nx] and nll [M] (the innovation negative log-likelihood) are optional (NULL: not
+ * recorded).
+ * Failure: status[s] = (filter, smoother), each -1 or the step t that failed.  A filter step fails if an r_tj is neither +inf nor
+ * finite and > 0, or if an s is not finite and > 0: the slot stops there, rows < t of xf / pf keep what was written and rows >= t
+ * are left alone, nll[s] = 0 and the smoother does not run.  A smoother step fails if a Cholesky pivot of Pm is <= 0 or not
+ * finite: rows <= t of xs / ps are left alone, rows > t keep what was written.  The other slots are unaffected.
+ * Only the buffers of out are written: the record, every buffer of the handle, the batch's own leaf tensors and the PRNG keys are
+ * untouched; the handle owns no buffer for this call.  RSR_ERR_ARG, checked before any device work: null handle, columns, in or
+ * out; a NULL dy, r, q, P0, xf or status; xs or ps without pf; ps without xs; M < 1 or T < 1; ny outside
+ * [1, RSR_MAX_SENSORDATA]; row_stride < 2 nv + ny; unknown flag bits (there are none yet: flags must be 0); M (T+1) at or above
+ * 2^31. */
+typedef struct rsr_kalman_in  { const float* dy; const float* r; const float* q; const float* x0; const float* P0; } rsr_kalman_in;
+typedef struct rsr_kalman_out { float* xf; float* pf; float* xs; float* ps; float* nll; float* status; } rsr_kalman_out;
+int rsr_physics_kalman(rsr_physics* p, int M, int T, const float* columns, int row_stride, int ny,
+                       const rsr_kalman_in* in, int flags, const rsr_kalman_out* out, void* hip_stream);
 
 /* Inverse kinematics on site pose targets: which qpos puts these sites there.  Damped least squares (Levenberg-Marquardt with a
  * fixed damping) on M independent problems, one launch with one wavefront per slot and every iteration inside it.  Slot s takes

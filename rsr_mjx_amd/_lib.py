@@ -46,7 +46,7 @@ PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step",
                 "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
                 "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts",
                 "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd", "rsr_physics_lqr_backward", "rsr_physics_ik",
-                "rsr_physics_cost_rollouts"]
+                "rsr_physics_cost_rollouts", "rsr_physics_kalman"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -130,6 +130,18 @@ class LqrOut(C.Structure):
     """struct rsr_lqr_out (include/rsr_physics.h): device pointers, gain [M, T, nu, nx], k [M, T, nu], dv [M, 2], status [M]
     (required), vx [M, T+1, nx] and vxx [M, T+1, nx, nx] (NULL = not recorded)."""
     _fields_ = [(n, C.c_void_p) for n in ("gain", "k", "dv", "status", "vx", "vxx")]
+
+
+class KalmanIn(C.Structure):
+    """struct rsr_kalman_in (include/rsr_physics.h): device pointers, dy [M, T, ny], r [M, T, ny] (+inf = missing), q [M, T, nx],
+    x0 [M, nx] (NULL = zeros), P0 [M, nx, nx]; nx = 2 nv."""
+    _fields_ = [(n, C.c_void_p) for n in ("dy", "r", "q", "x0", "P0")]
+
+
+class KalmanOut(C.Structure):
+    """struct rsr_kalman_out (include/rsr_physics.h): device pointers, xf [M, T+1, nx] and status [M, 2] (required), pf
+    [M, T+1, nx, nx] (required with xs), xs [M, T+1, nx] (NULL = no smoother), ps [M, T+1, nx, nx] and nll [M] (NULL = not recorded)."""
+    _fields_ = [(n, C.c_void_p) for n in ("xf", "pf", "xs", "ps", "nll", "status")]
 
 
 # the RSR_LQR_* flags (include/rsr_physics.h)
@@ -219,6 +231,7 @@ def lib() -> C.CDLL:
     L.rsr_physics_trajectory_fd.argtypes = [vp, vp, i32, vp, i32, i32, C.c_float, i32, vp, vp]
     L.rsr_physics_lqr_backward.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
     L.rsr_physics_ik.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    L.rsr_physics_kalman.argtypes = [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

@@ -3,8 +3,8 @@
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse), sampled rollouts (rsr_physics_sample_rollouts), parameter
 // rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts), cost rollouts (rsr_physics_cost_rollouts), the transition Jacobians along a
-// trajectory (rsr_physics_trajectory_fd), the LQR backward pass (rsr_physics_lqr_backward) and inverse kinematics on site pose
-// targets (rsr_physics_ik).  Every launch is a physics op
+// trajectory (rsr_physics_trajectory_fd), the LQR backward pass (rsr_physics_lqr_backward), inverse kinematics on site pose
+// targets (rsr_physics_ik) and the Kalman filter and smoother (rsr_physics_kalman).  Every launch is a physics op
 // (rsr::PhysOp) sent through physics_launch; the kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
@@ -550,6 +550,27 @@ extern "C" int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const floa
   x.ph.lq = rsr::LqrArgs{columns, row_stride, T, cost->lx, cost->lu, cost->lxx, cost->luu, cost->lux, mu, flags,
                          out->gain, out->k, out->dv, out->status, out->vx, out->vxx};
   return physics_launch(p, rsr::OP_LQR_BACKWARD, x, "rsr_physics_lqr_backward");
+}
+
+// One launch, one wave per slot (rsr_kalman.hpp).  The handle gives nv, nu, the device and the family's entry; none of its buffers is used.
+extern "C" int rsr_physics_kalman(rsr_physics* p, int M, int T, const float* columns, int row_stride, int ny, const rsr_kalman_in* in,
+                                  int flags, const rsr_kalman_out* out, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_kalman: null handle");
+  if (!columns || !in || !out) return fail(RSR_ERR_ARG, "rsr_physics_kalman: null columns, in or out");
+  if (!in->dy || !in->r || !in->q || !in->P0) return fail(RSR_ERR_ARG, "rsr_physics_kalman: in needs dy, r, q and P0 (only x0 may be null)");
+  if (!out->xf || !out->status) return fail(RSR_ERR_ARG, "rsr_physics_kalman: out needs xf and status");
+  if ((out->xs || out->ps) && !out->pf) return fail(RSR_ERR_ARG, "rsr_physics_kalman: xs and ps need pf");
+  if (out->ps && !out->xs) return fail(RSR_ERR_ARG, "rsr_physics_kalman: ps needs xs");
+  if (M < 1 || T < 1) return fail(RSR_ERR_ARG, "rsr_physics_kalman: M and T must be >= 1");
+  const rsr_dims& d = p->b->model->dims;
+  if (ny < 1 || ny > RSR_MAX_SENSORDATA) return fail(RSR_ERR_ARG, "rsr_physics_kalman: ny must lie in [1, " + std::to_string(RSR_MAX_SENSORDATA) + "]");
+  if (row_stride < 2 * d.nv + ny) return fail(RSR_ERR_ARG, "rsr_physics_kalman: row_stride must be >= 2 nv + ny");
+  if (flags != 0) return fail(RSR_ERR_ARG, "rsr_physics_kalman: unknown flag bits");
+  if ((int64_t)M * ((int64_t)T + 1) > INT32_MAX) return fail(RSR_ERR_ARG, "rsr_physics_kalman: M x (T + 1) must stay below 2^31");
+  rsr::Launch x = physics_args(p, nullptr, nullptr, M, 1, hip_stream);
+  x.ph.kf = rsr::KalmanArgs{columns, row_stride, T, ny, in->dy, in->r, in->q, in->x0, in->P0, out->xf, out->pf, out->xs, out->ps,
+                            out->nll, out->status};
+  return physics_launch(p, rsr::OP_KALMAN, x, "rsr_physics_kalman");
 }
 
 // One launch, one wave per slot (rsr_ik.hpp).  The task table goes by value; none of the handle's buffers is used.

@@ -179,6 +179,17 @@ struct CostArgs {
   float* ctrl_out;      // [M][K][T][nu] the applied ctrl, or null (sw.ctrl_out stays null: the cost stage writes the row)
 };
 static_assert(sizeof(CostArgs) == 13 * sizeof(void*), "cost_kernel's kernel-argument block");
+// rsr_physics_kalman (rsr_kalman.hpp): the caller's buffers, every row indexed by slot (PhysLaunch::kf).  nx = 2 nv.
+struct KalmanArgs {
+  const float* columns; // [M][T][nx + nu][row_stride]: of row j < nx the entries i < nx (A_t[i][j]) and nx + r, r < ny (C_t[r][j])
+  int row_stride, T, ny;
+  const float *dy, *r, *q;            // [M][T][ny], [M][T][ny] (+inf: missing), [M][T][nx]
+  const float* x0;      // [M][nx], or null: zeros
+  const float* P0;      // [M][nx][nx]
+  float *xf, *pf;       // [M][T+1][nx], [M][T+1][nx][nx] (null = not recorded; needed by the smoother)
+  float *xs, *ps;       // [M][T+1][nx] (null: no smoother), [M][T+1][nx][nx] (null = not recorded)
+  float *nll, *status;  // [M] (null = not recorded), [M][2]
+};
 
 // The physics ops of a family unit's launch entry (launch_physics, rsr_physics_kernels.hpp).  An entry takes its op as an int, of
 // enum Op (rsr_launch.hpp) or of this enum: these start above enum Op's, so that no value names two ops.  A new op is a member
@@ -200,6 +211,7 @@ enum PhysOp {
   OP_LQR_BACKWARD,       // rsr_physics_lqr_backward (lq): grid = slots; reads neither the model nor the record
   OP_IK,                 // rsr_physics_ik (ik): grid = slots, the env of a slot from ik.ids
   OP_COST_ROLLOUTS,      // rsr_physics_cost_rollouts (p, r, sw, cs): grid and rows as OP_PHYS_SWEEP's
+  OP_KALMAN,             // rsr_physics_kalman (kf): grid = slots; reads neither the model nor the record
 };
 // The physics ops' arguments (Launch::ph), one field per op that needs its own
 struct PhysLaunch {
@@ -215,6 +227,7 @@ struct PhysLaunch {
   LqrArgs lq;           // OP_LQR_BACKWARD
   IkArgs ik;            // OP_IK
   CostArgs cs;          // OP_COST_ROLLOUTS (with p, r and sw)
+  KalmanArgs kf;        // OP_KALMAN
   Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
 };
 

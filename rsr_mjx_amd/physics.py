@@ -34,6 +34,12 @@
                                                                                           (A_t, B_t and a quadratic cost model in,
                                                                                            the gains of feedback_rollouts out; one
                                                                                            launch, nothing of the env is read)
+    a Kalman filter / RTS smoother over a log   ->  Physics.kalman_smooth(columns, dy, r, q, P0)
+                                                                                          (A_t, C_t of trajectory_fd and measured
+                                                                                           minus nominal sensordata in, filtered and
+                                                                                           smoothed state deviations out; one launch,
+                                                                                           nothing of the env is read;
+                                                                                           Physics.integrate_state adopts them)
     an IK library on top of mj_jacSite          ->  Physics.ik(sites, target_pos, target_quat=None)
                                                                                           (which qpos puts these sites there:
                                                                                            damped least squares, M problems in one
@@ -833,6 +839,98 @@ class Physics:
                                                        C.c_void_p(mu_t.data_ptr()), _lib.LQR_REG_STATE if state_reg else 0,
                                                        C.byref(ptrs), self._stream()))
         return res
+
+    def kalman_smooth(self, columns, dy, r, q, P0, x0=None, smooth: bool = True, covariances: bool = False,
+                      out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """A linear time-varying Kalman filter with a Rauch-Tung-Striebel smoother over a log, the consumer of trajectory_fd's
+        sensor Jacobians: M independent problems, one launch with one wave per slot and the T steps inside it.  The state is
+        the deviation dx_t from the nominal run in the tangent space, nx = 2 nv (an error-state / linearised EKF):
+        dx_{t+1} = A_t dx_t + w_t, dy_t = C_t dx_t + v_t.  Nothing of the env is read: the handle gives nv and nu, and M is
+        whatever the buffers hold.  All float32 tensors on the env's device, contiguous, ncol = nx + nu:
+        columns [M, T, ncol, w]: trajectory_fd(...)["columns"] as it is, ny = w - nx sensor entries (1 <= ny <= 64; the B and D
+        rows are never read); dy [M, T, ny]: the measured sensordata minus the nominal run's (sample_rollouts with K = 1 on the
+        same record); r [M, T, ny] or [M, ny]: the measurement variances, +inf where a sample is missing (skipped exactly);
+        q [M, T, nx] or [M, nx]: the process-noise variances, finite and >= 0; P0 [M, nx, nx], symmetric, and x0 [M, nx] or None
+        (zeros): the prior on dx_0.  The measurement update takes one sensor entry at a time (R is diagonal), so no ny x ny
+        matrix is factorised.  Returns xf [M, T+1, nx] and Pf [M, T+1, nx, nx] (row t: after step t's measurements; row T: a
+        prediction), nll [M] (the innovation negative log-likelihood), status [M, 2] (filter, smoother: -1, or the step that
+        failed: a variance r that is neither +inf nor finite and > 0, an innovation variance that is not finite and > 0, or a
+        Cholesky pivot of the smoother's predicted covariance that is; that slot stopped there with the rows before the failure
+        written, nll = 0 after a filter failure and no smoother; the other slots are unaffected) and, with `smooth`, xs
+        [M, T+1, nx], and Ps [M, T+1, nx, nx] with `covariances`.  `out`: caller-owned float32 tensors under those names to fill
+        instead of new ones.  A slot's result depends on that slot's inputs alone, bit for bit; smooth=False gives the same xf,
+        Pf and nll bit for bit.  Writes nothing else: adopt xs[:, 0] with integrate_state and set_state."""
+        import torch
+        who = "kalman_smooth"
+        d = self.dims
+        nv, nu = int(d.nv), int(d.nu)
+        nx, ncol = 2 * nv, 2 * nv + nu
+        if covariances and not smooth:
+            raise ValueError(f"{who}: covariances=True needs smooth=True")
+        self._f32(f"{who} expects columns as", columns, f"(M >= 1, T >= 1, {ncol}, {nx} < w <= {nx + _lib.MAX_SENSORDATA})",
+                  lambda t: t.dim() == 4 and t.shape[0] >= 1 and t.shape[1] >= 1 and t.shape[2] == ncol
+                  and nx < t.shape[3] <= nx + _lib.MAX_SENSORDATA, True)
+        M, T, w = int(columns.shape[0]), int(columns.shape[1]), int(columns.shape[3])
+        ny = w - nx
+        if M * (T + 1) >= 2 ** 31:
+            raise ValueError(f"{who}: M * (T + 1) must stay below 2^31")
+        self._f32(f"{who} expects dy as", dy, f"{(M, T, ny)} (M, T and ny as columns has them)", (M, T, ny), True)
+        wide = {}
+        for name, t, n in (("r", r, ny), ("q", q, nx)):
+            self._f32(f"{who} expects {name} as", t, f"{(M, T, n)} or {(M, n)}",
+                      lambda t, n=n: tuple(t.shape) in ((M, T, n), (M, n)), True)
+            wide[name] = t if t.dim() == 3 else t[:, None, :].expand(M, T, n).contiguous()
+        self._f32(f"{who} expects P0 as", P0, (M, nx, nx), (M, nx, nx), True)
+        if x0 is not None:
+            self._f32(f"{who} expects x0 as", x0, f"{(M, nx)}, or None", (M, nx), True)
+        oshapes = dict(xf=(M, T + 1, nx), Pf=(M, T + 1, nx, nx))
+        if smooth:
+            oshapes.update(xs=(M, T + 1, nx))
+        if covariances:
+            oshapes.update(Ps=(M, T + 1, nx, nx))
+        oshapes.update(nll=(M,), status=(M, 2))
+        res = self._outputs(who, oshapes, out, True, f" (smooth={smooth}, covariances={covariances})")
+        ptrs = _lib.KalmanOut(**{dict(Pf="pf", Ps="ps").get(f, f): t.data_ptr() for f, t in res.items()})
+        ins = _lib.KalmanIn(dy.data_ptr(), wide["r"].data_ptr(), wide["q"].data_ptr(), None if x0 is None else x0.data_ptr(), P0.data_ptr())
+        self._held[who] = (columns, dy, r, q, wide["r"], wide["q"], P0, x0)
+        _lib.check(_lib.lib().rsr_physics_kalman(self._h, M, T, C.c_void_p(columns.data_ptr()), w, ny, C.byref(ins), 0,
+                                                 C.byref(ptrs), self._stream()))
+        return res
+
+    def integrate_state(self, qpos, qvel, dx):
+        """A tangent-space deviation applied to a state: (qpos', qvel') = (mj_integratePos(qpos, dx[..., :nv]) with dt = 1,
+        qvel + dx[..., nv:]), in torch, for any leading dims (qpos [..., nq], qvel [..., nv], dx [..., 2 nv], the same leading
+        dims).  A free joint's rotation dofs are a body-frame rotation vector, q' = q * exp(v / 2), and its quaternion is
+        normalised.  It is how a smoothed dx_0 of kalman_smooth becomes the state set_state takes; nothing of the batch is read
+        but the model's joint table, and nothing is written."""
+        import torch
+        who = "integrate_state"
+        nq, nv = int(self.dims.nq), int(self.dims.nv)
+        for name, t, n in (("qpos", qpos, nq), ("qvel", qvel, nv), ("dx", dx, 2 * nv)):
+            if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() < 1 or t.shape[-1] != n:
+                raise ValueError(f"{who} expects {name} as a floating-point tensor of shape (..., {n})")
+        if not (qpos.shape[:-1] == qvel.shape[:-1] == dx.shape[:-1]):
+            raise ValueError(f"{who}: qpos, qvel and dx must have the same leading dims")
+        A = self.env.sys.arrays
+        dq = dx[..., :nv]
+        out = qpos.clone()
+        for j in range(len(A["jnt_type"])):
+            jt, qa, da = int(A["jnt_type"][j]), int(A["jnt_qposadr"][j]), int(A["jnt_dofadr"][j])
+            if jt == 0:                                   # free: translation, then q * exp(v / 2)
+                out[..., qa:qa + 3] = qpos[..., qa:qa + 3] + dq[..., da:da + 3]
+                v = dq[..., da + 3:da + 6]
+                ang = v.norm(dim=-1, keepdim=True)
+                h = 0.5 * ang
+                f = torch.where(ang > 0, torch.sin(h) / torch.where(ang > 0, ang, torch.ones_like(ang)), torch.full_like(ang, 0.5))
+                bw, bv = torch.cos(h), v * f
+                aw, av = qpos[..., qa + 3:qa + 4], qpos[..., qa + 4:qa + 7]
+                qn = torch.cat([aw * bw - (av * bv).sum(-1, keepdim=True), aw * bv + bw * av + torch.linalg.cross(av, bv, dim=-1)], dim=-1)
+                out[..., qa + 3:qa + 7] = qn / qn.norm(dim=-1, keepdim=True)
+            elif jt in (2, 3):                            # slide, hinge
+                out[..., qa] = qpos[..., qa] + dq[..., da]
+            else:
+                raise ValueError(f"{who}: joint {j} has type {jt}; only free, slide and hinge joints are supported")
+        return out, qvel + dx[..., nv:]
 
     def ik(self, sites, target_pos, target_quat=None, pos_weight=1.0, rot_weight=None, dofs=None, qpos0=None, damping=1e-3,
            iters: int = 20, tol_pos: float = 1e-4, tol_rot: float = 1e-3, max_step: float = 0.3, limits: bool = True,
