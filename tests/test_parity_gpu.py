@@ -2,9 +2,13 @@
 
 Tolerances are per-field envelopes derived from what was measured on the hardware -- max = 5 x the measured maximum, p99 = 3 x
 the measured 99 % quantile; tests/parity_envelopes.py states the clauses for large and small samples and what the numbers mean
-against the north_star's 1e-5: exact for done / steps / truncation / time and PRNG-only quantities; obs, reward,
-metrics, xpos, info within 1e-5 on every env in a rollout; qvel / qacc_warmstart as documented deviations with quantile
-bounds.  Parity with the reference (MJX) itself is unpinned -- see oracle/rsr_oracle.c.
+against the north_star's 1e-5: exact for done / steps / truncation / time and PRNG-only quantities; qvel / qacc_warmstart as
+documented deviations with quantile bounds.  For the Airbot rollout fields (obs, reward, metrics, xpos, info) the committed
+envelopes do NOT say "within 1e-5 on every env": they bound the whole step, physics included, at e.g. 0.66 for the cube's
+rollout reward and 1.2e-2 for its obs, and `frac` lets 1 % of the envs exceed 1e-5 -- what they bound is that the HIP stepper
+stays as close to the fp32 oracle as was measured, outliers of the chaotic contact physics included.  The env logic itself
+(thresholds, gates, clamps, wrappers) is pinned by tests/test_airbot_epilogue_gpu.py, which takes the physics as an input and
+holds every branch bitwise or to a few ulp.  Parity with the reference (MJX) itself is unpinned -- see oracle/rsr_oracle.c.
 """
 import os
 
