@@ -4,10 +4,9 @@
 // system identification minimises: a weighted least-squares tracking cost per (slot, sample), with nothing of the trajectory
 // written to memory unless the caller asks for it.
 //
-// One wave per (slot, sample): sweep_kernel's launch shape and loop (rsr_sweep.hpp), restated statement for statement as that
-// kernel restates sample_kernel, with one stage more.  At the end of control step t, after sensor_stage and the rows of the
-// trajectory and before the next ctrl row overwrites s.ctrl, cost_stage takes the residuals against row (slot, t) of the
-// references, one lane per entry:
+// cost_stage is what sampled_kernel's COST switch adds to the (slot, sample) loop (rsr_sample.hpp, which includes this header).  At
+// the end of control step t, after sensor_stage and the rows of the trajectory and before the next ctrl row overwrites s.ctrl,
+// it takes the residuals against row (slot, t) of the references, one lane per entry:
 //   dq = qpos (-) qpos_ref   differentiate_pos with zero_at_equal, negated as feedback_ctrl negates it     lane < NV
 //   dv = qvel - qvel_ref                                                                                   lane < NV
 //   du = s.ctrl - ctrl_ref   the control that was applied, after the gain rows and the clamp                lane < NU
@@ -29,7 +28,7 @@
 
 namespace rsr {
 
-// LDS of a cost_kernel workgroup: Smem<C>, then the accumulators cost | qpos | qvel | ctrl | sensor term (padded to 8 floats)
+// LDS of a cost-rollout workgroup (sampled_kernel<.., CostOp>): Smem<C>, then the accumulators cost | qpos | qvel | ctrl | sensor term (padded to 8 floats)
 template <class C>
 constexpr size_t cost_acc_offset() { return (sizeof(Smem<C>) + 15) & ~size_t(15); }
 template <class C>
@@ -81,76 +80,6 @@ __device__ __forceinline__ void cost_stage(const Hot& hot, const Smem<C>& s, flo
   if (last && lane == 0) {
     c.cost[b] = acc[0];
     if (c.terms) { c.terms[4 * b] = acc[1]; c.terms[4 * b + 1] = acc[2]; c.terms[4 * b + 2] = acc[3]; c.terms[4 * b + 3] = acc[4]; }
-  }
-}
-
-// Workgroup b: slot b / K (env p.ids[slot], or slot), sample b % K, K = sw.K.  p, r, sw: as sweep_kernel takes them (sw.ctrl_out is
-// null; every pointer of r may be).  c: the references and weights [M][T][w] by slot, and the outputs by (slot, sample).
-// Ap: none, or Applied: the env's applied forces enter every pass, held for all T control steps.
-template <class C, int WAVES, class... Ap>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
-void cost_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs p, RollArgs r, SweepArgs sw, CostArgs c, Ap... ap) {
-  static_assert(4 * WAVES * cost_lds_bytes<C>() <= 160 * 1024, "4 x WAVES workgroups share a CU's LDS");
-  const DModel& m = *mp;
-  const Hot hot = make_hot(m);
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  Smem<C>& s = *reinterpret_cast<Smem<C>*>(smem_raw);
-  float* acc = reinterpret_cast<float*>(smem_raw + cost_acc_offset<C>());
-  const int K = sw.K;
-  const int b = (int)blockIdx.x, slot = b / K, lane = threadIdx.x;
-  const int e = p.ids ? p.ids[slot] : slot;
-  if (e < 0 || e >= a.n) return;                                // (an id out of range runs nothing)
-  const float* rec = a.state + (size_t)e * L.rec;
-  const auto stage = force_stage<C>(e, ap.xfrc..., ap.qfrc...);
-  PROF_DECL
-  // the record load of rollout_kernel, written out
-  for (int t = lane; t < C::NQ; t += 64) s.qpos[t] = rec[L.qpos + t];
-  float warm = 0.0f;
-  if (lane < C::NV) { s.qvel[lane] = rec[L.qvel + lane]; warm = rec[L.warm + lane]; }
-  float time = rec[L.time];
-  load_overrides<C>(m, s, a, e, lane);
-  overlay_leaves<C>(m, s, sw, b, lane);          // the sample's leaves over the env's own (same lanes, same words: no fence between)
-  if constexpr (C::XFRC) {        // the Go2 single-body kick path idle, as in the physics kernels
-    if (lane == 0) { s.acc_body = m.site_bodyid[m.env_ids[0]]; s.xfrc_body = 0; s.xfrc[0] = s.xfrc[1] = s.xfrc[2] = 0.0f; }
-  }
-  if (lane < 8) acc[lane] = 0.0f;                // (published to lane 0 by the fence below)
-  float Mrow[C::NV];
-  FwdOut<C> f;
-  const int nsd = p.sens.nsd;
-  // the slot's ctrl rows, or the sample's (uniform over the launch)
-  const size_t cb = sw.ctrl_per_sample ? (size_t)b : (size_t)slot;
-  // one loop over the T * nsteps substeps, the control-step boundary a wave-uniform branch, as in rollout_kernel
-  if (lane < C::NU) s.ctrl[lane] = r.ctrl[cb * r.T * C::NU + lane];
-  if (sw.fb_gain) feedback_ctrl<C>(m, hot, s, sw, (sw.fb_per_sample ? (size_t)b : (size_t)slot) * r.T, (size_t)b * r.T, lane);
-  WSYNC();
-  const int total = r.T * p.nsteps;              // (T * nsteps < 2^31: rsr_physics_cost_rollouts)
-  int t = 0, fr = 0;
-  for (int k = 0; k < total; ++k) {
-    const int lane_s = lrec_lane(lane);        // see step_kernel
-    forward<C>(m, hot, s, lane_s, Mrow, warm, f, nullptr PROF_PASS, stage);
-    integrate<C>(m, hot, s, lane_s, Mrow, f PROF_PASS);
-    time += hot.timestep;
-    if (++fr < p.nsteps) continue;
-    fr = 0;
-    WSYNC();
-    const int lt = lrec_lane(lane);            // opaque, as in sample_kernel: the rows' addresses are formed here, not kept across
-                                               // the solver
-    const size_t row = (size_t)b * r.T + t;
-    float sv = 0.0f;
-    if (nsd > 0) sv = sensor_stage<C>(m, s, lt, f.qacc, p.sens);      // (wave-uniform; no table: the stage is skipped)
-    if (r.qpos) for (int q = lt; q < C::NQ; q += 64) r.qpos[row * C::NQ + q] = s.qpos[q];
-    if (r.qvel && lt < C::NV) r.qvel[row * C::NV + lt] = s.qvel[lt];
-    if (r.time && lt == 0) r.time[row] = time;
-    if (r.aforce && lt < C::NU) r.aforce[row * C::NU + lt] = s.aforce[lt];
-    if (r.ncon && lt == 0) r.ncon[row] = (float)s.ncon;
-    if (r.sd && lt < nsd) r.sd[row * nsd + lt] = sv;
-    // s.ctrl still holds the control of this step: the next row is loaded below
-    cost_stage<C>(hot, s, acc, c, (size_t)slot * r.T + t, row, (size_t)b, t == r.T - 1, lt, sv, nsd);
-    if (++t < r.T) {
-      if (lt < C::NU) s.ctrl[lt] = r.ctrl[(cb * r.T + t) * C::NU + lt];
-      if (sw.fb_gain) feedback_ctrl<C>(m, hot, s, sw, (sw.fb_per_sample ? (size_t)b : (size_t)slot) * r.T + t, (size_t)b * r.T + t, lt);
-      WSYNC();
-    }
   }
 }
 

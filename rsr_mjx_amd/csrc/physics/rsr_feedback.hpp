@@ -1,9 +1,9 @@
 // rsr_feedback.hpp -- the control law of rsr_physics_feedback_rollouts (include/rsr_physics.h): affine state feedback computed on
-// the device at every control-step boundary of sweep_kernel (rsr_sweep.hpp), from the sample's own state in LDS:
+// the device at every control-step boundary of sampled_kernel's SWEEP switch (rsr_sample.hpp), from the sample's own state in LDS:
 //   u_j = ctrl_j + sum_i gain[j][i] (qpos (-) qpos_ref)_i + sum_i gain[j][nv + i] (qvel - qvel_ref)_i
 // with (-) in the tangent space of qpos (differentiate_pos of rsr_transition.hpp: MuJoCo's mj_differentiatePos).  What an iLQR
-// forward pass, MPPI with a feedback term and CEM over controller gains ask of a rollout.  A stage of its own header: the text
-// between overlay_leaves and sweep_kernel is pinned (tests/test_param_rollouts_api.py).
+// forward pass, MPPI with a feedback term and CEM over controller gains ask of a rollout.  A stage of its own header, called from the
+// kernel's SWEEP switch alone (tests/test_sampled_kernel_api.py).
 #pragma once
 #include "../rsr_launch.hpp"
 #include "rsr_transition.hpp"

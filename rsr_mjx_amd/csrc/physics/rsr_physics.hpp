@@ -112,7 +112,7 @@ struct InvArgs {
   const float* qacc;    // [N][nv] the accelerations, row e env e's
   int flags;            // RSR_INV_*
 };
-// The launch arguments of OP_PHYS_SWEEP (PhysLaunch::sw): what sweep_kernel (rsr_sweep.hpp) takes beside sample_kernel's arguments
+// The launch arguments of OP_PHYS_SWEEP (PhysLaunch::sw): what sampled_kernel<.., SweepOp> (rsr_sample.hpp) takes beside SampleOp's arguments
 // (PhysArgs p, RollArgs r, and Applied while the forces are on).
 struct SweepArgs {
   const float* leaf[RSR_DR_COUNT];   // per-sample leaves [M][K][width], indexed by enum rsr_dr_field; null: the env's own leaf
@@ -167,7 +167,7 @@ struct IkArgs {
   float tol_pos, tol_rot, max_step;
 };
 static_assert(sizeof(IkArgs) == 64 + 12 * RSR_MAX_JAC_SITES + 32, "ik_kernel's kernel-argument block");
-// rsr_physics_cost_rollouts (rsr_cost.hpp): what cost_kernel takes beside sweep_kernel's arguments (PhysLaunch::cs).  The
+// rsr_physics_cost_rollouts (rsr_cost.hpp): what sampled_kernel<.., CostOp> takes beside SweepOp's arguments (PhysLaunch::cs).  The
 // references and weights are rows [M][T][w] by slot, shared by a slot's K samples; the outputs are rows by (slot, sample).
 struct CostArgs {
   const float *qpos_ref, *qvel_ref, *ctrl_ref, *sensor_ref;   // [M][T][nq | nv | nu | nsd]; qvel / ctrl / sensor null: zeros
@@ -178,7 +178,7 @@ struct CostArgs {
   float* dx;            // [M][K][T][2 nv] dq | dv, or null
   float* ctrl_out;      // [M][K][T][nu] the applied ctrl, or null (sw.ctrl_out stays null: the cost stage writes the row)
 };
-static_assert(sizeof(CostArgs) == 13 * sizeof(void*), "cost_kernel's kernel-argument block");
+static_assert(sizeof(CostArgs) == 13 * sizeof(void*), "the cost op's kernel-argument block");
 // rsr_physics_kalman (rsr_kalman.hpp): the caller's buffers, every row indexed by slot (PhysLaunch::kf).  nx = 2 nv.
 struct KalmanArgs {
   const float* columns; // [M][T][nx + nu][row_stride]: of row j < nx the entries i < nx (A_t[i][j]) and nx + r, r < ny (C_t[r][j])

@@ -1,7 +1,7 @@
 // rsr_physics_kernels.hpp -- the physics-level kernels (include/rsr_physics.h): each family unit instantiates them for its Dims,
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
 // forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp), constraint_kernel (rsr_constraint.hpp), transition_kernel
-// (rsr_transition.hpp), inverse_kernel (rsr_inverse.hpp), sample_kernel (rsr_sample.hpp), sweep_kernel (rsr_sweep.hpp), cost_kernel (rsr_cost.hpp) and the two
+// (rsr_transition.hpp), inverse_kernel (rsr_inverse.hpp), sampled_kernel (rsr_sample.hpp: one body, three ops) and the two
 // of rsr_trajectory.hpp, nominal_kernel and trajectory_fd_kernel, lqr_kernel (rsr_lqr.hpp) and kalman_kernel (rsr_kalman.hpp), which run
 // no physics and take of a family only nv and nu, and ik_kernel (rsr_ik.hpp), which runs the kinematics and mass-matrix stages
 // alone; all but dynamics_kernel, inverse_kernel, lqr_kernel, kalman_kernel and ik_kernel are instantiated plain and with applied forces:
@@ -187,8 +187,8 @@ int launch_physics(int op, const Launch& x) {
   if (op == OP_LQR_BACKWARD) return go(lqr_kernel<C, WAVES>, ph.lq);      // rsr_physics_lqr_backward (rsr_lqr.hpp)
   if (op == OP_IK) return go(ik_kernel<C, WAVES>, ph.ik);                 // rsr_physics_ik (rsr_ik.hpp)
   if (op == OP_KALMAN) return go(kalman_kernel<C, WAVES>, ph.kf);         // rsr_physics_kalman (rsr_kalman.hpp)
-  // rsr_physics_cost_rollouts (rsr_cost.hpp)
-  if (op == OP_COST_ROLLOUTS) return ap ? go(cost_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.sw, ph.cs, ph.ap) : go(cost_kernel<C, WAVES>, ph.p, ph.r, ph.sw, ph.cs);
+  // rsr_physics_cost_rollouts (rsr_sample.hpp, rsr_cost.hpp)
+  if (op == OP_COST_ROLLOUTS) return ap ? go(sampled_kernel<C, WAVES, CostOp, Applied>, ph.p, ph.r, CostOp::Args{ph.sw, ph.cs}, ph.ap) : go(sampled_kernel<C, WAVES, CostOp>, ph.p, ph.r, CostOp::Args{ph.sw, ph.cs});
   switch (op) {
     case OP_PHYS_STEP: return ap ? go(physics_kernel<C, true, WAVES, Applied>, ph.p, ph.ap) : go(physics_kernel<C, true, WAVES>, ph.p);
     case OP_PHYS_FORWARD: return ap ? go(physics_kernel<C, false, WAVES, Applied>, ph.p, ph.ap) : go(physics_kernel<C, false, WAVES>, ph.p);
@@ -197,8 +197,8 @@ int launch_physics(int op, const Launch& x) {
     case OP_PHYS_DYNAMICS: return go(dynamics_kernel<C, WAVES>, ph.d);      // (applied forces enter none of its outputs, nor the inverse's)
     case OP_PHYS_CONSTRAINT: return ap ? go(constraint_kernel<C, WAVES, Applied>, ph.c, ph.ap) : go(constraint_kernel<C, WAVES>, ph.c);
     case OP_PHYS_INVERSE: return go(inverse_kernel<C, WAVES>, ph.inv);
-    case OP_PHYS_SAMPLE: return ap ? go(sample_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.K, ph.ap) : go(sample_kernel<C, WAVES>, ph.p, ph.r, ph.K);
-    case OP_PHYS_SWEEP: return ap ? go(sweep_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.sw, ph.ap) : go(sweep_kernel<C, WAVES>, ph.p, ph.r, ph.sw);
+    case OP_PHYS_SAMPLE: return ap ? go(sampled_kernel<C, WAVES, SampleOp, Applied>, ph.p, ph.r, ph.K, ph.ap) : go(sampled_kernel<C, WAVES, SampleOp>, ph.p, ph.r, ph.K);
+    case OP_PHYS_SWEEP: return ap ? go(sampled_kernel<C, WAVES, SweepOp, Applied>, ph.p, ph.r, ph.sw, ph.ap) : go(sampled_kernel<C, WAVES, SweepOp>, ph.p, ph.r, ph.sw);
     default: return -1;
   }
 }

@@ -2,7 +2,7 @@
 // rsr_physics_transition_fd at every control step of a nominal trajectory, what the backward pass of iLQR, a time-varying LQR,
 // linearised MPC and an EKF smoother over a log ask of the model.
 //
-// Two launches on the caller's stream.  nominal_kernel, one wave per slot, runs the trajectory once: sweep_kernel's record load and
+// Two launches on the caller's stream.  nominal_kernel, one wave per slot, runs the trajectory once: sampled_kernel's record load and
 // flattened loop without the overlay and feedback stages, so it is bit for bit the K = 1 run of rsr_physics_sample_rollouts.
 // Before control step t it stores qpos | qvel | qacc_warmstart to row (slot, t) of the handle's nominal scratch: what the record
 // would hold after t calls of rsr_physics_step.  trajectory_fd_kernel, one wave per (slot, t, column), is then the body of
@@ -74,7 +74,7 @@ void nominal_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArg
     if (++fr < p.nsteps) continue;
     fr = 0;
     WSYNC();
-    const int lt = lrec_lane(lane);            // opaque, as in sample_kernel: the rows' addresses are formed here, not kept across
+    const int lt = lrec_lane(lane);            // opaque, as in sampled_kernel: the rows' addresses are formed here, not kept across
                                                // the solver
     keep(++t, lt, warm);
     if (t < tj.T) {

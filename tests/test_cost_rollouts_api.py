@@ -111,46 +111,25 @@ def test_the_op_is_an_ordinary_op_and_the_kernel_a_header_of_its_own():
     lp = kernels[kernels.index("int launch_physics("):]
     assert "const size_t lds = op == OP_COST_ROLLOUTS ? cost_lds_bytes<C>() : op == OP_IK ? ik_lds_bytes<C>() :" in lp
     assert "op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>)" in lp and lp.count("hipLaunchKernelGGL(") == 1
-    assert ("if (op == OP_COST_ROLLOUTS) return ap ? go(cost_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.sw, ph.cs, ph.ap) : "
-            "go(cost_kernel<C, WAVES>, ph.p, ph.r, ph.sw, ph.cs);") in lp
+    assert ("if (op == OP_COST_ROLLOUTS) return ap ? go(sampled_kernel<C, WAVES, CostOp, Applied>, ph.p, ph.r, CostOp::Args{ph.sw, ph.cs}, ph.ap) : "
+            "go(sampled_kernel<C, WAVES, CostOp>, ph.p, ph.r, CostOp::Args{ph.sw, ph.cs});") in lp
     assert lp.index("if (op == OP_COST_ROLLOUTS)") < lp.index("switch (op)") and "case OP_COST" not in lp
-    assert lp.count("cost_kernel") == 2 and lp.count("sweep_kernel") == 2
+    assert lp.count("sampled_kernel<C, WAVES, CostOp") == 2 and lp.count("sampled_kernel<C, WAVES, SweepOp") == 2 and lp.count("sampled_kernel") == 6
+    # the two argument structs travel as one, in the order and with the bytes they had as two kernel arguments
+    assert "struct CostOp { struct Args { SweepArgs sw; CostArgs c; }; };" in re.sub(r"\s+", " ", _read("physics", "rsr_sample.hpp"))
     # nothing directly under csrc/ knows; the hashed sources are the parent's
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
             text = open(os.path.join(CSRC, f)).read()
-            assert "cost_kernel" not in text and "CostArgs" not in text and "OP_COST" not in text and "rsr_cost" not in text, f
+            assert "sampled_kernel" not in text and "CostOp" not in text and "CostArgs" not in text and "OP_COST" not in text and "rsr_cost" not in text, f
     import bench
     import parity_envelopes as PE
     assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
-    # the kernel: sweep_kernel's loop with one stage more, the stages it shares called, not restated
-    kern = _read("physics", "rsr_cost.hpp")
-    code = re.sub(r"//.*", "", kern)
-    assert "void cost_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a, PhysArgs p, RollArgs r, SweepArgs sw, CostArgs c, Ap... ap)" in code
-    assert "template <class C, int WAVES, class... Ap>" in code and "__launch_bounds__(64)" in code and '#include "rsr_sweep.hpp"' in code
-    assert code.count("forward<C>(") == 1 and code.count("integrate<C>(") == 1 and code.count("differentiate_pos<C>(") == 1
-    for k in ("overlay_leaves<C>(m, s, sw, b, lane)", "load_overrides<C>(m, s, a, e, lane)", "sensor_stage<C>(", "force_stage<C>(e, ", "wave_sum(",
-              "lrec_lane(lane)", "cost_lds_bytes<C>()", "#pragma clang fp contract(off)", "e < 0 || e >= a.n",
-              "static_assert(4 * WAVES * cost_lds_bytes<C>() <= 160 * 1024"):
-        assert k in code, k
-    for k in ("void overlay_leaves(", "void feedback_ctrl(", "float differentiate_pos(", "float wave_sum(", "asm", "atomic", "store_pipeline", "store_side",
-              "hipMalloc", "p.sd", "p.out", "sw.ctrl_out"):
-        assert k not in code, k
-    assert "const float* rec = a.state + (size_t)e * L.rec;" in code and not re.search(r"\brec\[[^\]]*\]\s*=[^=]", code)
-    k = code[code.index("void cost_kernel("):]
-    calls = [ln.strip() for ln in k.splitlines() if "feedback_ctrl<C>(" in ln]
-    assert len(calls) == 2 and all(ln.startswith("if (sw.fb_gain) feedback_ctrl<C>(m, hot, s, sw, ") for ln in calls)
-    # the stage sits after the sensors and the trajectory rows and ahead of the next ctrl row
-    assert k.index("sensor_stage<C>(") < k.index("r.sd[row * nsd + lt] = sv;") < k.index("cost_stage<C>(") < k.index("if (++t < r.T)") \
-        < k.index("s.ctrl[lt] = r.ctrl[")
-    # the accumulators are LDS words of lane 0, not registers carried across forward<C>
-    stage = code[code.index("void cost_stage("):code.index("void cost_kernel(")]
-    assert "if (lane == 0) acc[0] = acc[0] + ct;" in stage and "float* acc = reinterpret_cast<float*>(smem_raw + cost_acc_offset<C>());" in k
-    stores = set(re.findall(r"\b(c\.\w+)\[[^\]]*\] = ", stage))
-    assert stores == {"c.cost", "c.step_cost", "c.terms", "c.dx", "c.ctrl_out"}, stores
+    # the stage and the accumulators' place are a header of their own; the kernel's text: tests/test_sampled_kernel_api.py
+    assert "void cost_stage(" in _read("physics", "rsr_cost.hpp") and "cost_stage<C>(" in _read("physics", "rsr_sample.hpp")
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     sec = design[design.index("### 4q."):]
-    for word in ("cost_kernel", "cost_stage", "sweep_kernel", "wave_sum", "cost_lds_bytes", "VGPRs", "SGPR", "scratch", "cost_rollout_rates"):
+    for word in ("sampled_kernel", "CostOp", "cost_stage", "SweepOp", "wave_sum", "cost_lds_bytes", "VGPRs", "SGPR", "scratch", "cost_rollout_rates"):
         assert word in sec, word
     assert design.index("### 4p.") < design.index("### 4q.")
     assert "cost_rollouts(" in open(os.path.join(ROOT, "README.md")).read()

@@ -102,25 +102,19 @@ def test_the_stage_is_a_header_of_its_own_called_twice():
     hdr = _read("physics", "rsr_physics.hpp")
     for k in ("const float* fb_gain;", "const float* fb_qpos;", "const float* fb_qvel;", "float* ctrl_out;", "int fb_per_sample;", "int fb_clamp;"):
         assert k in hdr, k
-    kern = re.sub(r"//.*", "", _read("physics", "rsr_sweep.hpp"))
-    assert '#include "rsr_feedback.hpp"' in kern
-    calls = [ln.strip() for ln in kern.splitlines() if "feedback_ctrl<C>(" in ln]
-    assert len(calls) == 2 and all(ln.startswith("if (sw.fb_gain) feedback_ctrl<C>(m, hot, s, sw, ") for ln in calls)
-    # the first after the first ctrl load and ahead of its fence, the second inside the boundary's `if (++t < r.T)`
-    k = kern[kern.index("void sweep_kernel("):]
-    first, second = k.index(calls[0]), k.index(calls[1])
-    assert k.index("s.ctrl[lane] = r.ctrl[") < first < k.index("const int total") and k.index("if (++t < r.T)") < k.index("s.ctrl[lt] = r.ctrl[") < second
-    assert "(size_t)b * r.T + t, lt);" in calls[1] and "(size_t)b * r.T, lane);" in calls[0]
-    assert calls[0].count("sw.fb_per_sample ? (size_t)b : (size_t)slot") == 1 == calls[1].count("sw.fb_per_sample ? (size_t)b : (size_t)slot")
+    # the two calls, each under `if (sw.fb_gain)` inside the kernel's SWEEP switch: tests/test_sampled_kernel_api.py
+    assert '#include "rsr_feedback.hpp"' in _read("physics", "rsr_sweep.hpp")
+    kern = re.sub(r"//.*", "", _read("physics", "rsr_sample.hpp"))
+    assert len(re.findall(r"^\s*if \(sw\.fb_gain\) feedback_ctrl<C>\(m, hot, s, sw, ", kern, re.M)) == 2 == kern.count("feedback_ctrl")
     # the family units and the other ops' headers do not know
-    for f in ("rsr_physics_kernels.hpp", "rsr_sample.hpp", "rsr_transition.hpp"):
+    for f in ("rsr_physics_kernels.hpp", "rsr_transition.hpp", "rsr_inverse.hpp"):
         assert "feedback" not in _read("physics", f).lower(), f
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
             assert "feedback" not in open(os.path.join(CSRC, f)).read().lower(), f
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     sec = design[design.index("### 4k."):]
-    for word in ("feedback_ctrl", "sweep_kernel", "differentiate_pos", "VGPRs", "feedback_rollout_rates"):
+    for word in ("feedback_ctrl", "sampled_kernel", "differentiate_pos", "VGPRs", "feedback_rollout_rates"):
         assert word in sec, word
 
 

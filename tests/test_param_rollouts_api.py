@@ -1,6 +1,6 @@
 """Parameter rollouts of the physics layer (rsr_physics_param_rollouts, Physics.param_rollouts, tuning.RolloutLoss), host side
 only: the ABI, the launch as an op of the physics layer, the Python surface and the tuning helper's reduction.
-The kernel is covered by tests/test_param_rollouts_gpu.py."""
+The kernel's text is covered by tests/test_sampled_kernel_api.py, the kernel by tests/test_param_rollouts_gpu.py."""
 import ctypes as C
 import inspect
 import os
@@ -94,13 +94,15 @@ def test_the_launch_is_an_ordinary_op():
     phys = _read("physics", "rsr_physics.hpp")
     assert "struct SweepArgs" in phys and "const float* leaf[RSR_DR_COUNT];" in phys
     assert re.search(r"\bSweepArgs sw;", re.search(r"struct PhysLaunch \{(.*?)\};", phys, re.S).group(1))
-    # the op's own case, up to the next label: its kernel, plain and applied, with p, r and sw, and no other kernel
+    # the op's own case, up to the next label: the one (slot, sample) kernel as this op's, plain and applied, with p, r and sw,
+    # and no other kernel or op
     kernels = _read("physics", "rsr_physics_kernels.hpp")
     assert '#include "rsr_sweep.hpp"' in kernels
     lp = kernels[kernels.index("int launch_physics("):]
     case = re.search(r"case OP_PHYS_SWEEP:(.*?)\n\s*(?:case |default:)", lp, re.S).group(1)
-    assert case.count("sweep_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.sw, ph.ap)") == 1 and case.count("sweep_kernel<C, WAVES>, ph.p, ph.r, ph.sw)") == 1
-    assert re.findall(r"\b\w+_kernel\b", case) == ["sweep_kernel"] * 2 and lp.count("sweep_kernel") == 2
+    assert case.count("sampled_kernel<C, WAVES, SweepOp, Applied>, ph.p, ph.r, ph.sw, ph.ap)") == 1 and case.count("sampled_kernel<C, WAVES, SweepOp>, ph.p, ph.r, ph.sw)") == 1
+    assert re.findall(r"\b\w+_kernel\b", case) == ["sampled_kernel"] * 2 and lp.count("SweepOp") == 2 and re.findall(r"\b\w+Op\b", case) == ["SweepOp"] * 2
+    assert lp.count("sampled_kernel") == 6                              # three ops, plain and applied
     assert lp.index("case OP_PHYS_SAMPLE:") < lp.index("case OP_PHYS_SWEEP:") < lp.index("default:")
     assert lp.count("hipLaunchKernelGGL(") == 1 and "op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>)" in lp
     for hdr in ("rsr_sweep.hpp", "rsr_feedback.hpp"):
@@ -109,7 +111,7 @@ def test_the_launch_is_an_ordinary_op():
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
             text = open(os.path.join(CSRC, f)).read()
-            assert "sweep_kernel" not in text and "rsr_sweep" not in text and "SweepArgs" not in text, f
+            assert "sampled_kernel" not in text and "SweepOp" not in text and "rsr_sweep" not in text and "SweepArgs" not in text, f
     import bench
     import parity_envelopes as PE
     assert PE.ENV["_provenance"]["csrc_sha16"] == bench.csrc_sha16()
@@ -118,41 +120,6 @@ def test_the_launch_is_an_ordinary_op():
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     sec = design[design.index("### 4j."):design.index("### 4k.")]
     assert "**Dispatch: an ordinary op.**" in sec and "OP_PHYS_SWEEP" in sec and "PhysLaunch::sw" in sec
-
-
-def test_the_kernel_is_the_sample_loop_with_one_stage_more():
-    kern = _read("physics", "rsr_sweep.hpp")
-    assert "void sweep_kernel(" in kern and "void overlay_leaves(" in kern
-    code = re.sub(r"//.*", "", kern)
-    assert code.count("forward<C>(") == 1 and code.count("integrate<C>(") == 1
-    for k in ("sensor_stage<C>(", "force_stage<C>(e, ", "load_overrides<C>(m, s, a, e, lane)", "overlay_leaves<C>(m, s, sw, b, lane)",
-              "lrec_lane(lane)", "if constexpr (C::XFRC)"):
-        assert k in code, k
-    assert code.index("load_overrides<C>(m, s, a, e, lane)") < code.index("overlay_leaves<C>(m, s, sw, b, lane)") < code.index("forward<C>(")
-    for k in ("store_pipeline", "store_side", "asm", "atomic"):
-        assert k not in kern, k
-    # the record is read only, and neither the side buffer nor the sensordata row is written
-    assert "const float* rec = a.state + (size_t)e * L.rec;" in code and not re.search(r"(?<!const )float\* rec\b", code)
-    assert not re.search(r"\brec\[[^\]]*\]\s*=[^=]", code) and "p.sd" not in code and "p.out" not in code
-    # one flattened loop, rows by workgroup and ctrl by slot or workgroup, in size_t
-    assert len(re.findall(r"\bfor \(int k = 0; k < total; \+\+k\)", code)) == 1 and "const int total = r.T * p.nsteps;" in code
-    assert "const size_t cb = sw.ctrl_per_sample ? (size_t)b : (size_t)slot;" in code and "const size_t row = (size_t)b * r.T + t;" in code
-    assert "slot = b / K" in code and "p.ids ? p.ids[slot] : slot" in code and "if (e < 0 || e >= a.n) return;" in code
-    # the overlay: all nine images, rows in size_t, friction through the geom slots, every load ahead of the first store
-    ov = code[code.index("void overlay_leaves("):code.index("void sweep_kernel(")]
-    for img in ("s.fric[", "s.mass[", "s.damp[", "s.floss[", "s.dx_ipos[", "s.dx_qpos0[", "s.dx_arma[", "s.dx_gain[", "s.dx_bias["):
-        assert ov.count(img) == 1, img
-    assert "(size_t)b * width" in ov and "m.geom_slot_ids[tt / 3]" in ov and "C::NGA == C::NG" in ov and "WSYNC" not in ov
-    first_store = min(m.start() for m in re.finditer(r"\bs\.\w+\[[^\]]*\] = ", ov))
-    last_load = max(m.start() for m in re.finditer(r"= p_\w+\[", ov))
-    assert last_load < first_store
-    # the statements the two kernels share are the same text
-    sample = re.sub(r"//.*", "", _read("physics", "rsr_sample.hpp"))
-    body = lambda c, name: [ln.strip() for ln in c[c.index(f"void {name}("):].splitlines() if ln.strip()]
-    sw, sa = body(code, "sweep_kernel"), body(sample, "sample_kernel")
-    extra = [ln for ln in sw if ln not in sa]
-    assert len(extra) <= 8, extra                                   # the signature, K, the overlay, cb and the two ctrl loads
-    assert [ln for ln in sa if ln not in sw and "r.ctrl[" not in ln and "sample_kernel" not in ln and "slot = b / K" not in ln] == []
 
 
 def test_physics_module_surface(monkeypatch):

@@ -1,5 +1,5 @@
 """Sampled rollouts of the physics layer (rsr_physics_sample_rollouts, Physics.sample_rollouts), host side only: the ABI, the
-dispatch and the Python surface.  The kernel is covered by tests/test_sample_gpu.py."""
+dispatch and the Python surface.  The kernel's text is covered by tests/test_sampled_kernel_api.py, the kernel by tests/test_sample_gpu.py."""
 import ctypes as C
 import inspect
 import os
@@ -67,38 +67,20 @@ def test_refusals_come_before_device_work():
     assert sorted(set(re.findall(r"\bx\.ph\.(\w+)", call))) == ["K", "r"]
 
 
-def test_the_kernel_is_the_rollouts_loop_on_a_read_only_record():
-    kern = open(os.path.join(CSRC, "physics", "rsr_sample.hpp")).read()
-    assert "void sample_kernel(" in kern
-    code = re.sub(r"//.*", "", kern)
-    assert code.count("forward<C>(") == 1 and code.count("integrate<C>(") == 1
-    for k in ("sensor_stage<C>(", "force_stage<C>(e, ", "load_overrides<C>(m, s, a, e, lane)", "lrec_lane(lane)", "if constexpr (C::XFRC)"):
-        assert k in code, k
-    for k in ("store_pipeline", "store_side", "asm", "atomic"):
-        assert k not in kern, k
-    named = re.findall(r"\b(kinematics|com_crb_mass|load_mrow|smooth_forces|\w+_factor|\w+_solve|collision|make_constraint|solve)\b", code)
-    assert not named, named
-    # the record is read only, and neither the side buffer nor the sensordata row is written
-    assert "const float* rec = a.state + (size_t)e * L.rec;" in code and not re.search(r"(?<!const )float\* rec\b", code)
-    assert not re.search(r"\brec\[[^\]]*\]\s*=[^=]", code) and "p.sd" not in code and "p.out" not in code
-    # one flattened loop, rows and ctrl by workgroup in size_t
-    assert len(re.findall(r"\bfor \(int k = 0; k < total; \+\+k\)", code)) == 1 and "const int total = r.T * p.nsteps;" in code
-    assert "(size_t)b * r.T * C::NU" in code and "const size_t row = (size_t)b * r.T + t;" in code
-    assert "slot = b / K" in code and "p.ids ? p.ids[slot] : slot" in code and "if (e < 0 || e >= a.n) return;" in code
-
-
 def test_nothing_outside_the_physics_layer_knows():
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".hpp")):
             text = open(os.path.join(CSRC, f)).read()
-            assert "sample_kernel" not in text and "rsr_sample" not in text and "OP_PHYS_SAMPLE" not in text, f
+            assert "sampled_kernel" not in text and "SampleOp" not in text and "rsr_sample" not in text and "OP_PHYS_SAMPLE" not in text, f
     kernels = open(os.path.join(CSRC, "physics", "rsr_physics_kernels.hpp")).read()
     assert '#include "rsr_sample.hpp"' in kernels
     lp = kernels[kernels.index("int launch_physics("):]
-    # the op's own case, up to the next case label: its kernel, plain and applied, with p, r and K, and no other kernel
+    # the op's own case, up to the next case label: the one (slot, sample) kernel as this op's, plain and applied, with p, r and
+    # K, and no other kernel or op
     case = re.search(r"case OP_PHYS_SAMPLE:(.*?)\n\s*(?:case |default:)", lp, re.S).group(1)
-    assert case.count("sample_kernel<C, WAVES, Applied>, ph.p, ph.r, ph.K, ph.ap)") == 1 and case.count("sample_kernel<C, WAVES>, ph.p, ph.r, ph.K)") == 1
-    assert re.findall(r"\b\w+_kernel\b", case) == ["sample_kernel"] * 2 and lp.count("sample_kernel") == 2
+    assert case.count("sampled_kernel<C, WAVES, SampleOp, Applied>, ph.p, ph.r, ph.K, ph.ap)") == 1 and case.count("sampled_kernel<C, WAVES, SampleOp>, ph.p, ph.r, ph.K)") == 1
+    assert re.findall(r"\b\w+_kernel\b", case) == ["sampled_kernel"] * 2 and lp.count("SampleOp") == 2 and re.findall(r"\b\w+Op\b", case) == ["SampleOp"] * 2
+    assert lp.count("sampled_kernel") == 6                              # three ops, plain and applied
     assert lp.count("hipLaunchKernelGGL(") == 1 and "op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>)" in lp
     assert lp.rstrip().endswith("default: return -1;\n  }\n}\n\n}  // namespace rsr")      # nothing follows the switch
     phys = open(os.path.join(CSRC, "physics", "rsr_physics.hpp")).read()
