@@ -30,7 +30,8 @@ _DR_KEYS = [f for f in _BATCH_FIELDS if f.startswith("dr_")]
 
 
 class _OBatch(C.Structure):
-    _fields_ = [("n", C.c_int)] + [(f, C.POINTER(C.c_float)) for f in _BATCH_FIELDS] + [("stats", C.POINTER(C.c_int))]
+    _fields_ = [("n", C.c_int)] + [(f, C.POINTER(C.c_float)) for f in _BATCH_FIELDS] + [("stats", C.POINTER(C.c_int)),
+                                                                                        ("pair_dist", C.POINTER(C.c_float))]
 
 
 def build(force: bool = False) -> None:
@@ -132,6 +133,8 @@ class Oracle:
             a = st[f]
             setattr(b, f, None if a is None else a.ctypes.data_as(C.POINTER(C.c_float)))
         b.stats = st["stats"].ctypes.data_as(C.POINTER(C.c_int))
+        # optional: st["pair_dist"] = zeros [n, npair] float32 asks the handstand step for every pair's least distance at its last forward pass
+        b.pair_dist = st["pair_dist"].ctypes.data_as(C.POINTER(C.c_float)) if st.get("pair_dist") is not None else None
         return b
 
     def reset(self, st, keys: np.ndarray, threads: int = 0) -> None:

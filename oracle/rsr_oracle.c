@@ -243,6 +243,7 @@ typedef struct {
   /* contacts + constraint rows */
   int ncon, nefc, ne, nf, ncon_overflow;
   ocontact con[NCON_MAX];
+  real pair_dist[NPAIR_MAX];  /* least point distance of each pair's narrow phase, before culling and the cap (PAIR_FAR: no point) */
   real *efc_J;               /* [NEFC_MAX][nv] */
   real efc_pos[NEFC_MAX], efc_aref[NEFC_MAX], efc_D[NEFC_MAX], efc_R[NEFC_MAX], efc_floss[NEFC_MAX];
   real efc_force[NEFC_MAX];
@@ -262,6 +263,7 @@ static void odata_free(odata *d) { if (d) { free(d->efc_J); free(d); } }
 /* global knobs (tests flip them) */
 static int g_cull = 1;        /* 1: drop inactive limit rows / separated contacts (result-neutral) */
 static int g_ncon_cap = NCON_MAX;
+#define PAIR_FAR ((real)1e30)
 /* Line-search stop rule.  0: MJX's (gradient below gtol, no bracket update, or ls_iterations).  1: MJX's plus the HIP kernel's
  * fp32 noise-floor stop for converging solves (iterations > 1): a bracket end also counts as converged when |derivative| is
  * below g_ls_noise * eps * (sum |linear terms| + 2 |alpha| sum |quadratic terms|), the rounding noise of the derivative sum.
@@ -978,6 +980,8 @@ static void collision(const omodel *m, odata *d) {
       default: n = 0;
     }
     real includemargin = (real)m->pair_margin[p] - (real)m->pair_gap[p];   /* (the blob's floats, subtracted in `real`) */
+    d->pair_dist[p] = PAIR_FAR;
+    for (int i = 0; i < n; i++) if (pts[i].dist < d->pair_dist[p]) d->pair_dist[p] = pts[i].dist;
     for (int i = 0; i < n; i++) {
       if (g_cull && !(pts[i].dist - includemargin < 0)) continue;
       if (d->ncon >= g_ncon_cap) { d->ncon_overflow++; continue; }
@@ -1594,6 +1598,7 @@ typedef struct {
   float *dr_geom_friction, *dr_body_mass, *dr_dof_damping, *dr_dof_frictionloss;  /* NULL = model values */
   float *dr_body_ipos, *dr_qpos0, *dr_dof_armature, *dr_gainprm, *dr_biasprm;      /* Go2 randomize.py leaves; NULL = model values */
   int *stats;   /* [n][4]: solver iterations, line-search iterations, ncon, overflow (last substep) */
+  float *pair_dist;   /* [n][npair]: least point distance of every pair at the last forward pass (handstand step); NULL: not wanted */
 } obatch;
 
 static void load_env(const omodel *m, const obatch *s, int e, odata *d) {
@@ -2349,11 +2354,12 @@ static void go2_step_env(const omodel *m, obatch *s, int e, const float *action,
 enum { HS_STEP = 0, HS_LAST_ACT = 4, HS_OBS = 45, HS_PRIV = 94 };
 enum { HM_HEIGHT = 0, HM_ORIENT, HM_CONTACT, HM_ACTION_RATE, HM_TERM, HM_DOF_LIMITS, HM_TORQUES, HM_POSE, HM_STAY_STILL, HM_ENERGY, HM_DOF_ACC, HM_COUNT };
 
+/* Every pair is asked, before the contact cap: the cap limits only the contacts the physics sees (the reference has no cap). */
 static int hs_pair_touching(const omodel *m, const odata *d, int geom) {      /* collision.geoms_colliding(data, geom, floor) */
   const int floor_g = m->env_ids[1];
-  for (int i = 0; i < d->ncon; i++) {
-    if (!(d->con[i].dist < 0)) continue;
-    int g1 = m->pair_geom1[d->con[i].pair], g2 = m->pair_geom2[d->con[i].pair];
+  for (int p = 0; p < m->npair; p++) {
+    if (!(d->pair_dist[p] < 0)) continue;
+    int g1 = m->pair_geom1[p], g2 = m->pair_geom2[p];
     if ((g1 == floor_g && g2 == geom) || (g2 == floor_g && g1 == geom)) return 1;
   }
   return 0;
@@ -2478,6 +2484,7 @@ static void handstand_step_env(const omodel *m, obatch *s, int e, const float *a
   int unwanted = 0, feet = 0;
   for (int k = 0; k < 12; k++) unwanted |= hs_pair_touching(m, d, m->env_ids[2 + k]);
   for (int k = 0; k < 2; k++) feet |= hs_pair_touching(m, d, m->env_ids[14 + k]);
+  if (s->pair_dist) for (int p = 0; p < m->npair; p++) s->pair_dist[(size_t)e * m->npair + p] = (float)d->pair_dist[p];
   const float torso_height = (float)d->site_xpos[3 * m->env_ids[0] + 2];
   hs_obs(m, info, qpos, qvel, &sn, torso_height, &s->obs[e * m->obs_dim], s->priv_obs ? &s->priv_obs[(size_t)e * GO2_PRIV] : NULL);
   /* termination (:188-195) */
@@ -2619,7 +2626,7 @@ int oracle_debug_get(const omodel *m, const char *name, double *out, int cap) {
   G("qacc", d->qacc, m->nv) G("qfrc_constraint", d->qfrc_constraint, m->nv) G("qacc_warmstart", d->qacc_warmstart, m->nv)
   G("efc_J", d->efc_J, d->nefc * m->nv) G("efc_pos", d->efc_pos, d->nefc) G("efc_aref", d->efc_aref, d->nefc)
   G("efc_D", d->efc_D, d->nefc) G("efc_R", d->efc_R, d->nefc) G("efc_floss", d->efc_floss, d->nefc)
-  G("efc_force", d->efc_force, d->nefc)
+  G("efc_force", d->efc_force, d->nefc) G("pair_dist", d->pair_dist, m->npair)
 #undef G
   if (!strcmp(name, "counts")) {
     double v[6] = {(double)d->nefc, (double)d->ne, (double)d->nf, (double)d->ncon, (double)d->solver_niter, (double)d->ls_total};

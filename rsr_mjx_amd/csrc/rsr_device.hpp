@@ -1552,7 +1552,7 @@ __device__ __forceinline__ bool hfield_finish(V3 hpos, const float* hmat, float 
 }
 
 template <class C>
-__device__ __forceinline__ void collision(const DModel& m, const Hot& h, Smem<C>& s, int lane PROF_ARG) {
+__device__ __forceinline__ unsigned long long collision(const DModel& m, const Hot& h, Smem<C>& s, int lane PROF_ARG) {
   CPts pts; pts.cnt = 0; pts.t = v3(0, 0, 0);
   ClipJob job; job.kind = 0;
   float incl = 0.0f;
@@ -1796,6 +1796,12 @@ __device__ __forceinline__ void collision(const DModel& m, const Hot& h, Smem<C>
     }
   }
   PROF(PS_X1)
+  // bit p: some point of pair p has dist < 0, asked of every pair before the cap below drops any (geoms_colliding of the envs);
+  // wave-uniform, and dead code in every kernel that does not read it
+  bool touch = false;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) touch = touch || (i < pts.cnt && pts.dist[i] < 0.0f);
+  const unsigned long long touching = __ballot(touch);
   // keep penetrating contacts only (result-neutral culling), compact in pair order
   int keep = 0;
 #pragma unroll
@@ -1818,6 +1824,7 @@ __device__ __forceinline__ void collision(const DModel& m, const Hot& h, Smem<C>
   if (lane == 0) { s.ncon = total < C::NCON ? total : C::NCON; s.ncon_drop = total > C::NCON ? total - C::NCON : 0; }
   WSYNC();
   PROF(PS_X2)
+  return touching;
 }
 
 // =====================================================================================

@@ -763,14 +763,9 @@ void hs_step_kernel(const DModel* __restrict__ mp, Layout L, StepArgs a) {
   G2Sens sn;
   go2_sensors<C>(m, s, sn);
   go2_accelerometer<C>(m, s, lane, f.qacc, sn);
-  bool unwanted, feet;
-  {
-    const int nc = s.ncon, ci = lane < nc ? lane : 0;
-    const int cp = s.cpair[ci]; const float cd = s.cdist[ci];
-    const int cls = __shfl(pair_class, cp & 63);
-    const int mine = (lane < nc && cd < 0.0f) ? cls : 0;
-    unwanted = __ballot(mine == 1) != 0ull; feet = __ballot(mine == 2) != 0ull;
-  }
+  // every pair is asked, before collision() caps the list the physics sees at NCON points (collision.geoms_colliding)
+  const bool touch = lane < C::NP && ((f.touching >> lane) & 1ull) != 0ull;
+  const bool unwanted = __ballot(touch && pair_class == 1) != 0ull, feet = __ballot(touch && pair_class == 2) != 0ull;
   if (lane < C::NV) qacc_lds[lane] = f.qacc;
   WSYNC();
   hs_obs<C>(m, s, sn, obs_lds, bits, lane);

@@ -645,7 +645,7 @@ __device__ __forceinline__ void solve(const Hot& m, Smem<C>& s, int lane, int ne
 
 // per-lane registers that survive one forward pass
 template <class C>
-struct FwdOut { float qacc, qfc, fsmooth; int nefc; SolveStats st; };
+struct FwdOut { float qacc, qfc, fsmooth; int nefc; SolveStats st; unsigned long long touching; };      // touching: collision()'s pair word
 
 // forward()'s default force stage: none.  A stage maps this lane's qfrc_smooth to a new value right after smooth_forces; the
 // physics layer's applied forces are one (physics/rsr_applied.hpp).
@@ -699,7 +699,7 @@ __device__ __forceinline__ void forward(const DModel& m, const Hot& h, Smem<C>& 
     a0 = lane < C::NV ? chol_solve<C>(a, lt, dinv_m, fs, lane) : 0.0f;
   }
   PROF(PS_CHOLM)
-  collision<C>(m, h, s, lane PROF_PASS);
+  out.touching = collision<C>(m, h, s, lane PROF_PASS);
   PROF(PS_COLL)
   RowRegs rr[C::NCHUNK];
   float bcoef[C::NCHUNK], jqv[C::NCHUNK];

@@ -2,6 +2,7 @@
 scene_mjx_flat_terrain.xml -> go2_mjx.xml): the compiled model, and the oracle's env algebra against a numpy restatement written from
 the source text.  The narrow phase of the model's capsule / cylinder geoms: tests/test_collision.py.  GPU parity: test_go2.py-style
 tests at the end (marked gpu)."""
+import json
 import os
 
 import numpy as np
@@ -249,9 +250,26 @@ def test_handstand_hip_parity(oracle_mod, name, randomize):
     for k in FIELDS:
         env.view(GNAME.get(k, k)).copy_(torch.from_numpy(st[k].reshape(n, -1)))
     a = np.zeros((n, 12), f32)
+    # the float64 oracle on the same step, for every pair's distance at its last forward pass: the contact flags are asked of all 30
+    # pairs (the cap of 12 limits only what the physics sees), and only a pair inside the contact band may be called differently
+    o64 = oracle_mod.Oracle(env.blob, "f64"); o64.set_ncon_cap(env.dims.ncon_max)
+    st64 = o64.new_state(n, odr)
+    o64.reset(st64, keys)
+    for k in FIELDS:
+        st64[k][...] = st[k]
+    st64["pair_dist"] = np.zeros((n, 30), f32)
+    o64.step(st64, a)
     orc.step(st, a); state = env.step(state, a)
     torch.cuda.synchronize()
     np.testing.assert_array_equal(get("done"), st["done"])
+    band = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "handstand_epilogue_tolerances.json")))["contact_band"]["band"]
+    in_band = (np.abs(st64["pair_dist"]) < band).any(1)
+    ci = cfg.HANDSTAND_REWARDS.index("contact")
+    differs = get("metrics")[:, ci] != st["metrics"][:, ci]
+    print(f"{name} floor poses: {int(in_band.sum())} of {n} envs with a pair inside the contact band of {band:g}; contact metric differs in "
+          f"{int(differs.sum())}; {int((st['metrics'][:, ci] != 0).sum())} envs with a cost foot down, {int((st['stats'][:, 3] > 0).sum())} over the cap")
+    assert in_band.sum() <= 0.02 * n
+    assert not (differs & ~in_band).any(), np.flatnonzero(differs & ~in_band)[:10]
     np.testing.assert_array_equal(get("stats")[:, 2:], st["stats"][:, 2:])
     assert (st["stats"][:, 2] > 4).mean() > 0.5 and (st["stats"][:, 3] > 0).any()      # capsule / cylinder contacts, and the cap of 12 is met
     assert st["done"].mean() > 0.5
