@@ -1,6 +1,7 @@
 """Loader of the test-only HIP units under tests/device/: primitives.hip runs the in-register L D L^T layouts, the wave sums and
 the reciprocals of rsr_mjx_amd/csrc/rsr_device.hpp one wave per problem, hfield.hip the height-field narrow phase (hfield_place /
-hfield_search / hfield_finish, closest_on_triangle) one wave per NPAIR spheres.  Builds each with the product's compiler flags into
+hfield_search / hfield_finish, closest_on_triangle) one wave per NPAIR spheres, solver_rows.hip the Newton solver's leaf functions
+(rows_cost, ls_prepare / ls_point / ls_eval / ls_costs, jdot, jt_force of rsr_solver.hpp) one wave per problem.  Builds each with the product's compiler flags into
 tests/device/_build/ (stale against its own source or any csrc header), loads it with ctypes as rsr_mjx_amd/_lib.py loads the
 product library.  Nothing here decodes a layout: factor() returns the raw per-lane registers of all 64 lanes."""
 from __future__ import annotations
@@ -24,9 +25,12 @@ Unit = namedtuple("Unit", "src lib env flags")       # source, library, environm
 # likes, differently in each kernel a function is inlined into, so the last bits of one C++ expression differ between two kernels;
 # a bit-for-bit comparison of hfield_search with a serial scan is a statement about the source's arithmetic and the pick, and is
 # made on this build, where every operation rounds as written in both.  Everything else runs the product-flags build.
+# solver_rows_strict: the same for solver_rows.hip (ls_eval<3> against three ls_point, bit for bit); its tests run on both builds.
 UNITS = {name: Unit(os.path.join(_HERE, "device", src + ".hip"), os.path.join(BUILD_DIR, f"lib{name}.so"), env, flags)
          for name, src, env, flags in (("primitives", "primitives", "RSR_PRIM_LIB", []), ("hfield", "hfield", "RSR_HFIELD_LIB", []),
-                                       ("hfield_strict", "hfield", "RSR_HFIELD_STRICT_LIB", ["-ffp-contract=off"]))}
+                                       ("hfield_strict", "hfield", "RSR_HFIELD_STRICT_LIB", ["-ffp-contract=off"]),
+                                       ("solver_rows", "solver_rows", "RSR_SOLVER_ROWS_LIB", []),
+                                       ("solver_rows_strict", "solver_rows", "RSR_SOLVER_ROWS_STRICT_LIB", ["-ffp-contract=off"]))}
 SRC, LIB = UNITS["primitives"].src, UNITS["primitives"].lib
 
 SYMBOLS = ["rsr_prim_dims", "rsr_prim_supported", "rsr_prim_nreg", "rsr_prim_factor", "rsr_prim_lane_map", "rsr_prim_sums",
@@ -44,8 +48,17 @@ HF_SYMBOLS = ["rsr_hf_npair", "rsr_hf_contact", "rsr_hf_scan", "rsr_hf_triangle"
 HfContact = namedtuple("HfContact", "flag dist pos nrm state c0 r0 searched p q n jdist best q_pre best_pre")
 HfScan = namedtuple("HfScan", "state q best")
 
+SR_SYMBOLS = ["rsr_sr_dims", "rsr_sr_rows_cost", "rsr_sr_linesearch", "rsr_sr_jproducts"]
+SR_DIMS = ("CubeDims", "TShapeDims", "Go2FlatDims", "HandDims")           # (Go2Dims shares Go2FlatDims' row constants)
+SR_DIMS_FIELDS = ("NV", "NEQ", "NF", "NL", "NCON", "NPYR", "NBC", "NEFC", "NCHUNK", "NBASE", "LDJ")
+SrDims = namedtuple("SrDims", SR_DIMS_FIELDS)
+RowsCost = namedtuple("RowsCost", "cost cost_lane force hw")      # [n, 64] x 2, [n, 2, NCHUNK, 64] x 2 (REDUCE = true, false)
+LineSearch = namedtuple("LineSearch", "pt ev cost")               # [n, 3, 4] x 2 (q1, q2, d0(), d1()), [n, 2, 3]
+JProducts = namedtuple("JProducts", "jd qfc")                     # [n, NCHUNK, 64], [n, 64]
+
 _lib = None
 _hf_lib = None
+_sr_lib = None
 
 
 def _headers() -> list:
@@ -250,3 +263,112 @@ def hf_triangle(p, a, b, c):
     torch.cuda.synchronize()
     _check(hf_lib().rsr_hf_triangle(len(v), tv.data_ptr(), q.data_ptr()), "hf_triangle")
     return q.cpu().numpy()
+
+
+# ---------------------------------------------------------------- solver_rows.hip
+def sr_lib(strict: bool = False) -> C.CDLL:
+    global _sr_lib
+    _sr_lib = _sr_lib or {}
+    unit = "solver_rows_strict" if strict else "solver_rows"
+    if unit not in _sr_lib:
+        L = _open(unit)
+        vp, i32 = C.c_void_p, C.c_int
+        L.rsr_sr_dims.argtypes = [i32, C.POINTER(i32)]
+        L.rsr_sr_rows_cost.argtypes = [i32, i32] + [vp] * 9
+        L.rsr_sr_linesearch.argtypes = [i32, i32] + [vp] * 11
+        L.rsr_sr_jproducts.argtypes = [i32, i32] + [vp] * 6 + [C.c_float] + [vp] * 7
+        _sr_lib[unit] = L
+    return _sr_lib[unit]
+
+
+def sr_dims(name: str) -> SrDims:
+    """Row constants of one shipped Dims instantiation (host call: no GPU needed)."""
+    out = (C.c_int * len(SR_DIMS_FIELDS))()
+    rc = sr_lib().rsr_sr_dims(DIMS[name], out)
+    assert rc == 0, (name, rc)
+    return SrDims(*[int(v) for v in out])
+
+
+def _sr_rows(d: SrDims, nefc, *per_lane):
+    """device tensors of nefc[n] and of the per-lane arrays [n, NCHUNK, 64] (float32, or int32 for integer inputs)"""
+    nefc = np.asarray(nefc, dtype=np.int32)
+    n = len(nefc)
+    assert n > 0 and (nefc >= d.NEQ + d.NF).all() and (nefc <= d.NEFC).all(), "nefc outside [NEQ + NF, NEFC]"
+    out = [_dev(nefc, np.int32)]
+    for a in per_lane:
+        a = np.asarray(a)
+        assert a.shape == (n, d.NCHUNK, 64), (a.shape, (n, d.NCHUNK, 64))
+        out.append(_dev(a, np.int32 if a.dtype.kind in "iu" else np.float32))
+    return n, out
+
+
+def rows_cost(dims_name: str, nefc, jaref, D, R, floss, strict: bool = False) -> RowsCost:
+    """rows_cost<C, true> and rows_cost<C, false> of n waves: the reduced cost as every lane holds it, each lane's share, and the
+    force / weight registers of both calls.  Inputs [n, NCHUNK, 64] (row = lane + 64 * chunk)."""
+    import torch
+    d = sr_dims(dims_name)
+    n, t = _sr_rows(d, nefc, jaref, D, R, floss)
+    cost, lane = (torch.zeros((n, 64), dtype=torch.float32, device="cuda") for _ in range(2))
+    force, hw = (torch.zeros((n, 2, d.NCHUNK, 64), dtype=torch.float32, device="cuda") for _ in range(2))
+    torch.cuda.synchronize()
+    _check(sr_lib(strict).rsr_sr_rows_cost(DIMS[dims_name], n, *[x.data_ptr() for x in t + [cost, lane, force, hw]]), "rows_cost")
+    return RowsCost(*[x.cpu().numpy() for x in (cost, lane, force, hw)])
+
+
+def linesearch(dims_name: str, nefc, jaref, jv, D, R, floss, g, alpha, strict: bool = False) -> LineSearch:
+    """ls_prepare once, then ls_point at each of alpha[n, 3], ls_eval<C, 3> at the three together and ls_costs on either set of
+    points; g[n, 3] = (g0, g1, g2)."""
+    import torch
+    d = sr_dims(dims_name)
+    n, t = _sr_rows(d, nefc, jaref, jv, D, R, floss)
+    assert np.shape(g) == (n, 3) and np.shape(alpha) == (n, 3)
+    t += [_dev(g), _dev(alpha)]
+    pt, ev = (torch.zeros((n, 3, 4), dtype=torch.float32, device="cuda") for _ in range(2))
+    cost = torch.zeros((n, 2, 3), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    _check(sr_lib(strict).rsr_sr_linesearch(DIMS[dims_name], n, *[x.data_ptr() for x in t + [pt, ev, cost]]), "linesearch")
+    return LineSearch(pt.cpu().numpy(), ev.cpu().numpy(), cost.cpu().numpy())
+
+
+def jproducts(dims_name: str, nl, ncon, B, bmu, sdof, mu, bn, bk, v, force, poison: float = float("nan"), strict: bool = False) -> JProducts:
+    """vec_bcast + jdot of v[n, NV] and jt_force of force[n, NCHUNK, 64] on n LDS images.  nl[n], ncon[n]: active limits and
+    contacts (nefc = NEQ + NF + nl + NPYR ncon, nbase = NEQ + NF + nl + NBC ncon); B[n, NBASE, NV]: the base rows, of which the
+    first nbase are used; bmu[n, NBASE]: of which the contact tangents' are used; sdof[n, NSP]: of which the friction and limit
+    rows' are used; mu, bn, bk [n, NCHUNK, 64]: the rows' registers (padding rows: 0, NBASE, NBASE).  The image holds these words,
+    a zero null row and bval[NBASE .. NBASE + 4) = 0; every other word of J, bmu, bval, rw, jtp, wc and dgw holds `poison`
+    (solver_rows.hip states the contract)."""
+    import torch
+    d = sr_dims(dims_name)
+    nl, ncon = np.asarray(nl, dtype=np.int32), np.asarray(ncon, dtype=np.int32)
+    assert (nl >= 0).all() and (nl <= d.NL).all() and (ncon >= 0).all() and (ncon <= d.NCON).all()
+    rcon = d.NEQ + d.NF + nl
+    nefc, nbase = rcon + d.NPYR * ncon, rcon + d.NBC * ncon
+    bn, bk, sdof = np.asarray(bn), np.asarray(bk), np.asarray(sdof)
+    n, t = _sr_rows(d, nefc, np.asarray(mu, np.float32), bn.astype(np.int32), bk.astype(np.int32))
+    nsp = d.NEQ + d.NF + d.NL
+    assert (bn >= 0).all() and (bn <= d.NBASE).all() and (bk >= 0).all() and (bk <= d.NBASE).all(), "base row index outside the image"
+    assert sdof.shape == (n, nsp) and (sdof >= 0).all() and (sdof < d.NV).all(), "dof index outside the row"
+    B, bmu = np.asarray(B, np.float32), np.asarray(bmu, np.float32)
+    assert B.shape == (n, d.NBASE, d.NV) and bmu.shape == (n, d.NBASE) and np.shape(v) == (n, d.NV) and np.shape(force) == (n, d.NCHUNK, 64)
+    J = np.full((n, d.NBASE + 1, d.LDJ), poison, np.float32)
+    live = np.arange(d.NBASE)[None, :] < nbase[:, None]
+    J[:, :d.NBASE, :d.NV] = np.where(live[:, :, None], B, np.float32(poison))
+    J[:, d.NBASE, :] = 0.0
+    k = np.arange(d.NBASE)[None, :] - rcon[:, None]
+    tangent = live & (k >= 0) & (k % d.NBC != 0)
+    bmu_i = np.full((n, d.NBASE + 4), poison, np.float32)
+    bmu_i[:, :d.NBASE] = np.where(tangent, bmu, np.float32(poison))
+    bval = np.full((n, d.NBASE + 4), poison, np.float32)
+    bval[:, d.NBASE:] = 0.0
+    sd = np.zeros((n, nsp + 1), np.int32)
+    r = np.arange(nsp)[None, :]
+    sd[:, :nsp] = np.where((r >= d.NEQ) & (r < rcon[:, None]), sdof, 0)
+    jd = torch.zeros((n, d.NCHUNK, 64), dtype=torch.float32, device="cuda")
+    qfc = torch.zeros((n, 64), dtype=torch.float32, device="cuda")
+    nefc_t, mu_t, bn_t, bk_t = t
+    args = [nefc_t, _dev(ncon, np.int32), _dev(J), _dev(bmu_i), _dev(bval), _dev(sd, np.int32)]
+    tail = [mu_t, bn_t, bk_t, _dev(v), _dev(force), jd, qfc]
+    torch.cuda.synchronize()
+    _check(sr_lib(strict).rsr_sr_jproducts(DIMS[dims_name], n, *[x.data_ptr() for x in args], C.c_float(poison),
+                                           *[x.data_ptr() for x in tail]), "jproducts")
+    return JProducts(jd.cpu().numpy(), qfc.cpu().numpy())
