@@ -28,6 +28,8 @@
  *   rsr_physics_lqr_backward <- the backward pass of iLQR / time-varying LQR (the Riccati recursion over lax.scan(reverse=True)):
  *                          A_t, B_t and a quadratic cost model in, the gains K_t, k_t of rsr_physics_feedback_rollouts out, one
  *                          launch; neither the model nor the record is read.
+ *   rsr_physics_lqr_box <- the backward pass of control-limited DDP (Tassa, Mansard and Todorov 2014): the same with k_t the
+ *                          minimiser of a box-constrained QP and the gain rows of the clamped controls zero, one launch.
  *   rsr_physics_ik      <- an IK library on top of mj_jacSite (damped least squares on site pose targets): M problems, one launch,
  *                          every iteration on the device; the record is read only.
  *   rsr_physics_kalman  <- a Kalman filter and RTS smoother over a log (lax.scan over A_t, C_t forwards, then reverse=True): the
@@ -440,6 +442,49 @@ typedef struct rsr_lqr_out  { float* gain; float* k; float* dv; float* status; f
 int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const float* columns, int row_stride,
                              const rsr_lqr_cost* cost, const float* mu, int flags,
                              const rsr_lqr_out* out, void* hip_stream);
+
+/* Control-limited LQR backward pass (box-DDP: Tassa, Mansard and Todorov 2014), the backward pass that agrees with the clamp of
+ * rsr_physics_feedback_rollouts (RSR_FB_CLAMP): rsr_physics_lqr_backward with k_t the minimiser of the step's quadratic model over
+ * a box, and the gain rows of the clamped controls zero.  columns, cost, mu, flags (RSR_LQR_REG_STATE or 0) and out are exactly
+ * those of rsr_physics_lqr_backward, as are the layout, the one launch with one wavefront per slot and the fixed summation order.
+ * box: lo, hi [M, T, nu], required: the bounds on the control *change* k_t, i.e. the caller passes ctrlrange - u_nom[t]; -inf / +inf:
+ * no bound.  clamped [M, T, nu] (may be NULL): -1 where k_t sits at lo, +1 at hi, 0 where it is free.  qp [M, T, 2] (may be NULL):
+ * the Newton steps taken and a code: 0 converged, 1 every control clamped, 2 max_iter reached, 3 the line search found no descent.
+ * max_iter in [1, 64].
+ * At step t, Qx .. Quu, Quu~ and Qux~ as in rsr_physics_lqr_backward; then with H = Quu~, g = Qu, l = lo[s, t], h = hi[s, t]:
+ *   not (l_j <= h_j) for some j (a NaN included): the step fails, like a bad pivot
+ *   x = min(max(0, l), h);  full = false;  c_prev = none
+ *   for it = 0, 1, ...:
+ *     grad_j = g_j + sum_i H_ji x_i                                  (one fma chain over i ascending, from g_j)
+ *     c_j = (x_j == l_j and grad_j > 0) or (x_j == h_j and grad_j < 0)
+ *     all c: code 1, stop
+ *     full and c == c_prev: code 0, stop                             (a full Newton step and the set held: the face's minimiser)
+ *     it == max_iter: code 2, stop
+ *     Cholesky of Hm = H with the rows and columns of c replaced by the identity's; a bad pivot fails the step
+ *     r_j = 0 where c_j, else g_j + sum_{i in c} H_ji x_i            (ascending, from g_j)
+ *     y = -Hm^-1 r;  x*_j = x_j where c_j, else y_j;  d = x* - x;  c_prev = c
+ *     l_j <= fl(x_j + d_j) <= h_j for every j: x = x*, full = true, next it
+ *     full = false;  f(z) = 1/2 z^T H z + g^T z = sum_j (1/2 (H z)_j + g_j) z_j
+ *     for n = 0 .. 19, a = 0.6^n (repeated fp32 products): z = min(max(fl(x + a d), l), h); take the first z with
+ *       f(x) - f(z) >= 0.1 grad^T (x - z)
+ *     none taken: code 3, stop;  else x = z
+ *   k = x (a clamped entry is its bound bit for bit)
+ *   K: the rows of the last c are 0, the others -Hm^-1 Qux~ with the factor of that c (taken now if the loop's last factor was of
+ *   another set); code 1: K = 0 and no factor
+ *   Vx, Vxx (from the unregularised Quu, Qux, symmetrised) and dv from these k, K by the formulas of rsr_physics_lqr_backward
+ * Every loop is bounded: max_iter Newton steps, 20 trial points, nu columns.  qp[s, t, 0] is `it` at the stop.  H_ff is positive
+ * definite wherever a factor exists, so the KKT conditions of a step's QP are sufficient for its minimiser.
+ * With lo = -inf and hi = +inf everywhere, and with finite bounds that no step reaches, every buffer of out equals what
+ * rsr_physics_lqr_backward writes bit for bit (x = 0, grad = r = g, nothing masked, the full step taken without the Armijo test),
+ * clamped is 0 and qp is (1, 0).
+ * Failure: as rsr_physics_lqr_backward: status[s] = t, dv[s] = (0, 0), rows t' <= t of every buffer of out and of clamped / qp are
+ * left alone, rows t' > t keep what was written; on success status[s] = -1.
+ * Only the buffers of out and of box are written; the handle owns no buffer for this call.
+ * RSR_ERR_ARG, checked before any device work: everything rsr_physics_lqr_backward refuses; a NULL box, box->lo or box->hi;
+ * max_iter outside [1, 64]. */
+typedef struct rsr_lqr_box { const float* lo; const float* hi; float* clamped; float* qp; } rsr_lqr_box;
+int rsr_physics_lqr_box(rsr_physics* p, int M, int T, const float* columns, int row_stride, const rsr_lqr_cost* cost,
+                        const rsr_lqr_box* box, const float* mu, int max_iter, int flags, const rsr_lqr_out* out, void* hip_stream);
 
 /* Kalman filter and smoother, the estimation dual of rsr_physics_lqr_backward: a linear time-varying Kalman filter with a
  * Rauch-Tung-Striebel smoother on M independent problems, one launch with one wavefront per slot and all T steps inside it.  The

@@ -46,7 +46,7 @@ PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step",
                 "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
                 "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts",
                 "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd", "rsr_physics_lqr_backward", "rsr_physics_ik",
-                "rsr_physics_cost_rollouts", "rsr_physics_kalman"]
+                "rsr_physics_cost_rollouts", "rsr_physics_kalman", "rsr_physics_lqr_box"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -130,6 +130,12 @@ class LqrOut(C.Structure):
     """struct rsr_lqr_out (include/rsr_physics.h): device pointers, gain [M, T, nu, nx], k [M, T, nu], dv [M, 2], status [M]
     (required), vx [M, T+1, nx] and vxx [M, T+1, nx, nx] (NULL = not recorded)."""
     _fields_ = [(n, C.c_void_p) for n in ("gain", "k", "dv", "status", "vx", "vxx")]
+
+
+class LqrBox(C.Structure):
+    """struct rsr_lqr_box (include/rsr_physics.h): device pointers, lo and hi [M, T, nu] (required; -inf / +inf = no bound), clamped
+    [M, T, nu] and qp [M, T, 2] (NULL = not recorded)."""
+    _fields_ = [(n, C.c_void_p) for n in ("lo", "hi", "clamped", "qp")]
 
 
 class KalmanIn(C.Structure):
@@ -230,6 +236,7 @@ def lib() -> C.CDLL:
     L.rsr_physics_cost_rollouts.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.rsr_physics_trajectory_fd.argtypes = [vp, vp, i32, vp, i32, i32, C.c_float, i32, vp, vp]
     L.rsr_physics_lqr_backward.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
+    L.rsr_physics_lqr_box.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp]
     L.rsr_physics_ik.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.rsr_physics_kalman.argtypes = [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp]
     L.rsr_batch_set_debug.argtypes = [vp, vp]

@@ -22,6 +22,13 @@
 // The NU x NU Cholesky runs in LDS on the wave (a column per step), the solves one right-hand side per lane (nx columns of Qux~
 // and Qu) with the column in registers.  Global loads of the next step's F and of this step's cost rows are issued before the first
 // product and land in registers while it runs.
+//
+// rsr_physics_lqr_box (box_backward_kernel) is the same body with BOX = true: between the Q blocks and the value update, k_t is the
+// minimiser of the step's QP over lo <= x <= hi by projected Newton steps (the iteration is stated in include/rsr_physics.h), the
+// factor is taken of Quu~ with the clamped rows and columns replaced by the identity's, and the right-hand sides of the clamped rows
+// of K are zeros.  Lane j < nu holds entry j of the QP's vectors and forms its entry of H x as one fma chain; every lane runs the one
+// nu x nu solve on the same LDS words, so y needs no broadcast; the clamped set is a ballot.  With no bound reached the arithmetic
+// that reaches the outputs is the plain pass's, operation for operation.
 #pragma once
 #include "../rsr_launch.hpp"
 
@@ -73,17 +80,46 @@ __device__ __forceinline__ float row_dot(const float* a, const float* b, float a
   return acc;
 }
 
+// What rsr_physics_lqr_box adds to the image: Quu~ as it was formed (the factor is taken in place and taken again for every set of
+// clamped controls), and the QP's vectors, 16 floats each: x, the gradient, the right-hand side, the trial point, H z.  The bounds
+// of a step stay in the registers of the lanes j < nu.
+template <class C>
+struct BoxDims {
+  static constexpr int NU = C::NU;
+  static constexpr int H = LqrDims<C>::FLOATS, X = H + ((NU * NU + 3) & ~3), GR = X + 16, R = GR + 16, Z = R + 16, HZ = Z + 16;
+  static constexpr int FLOATS = HZ + 16;
+};
+template <class C>
+constexpr size_t box_lds_bytes() { return sizeof(float) * BoxDims<C>::FLOATS; }
+
+// The one body of both passes.  BOX = false: the plain recursion; bx is not read and every branch on BOX folds away.
+template <class C, bool BOX>
+__device__ __forceinline__ void lqr_body(const LqrArgs& q, const BoxArgs& bx);
+
 // Workgroup s: slot s.  WAVES: the family's waves per SIMD, an upper bound only (the LDS image admits fewer).
 template <class C, int WAVES>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WAVES)))
 void lqr_kernel(const DModel* __restrict__, Layout, StepArgs, LqrArgs q) {
+  lqr_body<C, false>(q, BoxArgs{});
+}
+// rsr_physics_lqr_box: the same recursion with k_t the minimiser of the step's box-constrained QP (Tassa, Mansard and Todorov 2014)
+template <class C, int WAVES>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WAVES)))
+void box_backward_kernel(const DModel* __restrict__, Layout, StepArgs, BoxArgs b) {
+  lqr_body<C, true>(b.lq, b);
+}
+
+template <class C, bool BOX>
+__device__ __forceinline__ void lqr_body(const LqrArgs& q, const BoxArgs& bx) {
   using D = LqrDims<C>;
+  using E = BoxDims<C>;
   constexpr int NX = D::NX, NU = D::NU, NC = D::NC, LD = D::LD, IB = D::IB, KBLK = D::KBLK, KB = D::KB, NREG = D::NREG;
   constexpr int NQUU = (NU * NU + 63) / 64;      // entries of Quu per lane
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* const sm = reinterpret_cast<float*>(smem_raw);
   float *const V = sm + D::V, *const F = sm + D::F, *const W = sm + D::W, *const P = sm + D::P, *const K = sm + D::K, *const G = sm + D::G;
   float *const QUU = sm + D::QUU, *const LF = sm + D::LF, *const VX = sm + D::VX, *const Q = sm + D::Q, *const KV = sm + D::KV, *const GV = sm + D::GV;
+  float *const HQ = sm + E::H, *const BX = sm + E::X, *const BG = sm + E::GR, *const BR = sm + E::R, *const BZ = sm + E::Z, *const BHZ = sm + E::HZ;   // (BOX)
   const int lane = threadIdx.x, T = q.T;
   const size_t slot = blockIdx.x;
   const float mu = q.mu[slot];
@@ -144,6 +180,11 @@ void lqr_kernel(const DModel* __restrict__, Layout, StepArgs, LqrArgs q) {
     if (t > 0) fetch_F(t - 1);
     // (and the step's small cost rows: a load where its value is used would stand in the way for a round trip to memory)
     const float lq = lane < NX ? q.lx[(slot * (T + 1) + t) * NX + lane] : (lane < NC ? q.lu[(slot * T + t) * NU + lane - NX] : 0.0f);
+    const bool mine = lane < NU;                   // (BOX) lane j < nu: entry j of the QP's vectors
+    float lj = 0.0f, hj = 0.0f;
+    if constexpr (BOX) {
+      if (mine) { lj = bx.lo[(slot * T + t) * NU + lane]; hj = bx.hi[(slot * T + t) * NU + lane]; }
+    }
     float luu[NQUU];
 #pragma unroll
     for (int n = 0; n < NQUU; ++n) luu[n] = lane + 64 * n < NU * NU ? q.luu[(slot * T + t) * (size_t)(NU * NU) + lane + 64 * n] : 0.0f;
@@ -196,38 +237,33 @@ void lqr_kernel(const DModel* __restrict__, Layout, StepArgs, LqrArgs q) {
       if (e >= NU * NU) continue;
       const float quu = luu[n] + row_dot<NX>(F + (NX + j) * LD, W + (NX + j2) * LD, 0.0f);
       QUU[e] = quu;
-      LF[e] = quu + (state_reg ? mu * row_dot<NX>(F + (NX + j) * LD, F + (NX + j2) * LD, 0.0f) : (j == j2 ? mu : 0.0f));
+      const float quur = quu + (state_reg ? mu * row_dot<NX>(F + (NX + j) * LD, F + (NX + j2) * LD, 0.0f) : (j == j2 ? mu : 0.0f));
+      LF[e] = quur;
+      if constexpr (BOX) HQ[e] = quur;
     }
     WSYNC();
-    // Cholesky of Quu~ in place, a column per trip; a pivot <= 0 or not finite ends the slot (wave-uniform: one LDS word).  Every
-    // lane keeps the reciprocals of the factor's diagonal: the solves multiply by them.
-    bool ok = true;
+    // Cholesky of what LF holds, in place, a column per trip; a pivot <= 0 or not finite ends the slot (wave-uniform: one LDS
+    // word).  Every lane keeps the reciprocals of the factor's diagonal: the solves multiply by them.
     float dinv[NU];
-#pragma unroll
-    for (int j = 0; j < NU; ++j) {
-      const float d = asf(uniform_i(__builtin_bit_cast(int, LF[j * NU + j])));
-      if (!(d > 0.0f) || !(d < __builtin_inff())) ok = false;       // (the later columns then run on for nothing: the slot ends below)
-      dinv[j] = 1.0f / sqrtf(d);
-      if (lane > j && lane < NU) LF[lane * NU + j] = LF[lane * NU + j] * dinv[j];
-      WSYNC();
-      for (int e = lane; e < NU * NU; e += 64) {
-        const int i = e / NU, c = e - i * NU;
-        if (c > j && i >= c) LF[e] = __builtin_fmaf(-LF[i * NU + j], LF[c * NU + j], LF[e]);
-      }
-      WSYNC();
-    }
-    if (!ok) {
-      if (lane == 0) { q.status[slot] = (float)t; q.dv[2 * slot] = 0.0f; q.dv[2 * slot + 1] = 0.0f; }
-      return;
-    }
-    // K = -Quu~^-1 Qux~ and k = -Quu~^-1 Qu: lane b < nx column b, lane nx the vector; then G = Quu K + Qux, Quu k + Qu, dV
-    if (lane <= NX) {
-      float x[NU];
+    auto chol = [&]() {
+      bool ok = true;
 #pragma unroll
       for (int j = 0; j < NU; ++j) {
-        if (lane == NX) x[j] = Q[NX + j];
-        else x[j] = P[(NX + j) * LD + lane] + (state_reg ? mu * row_dot<NX>(F + (NX + j) * LD, F + lane * LD, 0.0f) : 0.0f);
+        const float d = asf(uniform_i(__builtin_bit_cast(int, LF[j * NU + j])));
+        if (!(d > 0.0f) || !(d < __builtin_inff())) ok = false;     // (the later columns then run on for nothing: the slot ends below)
+        dinv[j] = 1.0f / sqrtf(d);
+        if (lane > j && lane < NU) LF[lane * NU + j] = LF[lane * NU + j] * dinv[j];
+        WSYNC();
+        for (int e = lane; e < NU * NU; e += 64) {
+          const int i = e / NU, c = e - i * NU;
+          if (c > j && i >= c) LF[e] = __builtin_fmaf(-LF[i * NU + j], LF[c * NU + j], LF[e]);
+        }
+        WSYNC();
       }
+      return ok;
+    };
+    // x = -(L L^T)^-1 x with the factor in LF, the column in registers
+    auto solve = [&](float (&x)[NU]) {
 #pragma unroll
       for (int j = 0; j < NU; ++j) {
 #pragma unroll
@@ -242,6 +278,132 @@ void lqr_kernel(const DModel* __restrict__, Layout, StepArgs, LqrArgs q) {
       }
 #pragma unroll
       for (int j = 0; j < NU; ++j) x[j] = -x[j];
+    };
+    bool ok;
+    unsigned cm = 0u;                              // bit j: control j is clamped (the plain pass: none)
+    int code = 0, steps = 0;
+    float clampj = 0.0f;
+    if constexpr (!BOX) ok = chol();
+    else {
+      // k = argmin 1/2 x^T H x + g^T x over lo <= x <= hi, H = Quu~, g = Qu, by projected Newton steps (include/rsr_physics.h states
+      // it line by line).  Lane j < nu holds entry j of x, l, h, the gradient and the step, and forms its entry of every product as
+      // one fma chain over i ascending; the solve and the two scalars of the Armijo test are formed by every lane alike from LDS
+      // words.  Every branch around a WSYNC is taken on a ballot, on `it`, or on a value sent through uniform_i.
+      constexpr unsigned ALL = (1u << NU) - 1u, NONE = ~0u;
+      const float* Hj = HQ + (mine ? lane : 0) * NU;                // row j of H
+      // Armijo needs f(v) = 1/2 v^T H v + g^T v of a vector in LDS: H v a lane per row, then sum_j (1/2 (H v)_j + g_j) v_j ascending
+      auto fval = [&](const float* v) {
+        float hv = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NU; ++i) hv = __builtin_fmaf(Hj[i], v[i], hv);
+        WSYNC();
+        if (mine) BHZ[lane] = hv;
+        WSYNC();
+        float f = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NU; ++j) f = __builtin_fmaf(__builtin_fmaf(0.5f, BHZ[j], Q[NX + j]), v[j], f);
+        return f;
+      };
+      auto factor = [&]() {                        // Hm: H with the rows and columns of cm replaced by the identity's
+        WSYNC();
+        for (int e = lane; e < NU * NU; e += 64) {
+          const int i = e / NU, c = e - i * NU;
+          LF[e] = ((cm >> i) | (cm >> c)) & 1u ? (i == c ? 1.0f : 0.0f) : HQ[e];
+        }
+        WSYNC();
+        return chol();
+      };
+      ok = __ballot(mine && !(lj <= hj)) == 0ull;
+      if (ok) {
+        const float gj = mine ? Q[NX + lane] : 0.0f;
+        float xj = 0.0f < lj ? lj : (0.0f > hj ? hj : 0.0f), grad = 0.0f;
+        bool cj = false, full = false;
+        unsigned cprev = NONE, cfac = NONE;
+        if (mine) BX[lane] = xj;
+        WSYNC();
+        for (int it = 0;; ++it) {                  // (leaves at it == max_iter at the latest)
+          grad = gj;
+#pragma unroll
+          for (int i = 0; i < NU; ++i) grad = __builtin_fmaf(Hj[i], BX[i], grad);
+          cj = mine && ((xj == lj && grad > 0.0f) || (xj == hj && grad < 0.0f));
+          cm = (unsigned)__ballot(cj);
+          steps = it;
+          if (cm == ALL) { code = 1; break; }
+          if (full && cm == cprev) { code = 0; break; }
+          if (it == bx.max_iter) { code = 2; break; }
+          ok = factor();
+          cfac = cm;
+          if (!ok) break;
+          float r = gj;
+#pragma unroll
+          for (int i = 0; i < NU; ++i) r = (cm >> i) & 1u ? __builtin_fmaf(Hj[i], BX[i], r) : r;
+          if (mine) { BR[lane] = cj ? 0.0f : r; BG[lane] = grad; }
+          WSYNC();
+          float y[NU], yj = 0.0f;
+#pragma unroll
+          for (int j = 0; j < NU; ++j) y[j] = BR[j];
+          solve(y);
+#pragma unroll
+          for (int j = 0; j < NU; ++j) yj = lane == j ? y[j] : yj;
+          const float xs = cj ? xj : yj, dj = xs - xj, xn = xj + dj;
+          cprev = cm;
+          if (__ballot(mine && !(lj <= xn && xn <= hj)) == 0ull) {   // the full step stays inside: take it as it is
+            xj = xs; full = true;
+            WSYNC();
+            if (mine) BX[lane] = xj;
+            WSYNC();
+            continue;
+          }
+          full = false;
+          const float f0 = fval(BX);
+          float a = 1.0f, zj = xj;
+          bool taken = false;
+          for (int n = 0; n < 20 && !taken; ++n, a *= 0.6f) {
+            zj = __builtin_fmaf(a, dj, xj);
+            zj = zj < lj ? lj : (zj > hj ? hj : zj);
+            WSYNC();
+            if (mine) BZ[lane] = zj;
+            WSYNC();
+            const float fz = fval(BZ);
+            float gd = 0.0f;
+#pragma unroll
+            for (int j = 0; j < NU; ++j) gd = __builtin_fmaf(BG[j], BX[j] - BZ[j], gd);
+            taken = uniform_i(f0 - fz >= 0.1f * gd) != 0;
+          }
+          if (!taken) { code = 3; break; }
+          xj = zj;
+          WSYNC();
+          if (mine) BX[lane] = xj;
+          WSYNC();
+        }
+        if (ok && code != 1 && cm != cfac) ok = factor();            // (max_iter came with another set than the last factor's)
+        // a clamped control is its bound bit for bit (the sign of a zero too)
+        if (cj) xj = grad > 0.0f ? lj : hj;
+        clampj = cj ? (grad > 0.0f ? -1.0f : 1.0f) : 0.0f;
+        WSYNC();
+        if (mine) BX[lane] = xj;
+        WSYNC();
+      }
+    }
+    if (!ok) {
+      if (lane == 0) { q.status[slot] = (float)t; q.dv[2 * slot] = 0.0f; q.dv[2 * slot + 1] = 0.0f; }
+      return;
+    }
+    if constexpr (BOX) {
+      if (bx.clamped && mine) bx.clamped[(slot * T + t) * NU + lane] = clampj;
+      if (bx.qp && lane == 0) { bx.qp[(slot * T + t) * 2] = (float)steps; bx.qp[(slot * T + t) * 2 + 1] = (float)code; }
+    }
+    // K = -Quu~^-1 Qux~ and k = -Quu~^-1 Qu: lane b < nx column b, lane nx the vector; then G = Quu K + Qux, Quu k + Qu, dV.  BOX: k
+    // is the QP's x, and the rows of K of the clamped controls are zeros (their right-hand sides are, and Hm's rows are the identity's)
+    if (lane <= NX) {
+      float x[NU];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        if (lane == NX) x[j] = BOX ? BX[j] : Q[NX + j];
+        else x[j] = P[(NX + j) * LD + lane] + (state_reg ? mu * row_dot<NX>(F + (NX + j) * LD, F + lane * LD, 0.0f) : 0.0f);
+        if (BOX && lane != NX && ((cm >> j) & 1u)) x[j] = 0.0f;
+      }
+      if (!BOX || (lane != NX && code != 1)) solve(x);
       float g[NU];                                  // Quu x
 #pragma unroll
       for (int j = 0; j < NU; ++j) {

@@ -3,7 +3,7 @@
 // the dynamics terms (rsr_physics_dynamics), the constraint and contact forces (rsr_physics_constraint) and the transition Jacobians
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse), sampled rollouts (rsr_physics_sample_rollouts), parameter
 // rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts), cost rollouts (rsr_physics_cost_rollouts), the transition Jacobians along a
-// trajectory (rsr_physics_trajectory_fd), the LQR backward pass (rsr_physics_lqr_backward), inverse kinematics on site pose
+// trajectory (rsr_physics_trajectory_fd), the LQR backward pass (rsr_physics_lqr_backward) and its control-limited form (rsr_physics_lqr_box), inverse kinematics on site pose
 // targets (rsr_physics_ik) and the Kalman filter and smoother (rsr_physics_kalman).  Every launch is a physics op
 // (rsr::PhysOp) sent through physics_launch; the kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
@@ -550,6 +550,27 @@ extern "C" int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const floa
   x.ph.lq = rsr::LqrArgs{columns, row_stride, T, cost->lx, cost->lu, cost->lxx, cost->luu, cost->lux, mu, flags,
                          out->gain, out->k, out->dv, out->status, out->vx, out->vxx};
   return physics_launch(p, rsr::OP_LQR_BACKWARD, x, "rsr_physics_lqr_backward");
+}
+
+// The same launch with the bounds on k_t (box_backward_kernel, rsr_lqr.hpp).  None of the handle's buffers is used.
+extern "C" int rsr_physics_lqr_box(rsr_physics* p, int M, int T, const float* columns, int row_stride, const rsr_lqr_cost* cost,
+                                   const rsr_lqr_box* box, const float* mu, int max_iter, int flags, const rsr_lqr_out* out, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: null handle");
+  if (!columns || !cost || !box || !mu || !out) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: null columns, cost, box, mu or out");
+  if (!cost->lx || !cost->lu || !cost->lxx || !cost->luu) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: cost needs lx, lu, lxx and luu (only lux may be null)");
+  if (!box->lo || !box->hi) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: box needs lo and hi (only clamped and qp may be null)");
+  if (!out->gain || !out->k || !out->dv || !out->status) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: out needs gain, k, dv and status (only vx and vxx may be null)");
+  if (M < 1 || T < 1) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: M and T must be >= 1");
+  const rsr_dims& d = p->b->model->dims;
+  if (row_stride < 2 * d.nv) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: row_stride must be >= 2 nv");
+  if (max_iter < 1 || max_iter > 64) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: max_iter must lie in [1, 64]");
+  if (flags & ~RSR_LQR_REG_STATE) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: unknown flag bits");
+  if ((int64_t)M * ((int64_t)T + 1) > INT32_MAX) return fail(RSR_ERR_ARG, "rsr_physics_lqr_box: M x (T + 1) must stay below 2^31");
+  rsr::Launch x = physics_args(p, nullptr, nullptr, M, 1, hip_stream);
+  x.ph.bx = rsr::BoxArgs{rsr::LqrArgs{columns, row_stride, T, cost->lx, cost->lu, cost->lxx, cost->luu, cost->lux, mu, flags,
+                                      out->gain, out->k, out->dv, out->status, out->vx, out->vxx},
+                         box->lo, box->hi, box->clamped, box->qp, max_iter};
+  return physics_launch(p, rsr::OP_BOX_BACKWARD, x, "rsr_physics_lqr_box");
 }
 
 // One launch, one wave per slot (rsr_kalman.hpp).  The handle gives nv, nu, the device and the family's entry; none of its buffers is used.

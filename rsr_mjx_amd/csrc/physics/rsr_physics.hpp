@@ -149,6 +149,14 @@ struct LqrArgs {
   float *gain, *k, *dv, *status;      // [M][T][nu][nx], [M][T][nu], [M][2], [M]
   float *vx, *vxx;      // [M][T+1][nx], [M][T+1][nx][nx], each null = not recorded
 };
+// rsr_physics_lqr_box (box_backward_kernel, rsr_lqr.hpp): the plain pass's arguments and the bounds on k_t (PhysLaunch::bx)
+struct BoxArgs {
+  LqrArgs lq;
+  const float *lo, *hi; // [M][T][nu], -inf / +inf: no bound
+  float* clamped;       // [M][T][nu] -1 at lo, +1 at hi, 0 free, or null
+  float* qp;            // [M][T][2] Newton steps taken, code, or null
+  int max_iter;         // 1 .. 64
+};
 // rsr_physics_ik (rsr_ik.hpp): the caller's buffers, every row indexed by slot, and the task table by value (PhysLaunch::ik): the
 // op has no device table and no state in the handle.
 struct IkArgs {
@@ -212,6 +220,7 @@ enum PhysOp {
   OP_IK,                 // rsr_physics_ik (ik): grid = slots, the env of a slot from ik.ids
   OP_COST_ROLLOUTS,      // rsr_physics_cost_rollouts (p, r, sw, cs): grid and rows as OP_PHYS_SWEEP's
   OP_KALMAN,             // rsr_physics_kalman (kf): grid = slots; reads neither the model nor the record
+  OP_BOX_BACKWARD,       // rsr_physics_lqr_box (bx): grid = slots; reads neither the model nor the record
 };
 // The physics ops' arguments (Launch::ph), one field per op that needs its own
 struct PhysLaunch {
@@ -228,6 +237,7 @@ struct PhysLaunch {
   IkArgs ik;            // OP_IK
   CostArgs cs;          // OP_COST_ROLLOUTS (with p, r and sw)
   KalmanArgs kf;        // OP_KALMAN
+  BoxArgs bx;           // OP_BOX_BACKWARD
   Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
 };
 

@@ -34,6 +34,10 @@
                                                                                           (A_t, B_t and a quadratic cost model in,
                                                                                            the gains of feedback_rollouts out; one
                                                                                            launch, nothing of the env is read)
+    control-limited DDP's backward pass          ->  Physics.lqr_backward_box(columns, lx, lu, lxx, luu, lo, hi)
+                                                                                          (the same with lo <= k_t <= hi, e.g.
+                                                                                           Physics.ctrl_bounds(u_nom): what agrees
+                                                                                           with feedback_rollouts(clamp=True))
     a Kalman filter / RTS smoother over a log   ->  Physics.kalman_smooth(columns, dy, r, q, P0)
                                                                                           (A_t, C_t of trajectory_fd and measured
                                                                                            minus nominal sensordata in, filtered and
@@ -805,8 +809,20 @@ class Physics:
         slot stopped there with dV = 0, its rows t' > t written and its rows t' <= t left alone; raise its mu and call again)
         and, with `values`, Vx [M, T+1, nx] and Vxx [M, T+1, nx, nx].  `out`: caller-owned float32 tensors under those names to
         fill instead of new ones.  A slot's result depends on that slot's inputs alone, bit for bit.  Writes nothing else."""
-        import torch
         who = "lqr_backward"
+        M, T, w, mu_t, res = self._lqr_io(who, columns, lx, lu, lxx, luu, lux, mu, values, out)
+        ptrs = _lib.LqrOut(**{dict(dV="dv", Vx="vx", Vxx="vxx").get(f, f): t.data_ptr() for f, t in res.items()})
+        cost = _lib.LqrCost(lx.data_ptr(), lu.data_ptr(), lxx.data_ptr(), luu.data_ptr(), None if lux is None else lux.data_ptr())
+        self._held[who] = (columns, lx, lu, lxx, luu, lux, mu_t)
+        _lib.check(_lib.lib().rsr_physics_lqr_backward(self._h, M, T, C.c_void_p(columns.data_ptr()), w, C.byref(cost),
+                                                       C.c_void_p(mu_t.data_ptr()), _lib.LQR_REG_STATE if state_reg else 0,
+                                                       C.byref(ptrs), self._stream()))
+        return res
+
+    def _lqr_io(self, who: str, columns, lx, lu, lxx, luu, lux, mu, values: bool, out, extra=None):
+        """What lqr_backward and lqr_backward_box share ahead of the C call: the inputs checked, mu as a tensor [M] and the outputs
+        (`extra`: further {name: shape} a caller may also pass in `out`).  Returns M, T, w, mu_t and the outputs."""
+        import torch
         d, dev = self.dims, self.qvel.device
         nv, nu = int(d.nv), int(d.nu)
         nx, ncol = 2 * nv, 2 * nv + nu
@@ -831,14 +847,55 @@ class Physics:
         oshapes = dict(gain=(M, T, nu, nx), k=(M, T, nu), dV=(M, 2), status=(M,))
         if values:
             oshapes.update(Vx=(M, T + 1, nx), Vxx=(M, T + 1, nx, nx))
-        res = self._outputs(who, oshapes, out, True, "" if values else " (values=False)")
-        ptrs = _lib.LqrOut(**{dict(dV="dv", Vx="vx", Vxx="vxx").get(f, f): t.data_ptr() for f, t in res.items()})
+        oshapes.update(extra(M, T) if extra else {})
+        return M, T, w, mu_t, self._outputs(who, oshapes, out, True, "" if values else " (values=False)")
+
+    def lqr_backward_box(self, columns, lx, lu, lxx, luu, lo, hi, lux=None, mu=0.0, state_reg: bool = False, values: bool = False,
+                         max_iter: int = 32, report: bool = False, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """The control-limited backward pass (box-DDP: Tassa, Mansard and Todorov 2014), the one that agrees with
+        feedback_rollouts(..., clamp=True): lqr_backward with k_t the minimiser of the step's quadratic model over
+        lo_t <= k_t <= hi_t, and the gain rows of the clamped controls zero, so that k points into the feasible set, the gain
+        promises no feedback the clamp swallows and dV is a change the rollout can deliver.  Inputs, `mu`, `state_reg`, `values`,
+        `out` and the layout are lqr_backward's.  lo, hi [M, T, nu]: the bounds on the control *change*, ctrlrange - u_nom
+        (ctrl_bounds(u_nom) gives them; -inf / +inf: no bound).  The QP of a step is solved on the device inside the recursion
+        by projected Newton steps, at most `max_iter` of them (1 .. 64; include/rsr_physics.h states the iteration line by
+        line).  Returns lqr_backward's dict and, with `report`, clamped [M, T, nu] (-1 at lo, +1 at hi, 0 free) and qp [M, T, 2]
+        (Newton steps taken, and a code: 0 converged, 1 every control clamped, 2 max_iter reached, 3 the line search found no
+        descent).  status [M] is -1, or the step t at which a Cholesky pivot was bad or the bounds were not ordered (lo > hi, or
+        a NaN).  With infinite bounds, and with bounds no step reaches, every output is lqr_backward's bit for bit.  Writes
+        nothing else."""
+        who = "lqr_backward_box"
+        nu = int(self.dims.nu)
+        if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not 1 <= max_iter <= 64:
+            raise ValueError(f"{who}: max_iter must be an int in [1, 64], got {max_iter!r}")
+        extra = (lambda M, T: dict(clamped=(M, T, nu), qp=(M, T, 2))) if report else None
+        M, T, w, mu_t, res = self._lqr_io(who, columns, lx, lu, lxx, luu, lux, mu, values, out, extra)
+        for name, t in (("lo", lo), ("hi", hi)):
+            self._f32(f"{who} expects {name} as", t, f"{(M, T, nu)} (M and T as columns has them)", (M, T, nu), True)
+        names = dict(dV="dv", Vx="vx", Vxx="vxx")
+        ptrs = _lib.LqrOut(**{names.get(f, f): t.data_ptr() for f, t in res.items() if f not in ("clamped", "qp")})
         cost = _lib.LqrCost(lx.data_ptr(), lu.data_ptr(), lxx.data_ptr(), luu.data_ptr(), None if lux is None else lux.data_ptr())
-        self._held[who] = (columns, lx, lu, lxx, luu, lux, mu_t)
-        _lib.check(_lib.lib().rsr_physics_lqr_backward(self._h, M, T, C.c_void_p(columns.data_ptr()), w, C.byref(cost),
-                                                       C.c_void_p(mu_t.data_ptr()), _lib.LQR_REG_STATE if state_reg else 0,
-                                                       C.byref(ptrs), self._stream()))
+        box = _lib.LqrBox(lo.data_ptr(), hi.data_ptr(), res["clamped"].data_ptr() if report else None, res["qp"].data_ptr() if report else None)
+        self._held[who] = (columns, lx, lu, lxx, luu, lux, mu_t, lo, hi)
+        _lib.check(_lib.lib().rsr_physics_lqr_box(self._h, M, T, C.c_void_p(columns.data_ptr()), w, C.byref(cost), C.byref(box),
+                                                  C.c_void_p(mu_t.data_ptr()), max_iter, _lib.LQR_REG_STATE if state_reg else 0,
+                                                  C.byref(ptrs), self._stream()))
         return res
+
+    def ctrl_bounds(self, u_nom):
+        """(lo, hi) for lqr_backward_box about the nominal controls u_nom [M, T, nu] (float32, on the env's device): float32
+        [M, T, nu], contiguous, actuator_ctrlrange - u_nom where the actuator is ctrl-limited (what feedback_rollouts' clamp
+        clips to), -inf / +inf elsewhere.  Plain torch; nothing of the env's state is read."""
+        import numpy as np
+        import torch
+        nu = int(self.dims.nu)
+        self._f32("ctrl_bounds expects u_nom as", u_nom, f"(M, T, {nu})", lambda t: t.dim() == 3 and t.shape[2] == nu, False)
+        A = self.env.sys.arrays
+        rng = np.asarray(A["actuator_ctrlrange"], np.float32).reshape(nu, 2)
+        lim = np.asarray(A["actuator_ctrllimited"]).reshape(nu) != 0
+        lo_r = torch.as_tensor(np.where(lim, rng[:, 0], -np.inf).astype(np.float32), device=u_nom.device)
+        hi_r = torch.as_tensor(np.where(lim, rng[:, 1], np.inf).astype(np.float32), device=u_nom.device)
+        return (lo_r - u_nom).contiguous(), (hi_r - u_nom).contiguous()
 
     def kalman_smooth(self, columns, dy, r, q, P0, x0=None, smooth: bool = True, covariances: bool = False,
                       out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
