@@ -30,6 +30,9 @@
  *                          launch; neither the model nor the record is read.
  *   rsr_physics_lqr_box <- the backward pass of control-limited DDP (Tassa, Mansard and Todorov 2014): the same with k_t the
  *                          minimiser of a box-constrained QP and the gain rows of the clamped controls zero, one launch.
+ *   rsr_physics_cost_expand <- jax.grad / jax.hessian (Gauss-Newton) of the cost of rsr_physics_cost_rollouts about a nominal run:
+ *                          the cost rows and the C_t, D_t of rsr_physics_trajectory_fd in, lx, lu, lxx, luu, lux of
+ *                          rsr_physics_lqr_backward out, one launch; neither the model nor the record is read.
  *   rsr_physics_ik      <- an IK library on top of mj_jacSite (damped least squares on site pose targets): M problems, one launch,
  *                          every iteration on the device; the record is read only.
  *   rsr_physics_kalman  <- a Kalman filter and RTS smoother over a log (lax.scan over A_t, C_t forwards, then reverse=True): the
@@ -485,6 +488,54 @@ int rsr_physics_lqr_backward(rsr_physics* p, int M, int T, const float* columns,
 typedef struct rsr_lqr_box { const float* lo; const float* hi; float* clamped; float* qp; } rsr_lqr_box;
 int rsr_physics_lqr_box(rsr_physics* p, int M, int T, const float* columns, int row_stride, const rsr_lqr_cost* cost,
                         const rsr_lqr_box* box, const float* mu, int max_iter, int flags, const rsr_lqr_out* out, void* hip_stream);
+
+/* Cost expansion, the step between rsr_physics_cost_rollouts / rsr_physics_trajectory_fd and rsr_physics_lqr_backward in an iLQR
+ * iteration: the weighted least-squares cost of rsr_physics_cost_rollouts, stated once as its struct rsr_cost, expanded to second
+ * order about a nominal run into exactly the operands of rsr_lqr_cost, on M independent problems in one launch with one wavefront
+ * per (slot, t'), t' = 0 .. T.  The handle supplies nv, nu, the device and the family's launch entry only: the call reads neither
+ * the model nor the record, takes no env_ids, and the M slots are whatever the caller's buffers hold.  All pointers are device
+ * float32; nx = 2 nv, ncol = nx + nu.
+ * cost: the rows of rsr_physics_cost_rollouts, [M, T, width]: w_qpos, w_qvel [.., nv], w_ctrl [.., nu], w_sensor [.., ny]; a NULL
+ * weight switches its term off.  ctrl_ref [.., nu] and sensor_ref [.., ny]: NULL stands for zeros.  qpos_ref and qvel_ref are not
+ * read: the state residual arrives already formed, as nominal->dx.
+ * nominal (struct rsr_cost_nominal): the residual sources on the nominal run.  dx [M, T, nx]: dq | dv at the end of control step t,
+ * exactly the dx rows rsr_physics_cost_rollouts writes for the nominal sample; required when w_qpos or w_qvel is given.  ctrl
+ * [M, T, nu]: the control that was applied; required with w_ctrl.  sensordata [M, T, ny]: required with w_sensor.
+ * columns: [M, T, ncol, row_stride], row_stride >= nx + ny: the buffer rsr_physics_trajectory_fd writes, passed as it is, so
+ * C_t[j][a] = columns[s, t, a, nx + j] and D_t[j][p] = columns[s, t, nx + p, nx + j]; required with w_sensor and not read without
+ * it.  Entries below nx and entries at or above nx + ny of a row are never read.
+ * out (struct rsr_cost_expansion): lx [M, T+1, nx], lu [M, T, nu], lxx [M, T+1, nx, nx], luu [M, T, nu, nu], lux [M, T, nu, nx];
+ * all five are required and every element of all five is written.  With du = ctrl - ctrl_ref, ds = sensordata - sensor_ref and
+ * W = diag(w_sensor[s, t]):
+ *   state part of cost row t  -> index t+1:  lx[t+1] = [w_qpos . dq | w_qvel . dv]   lxx[t+1] = diag(w_qpos | w_qvel)
+ *   ctrl part of cost row t   -> index t:    lu[t]   = w_ctrl . du                    luu[t]   = diag(w_ctrl)
+ *   sensor part of cost row t -> index t:    lx[t]  += C_t^T (W ds)    lu[t]  += D_t^T (W ds)
+ *                                            lxx[t] += C_t^T W C_t     luu[t] += D_t^T W D_t     lux[t] = D_t^T W C_t
+ * Row 0 of lx / lxx holds the sensor part only; row T holds the state part of cost row T-1 only (the terminal cost).  A term that
+ * is off contributes nothing: its entries are +0 and its residual source is not read.
+ * This is the Gauss-Newton expansion.  It is the exact Hessian for the ctrl and qvel terms and for the hinge, slide and translation
+ * entries of the qpos term.  For a free joint's rotation the Jacobian of dq with respect to a right-multiplied perturbation is taken
+ * as the identity, which is first order in the rotation error: rsr_physics_trajectory_fd perturbs on the right and
+ * mj_differentiatePos differences in the same local frame, so the two are consistent.  The sensors' second derivatives are dropped.
+ * With weights >= 0, lxx and luu are positive semi-definite by construction.
+ * Arithmetic: fp32, no contraction (every product and every sum rounds once).  Every output element is one chain in a fixed order:
+ * it starts from its state or ctrl part (w . residual, or the weight on the diagonal; +0 where there is none) and adds the sensor
+ * entries j = 0 .. ny-1 ascending, c_a[j] g[j] with g[j] = w_sensor[j] ds[j] for lx / lu and (c_a[j] c_b[j]) w_sensor[j] for lxx /
+ * luu / lux (c_a: row a of columns).  A problem's result therefore depends on its own inputs alone, bit for bit, whatever M is and
+ * from run to run.  Two guarantees follow:
+ *   1. with w_sensor NULL, lx[t+1] is the single fp32 product w . dx[t] bit for bit, lu[t] is w_ctrl . (ctrl - ctrl_ref) with one
+ *      subtraction and one product, lxx and luu are exactly diagonal with exactly the weights on the diagonal, and lux, lx[0] and
+ *      lxx[0] are exactly +0;
+ *   2. lxx and luu are symmetric bit for bit: the product (c_a c_b) commutes and is weighted afterwards.
+ * Only the five buffers of out are written: the record, every buffer of the handle, the batch's own leaf tensors and the PRNG keys
+ * are untouched; the handle owns no buffer for this call.  RSR_ERR_ARG, checked before any device work: a null handle, cost, nominal
+ * or out; a NULL member of out; M < 1 or T < 1; ny outside [0, RSR_MAX_SENSORDATA]; no weight given at all; w_qpos or w_qvel
+ * without nominal->dx; w_ctrl without nominal->ctrl; w_sensor with ny == 0, without nominal->sensordata or without columns;
+ * row_stride < nx + ny when columns is read; M (T+1) at or above 2^31. */
+typedef struct rsr_cost_nominal { const float* dx; const float* ctrl; const float* sensordata; } rsr_cost_nominal;
+typedef struct rsr_cost_expansion { float* lx; float* lu; float* lxx; float* luu; float* lux; } rsr_cost_expansion;
+int rsr_physics_cost_expand(rsr_physics* p, int M, int T, const float* columns, int row_stride, int ny, const rsr_cost* cost,
+                            const rsr_cost_nominal* nominal, const rsr_cost_expansion* out, void* hip_stream);
 
 /* Kalman filter and smoother, the estimation dual of rsr_physics_lqr_backward: a linear time-varying Kalman filter with a
  * Rauch-Tung-Striebel smoother on M independent problems, one launch with one wavefront per slot and all T steps inside it.  The

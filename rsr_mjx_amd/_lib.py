@@ -46,7 +46,7 @@ PHYS_SYMBOLS = ["rsr_physics_create", "rsr_physics_destroy", "rsr_physics_step",
                 "rsr_physics_constraint", "rsr_physics_constraint_view", "rsr_physics_transition_fd", "rsr_physics_transition_view",
                 "rsr_physics_inverse", "rsr_physics_inverse_view", "rsr_physics_sample_rollouts", "rsr_physics_param_rollouts",
                 "rsr_physics_feedback_rollouts", "rsr_physics_trajectory_fd", "rsr_physics_lqr_backward", "rsr_physics_ik",
-                "rsr_physics_cost_rollouts", "rsr_physics_kalman", "rsr_physics_lqr_box"]
+                "rsr_physics_cost_rollouts", "rsr_physics_kalman", "rsr_physics_lqr_box", "rsr_physics_cost_expand"]
 
 # enum rsr_applied_field (include/rsr_physics.h), in order
 APPLIED_FIELDS = ["xfrc_applied", "qfrc_applied"]
@@ -136,6 +136,18 @@ class LqrBox(C.Structure):
     """struct rsr_lqr_box (include/rsr_physics.h): device pointers, lo and hi [M, T, nu] (required; -inf / +inf = no bound), clamped
     [M, T, nu] and qp [M, T, 2] (NULL = not recorded)."""
     _fields_ = [(n, C.c_void_p) for n in ("lo", "hi", "clamped", "qp")]
+
+
+class CostNominal(C.Structure):
+    """struct rsr_cost_nominal (include/rsr_physics.h): device pointers, the residual sources of rsr_physics_cost_expand on the
+    nominal run: dx [M, T, 2 nv] (needed by w_qpos / w_qvel), ctrl [M, T, nu] (by w_ctrl), sensordata [M, T, ny] (by w_sensor)."""
+    _fields_ = [(n, C.c_void_p) for n in ("dx", "ctrl", "sensordata")]
+
+
+class CostExpansion(C.Structure):
+    """struct rsr_cost_expansion (include/rsr_physics.h): device pointers, the outputs of rsr_physics_cost_expand, all required:
+    the members of struct rsr_lqr_cost, to be written."""
+    _fields_ = [(n, C.c_void_p) for n in ("lx", "lu", "lxx", "luu", "lux")]
 
 
 class KalmanIn(C.Structure):
@@ -239,6 +251,7 @@ def lib() -> C.CDLL:
     L.rsr_physics_lqr_box.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp]
     L.rsr_physics_ik.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.rsr_physics_kalman.argtypes = [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp]
+    L.rsr_physics_cost_expand.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
     L.rsr_batch_set_debug.argtypes = [vp, vp]
     L.rsr_batch_set_schedule.argtypes = [vp, i32]
     L.rsr_batch_set_whole_envs.argtypes = [vp, i32]

@@ -4,7 +4,7 @@
 // (rsr_physics_transition_fd), inverse dynamics (rsr_physics_inverse), sampled rollouts (rsr_physics_sample_rollouts), parameter
 // rollouts (rsr_physics_param_rollouts), closed-loop rollouts (rsr_physics_feedback_rollouts), cost rollouts (rsr_physics_cost_rollouts), the transition Jacobians along a
 // trajectory (rsr_physics_trajectory_fd), the LQR backward pass (rsr_physics_lqr_backward) and its control-limited form (rsr_physics_lqr_box), inverse kinematics on site pose
-// targets (rsr_physics_ik) and the Kalman filter and smoother (rsr_physics_kalman).  Every launch is a physics op
+// targets (rsr_physics_ik), the Kalman filter and smoother (rsr_physics_kalman) and the cost expansion (rsr_physics_cost_expand).  Every launch is a physics op
 // (rsr::PhysOp) sent through physics_launch; the kernels are in the family units (physics/rsr_physics_kernels.hpp).
 #include <hip/hip_runtime.h>
 
@@ -592,6 +592,28 @@ extern "C" int rsr_physics_kalman(rsr_physics* p, int M, int T, const float* col
   x.ph.kf = rsr::KalmanArgs{columns, row_stride, T, ny, in->dy, in->r, in->q, in->x0, in->P0, out->xf, out->pf, out->xs, out->ps,
                             out->nll, out->status};
   return physics_launch(p, rsr::OP_KALMAN, x, "rsr_physics_kalman");
+}
+
+// One launch, one wave per (slot, t'), t' = 0 .. T (rsr_expand.hpp).  The handle gives nv, nu, the device and the family's entry; none of its buffers is used.
+extern "C" int rsr_physics_cost_expand(rsr_physics* p, int M, int T, const float* columns, int row_stride, int ny, const rsr_cost* cost,
+                                       const rsr_cost_nominal* nominal, const rsr_cost_expansion* out, void* hip_stream) {
+  if (!p) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: null handle");
+  if (!cost || !nominal || !out) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: null cost, nominal or out");
+  if (!out->lx || !out->lu || !out->lxx || !out->luu || !out->lux) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: out needs lx, lu, lxx, luu and lux");
+  if (M < 1 || T < 1) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: M and T must be >= 1");
+  if (ny < 0 || ny > RSR_MAX_SENSORDATA) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: ny must lie in [0, " + std::to_string(RSR_MAX_SENSORDATA) + "]");
+  if (!(cost->w_qpos || cost->w_qvel || cost->w_ctrl || cost->w_sensor)) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: no weight is given");
+  if ((cost->w_qpos || cost->w_qvel) && !nominal->dx) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: w_qpos and w_qvel need nominal->dx");
+  if (cost->w_ctrl && !nominal->ctrl) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: w_ctrl needs nominal->ctrl");
+  if (cost->w_sensor && ny == 0) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: w_sensor given with ny == 0");
+  if (cost->w_sensor && (!nominal->sensordata || !columns)) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: w_sensor needs nominal->sensordata and columns");
+  const rsr_dims& d = p->b->model->dims;
+  if (cost->w_sensor && row_stride < 2 * d.nv + ny) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: row_stride must be >= 2 nv + ny");
+  if ((int64_t)M * ((int64_t)T + 1) > INT32_MAX) return fail(RSR_ERR_ARG, "rsr_physics_cost_expand: M x (T + 1) must stay below 2^31");
+  rsr::Launch x = physics_args(p, nullptr, nullptr, M * (T + 1), 1, hip_stream);
+  x.ph.ex = rsr::ExpandArgs{columns, row_stride, T, ny, cost->ctrl_ref, cost->sensor_ref, cost->w_qpos, cost->w_qvel, cost->w_ctrl, cost->w_sensor,
+                            nominal->dx, nominal->ctrl, nominal->sensordata, out->lx, out->lu, out->lxx, out->luu, out->lux};
+  return physics_launch(p, rsr::OP_EXPAND, x, "rsr_physics_cost_expand");
 }
 
 // One launch, one wave per slot (rsr_ik.hpp).  The task table goes by value; none of the handle's buffers is used.

@@ -198,6 +198,15 @@ struct KalmanArgs {
   float *xs, *ps;       // [M][T+1][nx] (null: no smoother), [M][T+1][nx][nx] (null = not recorded)
   float *nll, *status;  // [M] (null = not recorded), [M][2]
 };
+// rsr_physics_cost_expand (rsr_expand.hpp): the caller's buffers, every row indexed by slot (PhysLaunch::ex).  nx = 2 nv.
+struct ExpandArgs {
+  const float* columns; // [M][T][nx + nu][row_stride]: of every row the entries nx + j, j < ny (C_t | D_t); null without w_sensor
+  int row_stride, T, ny;
+  const float *ctrl_ref, *sensor_ref;                    // [M][T][nu | ny], each null: zeros
+  const float *w_qpos, *w_qvel, *w_ctrl, *w_sensor;      // [M][T][nv | nv | nu | ny]; null: the term is off
+  const float *dx, *ctrl, *sensordata;                   // [M][T][nx | nu | ny] the residual sources on the nominal run
+  float *lx, *lu, *lxx, *luu, *lux;                      // [M][T+1][nx], [M][T][nu], [M][T+1][nx][nx], [M][T][nu][nu], [M][T][nu][nx]
+};
 
 // The physics ops of a family unit's launch entry (launch_physics, rsr_physics_kernels.hpp).  An entry takes its op as an int, of
 // enum Op (rsr_launch.hpp) or of this enum: these start above enum Op's, so that no value names two ops.  A new op is a member
@@ -221,6 +230,7 @@ enum PhysOp {
   OP_COST_ROLLOUTS,      // rsr_physics_cost_rollouts (p, r, sw, cs): grid and rows as OP_PHYS_SWEEP's
   OP_KALMAN,             // rsr_physics_kalman (kf): grid = slots; reads neither the model nor the record
   OP_BOX_BACKWARD,       // rsr_physics_lqr_box (bx): grid = slots; reads neither the model nor the record
+  OP_EXPAND,             // rsr_physics_cost_expand (ex): grid = slots x (T + 1); reads neither the model nor the record
 };
 // The physics ops' arguments (Launch::ph), one field per op that needs its own
 struct PhysLaunch {
@@ -238,6 +248,7 @@ struct PhysLaunch {
   CostArgs cs;          // OP_COST_ROLLOUTS (with p, r and sw)
   KalmanArgs kf;        // OP_KALMAN
   BoxArgs bx;           // OP_BOX_BACKWARD
+  ExpandArgs ex;        // OP_EXPAND
   Applied ap;           // the ops that take p or c: the applied forces, or ap.xfrc null: none (the plain kernels)
 };
 

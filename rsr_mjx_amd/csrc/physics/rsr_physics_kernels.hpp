@@ -2,9 +2,9 @@
 // with its flags and next to its env kernels, and launches them through launch_physics.  One body per kind, physics_kernel (step and
 // forward), rollout_kernel, dynamics_kernel (rsr_dynamics.hpp), constraint_kernel (rsr_constraint.hpp), transition_kernel
 // (rsr_transition.hpp), inverse_kernel (rsr_inverse.hpp), sampled_kernel (rsr_sample.hpp: one body, three ops) and the two
-// of rsr_trajectory.hpp, nominal_kernel and trajectory_fd_kernel, lqr_kernel with box_backward_kernel (rsr_lqr.hpp, one body) and kalman_kernel (rsr_kalman.hpp), which run
+// of rsr_trajectory.hpp, nominal_kernel and trajectory_fd_kernel, lqr_kernel with box_backward_kernel (rsr_lqr.hpp, one body), kalman_kernel (rsr_kalman.hpp) and expand_kernel (rsr_expand.hpp), which run
 // no physics and take of a family only nv and nu, and ik_kernel (rsr_ik.hpp), which runs the kinematics and mass-matrix stages
-// alone; all but dynamics_kernel, inverse_kernel, lqr_kernel, kalman_kernel and ik_kernel are instantiated plain and with applied forces:
+// alone; all but dynamics_kernel, inverse_kernel, lqr_kernel, kalman_kernel, expand_kernel and ik_kernel are instantiated plain and with applied forces:
 // the applied kernels take the handle's Applied buffers as one more argument and pass forward<C> their env's rows as its force
 // stage (rsr_applied.hpp).
 #pragma once
@@ -22,6 +22,7 @@
 #include "rsr_kalman.hpp"
 #include "rsr_ik.hpp"
 #include "rsr_cost.hpp"
+#include "rsr_expand.hpp"
 
 namespace rsr {
 
@@ -176,8 +177,8 @@ template <class C, int WAVES>
 int launch_physics(int op, const Launch& x) {
   // (the LDS of the transition and of the trajectory's columns: Smem<C> and the words the first run's end state waits in; the
   // backward pass has an image of its own, LqrDims<C>, the control-limited one BoxDims<C> behind it; inverse kinematics adds IkDims<C> behind Smem<C>, the cost rollouts their
-  // accumulators; the Kalman filter and smoother have an image of their own, KalmanDims<C>)
-  const size_t lds = op == OP_COST_ROLLOUTS ? cost_lds_bytes<C>() : op == OP_IK ? ik_lds_bytes<C>() : op == OP_KALMAN ? kalman_lds_bytes<C>(x.ph.kf.xs != nullptr) : op == OP_LQR_BACKWARD ? lqr_lds_bytes<C>() : op == OP_BOX_BACKWARD ? box_lds_bytes<C>() : op == OP_TRAJ_FD || op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>);
+  // accumulators; the Kalman filter and smoother have an image of their own, KalmanDims<C>, and so has the cost expansion, ExpandDims<C>)
+  const size_t lds = op == OP_COST_ROLLOUTS ? cost_lds_bytes<C>() : op == OP_IK ? ik_lds_bytes<C>() : op == OP_EXPAND ? expand_lds_bytes<C>() : op == OP_KALMAN ? kalman_lds_bytes<C>(x.ph.kf.xs != nullptr) : op == OP_LQR_BACKWARD ? lqr_lds_bytes<C>() : op == OP_BOX_BACKWARD ? box_lds_bytes<C>() : op == OP_TRAJ_FD || op == OP_PHYS_TRANSITION ? fd_lds_bytes<C>() : sizeof(Smem<C>);
   auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(64), lds, x.stream, x.dm, x.L, x.a, args...); return 0; };
   const PhysLaunch& ph = x.ph;
   const bool ap = ph.ap.xfrc != nullptr;     // applied forces on
@@ -188,6 +189,7 @@ int launch_physics(int op, const Launch& x) {
   if (op == OP_BOX_BACKWARD) return go(box_backward_kernel<C, WAVES>, ph.bx);   // rsr_physics_lqr_box (rsr_lqr.hpp)
   if (op == OP_IK) return go(ik_kernel<C, WAVES>, ph.ik);                 // rsr_physics_ik (rsr_ik.hpp)
   if (op == OP_KALMAN) return go(kalman_kernel<C, WAVES>, ph.kf);         // rsr_physics_kalman (rsr_kalman.hpp)
+  if (op == OP_EXPAND) return go(expand_kernel<C, WAVES>, ph.ex);         // rsr_physics_cost_expand (rsr_expand.hpp)
   // rsr_physics_cost_rollouts (rsr_sample.hpp, rsr_cost.hpp)
   if (op == OP_COST_ROLLOUTS) return ap ? go(sampled_kernel<C, WAVES, CostOp, Applied>, ph.p, ph.r, CostOp::Args{ph.sw, ph.cs}, ph.ap) : go(sampled_kernel<C, WAVES, CostOp>, ph.p, ph.r, CostOp::Args{ph.sw, ph.cs});
   switch (op) {

@@ -38,6 +38,12 @@
                                                                                           (the same with lo <= k_t <= hi, e.g.
                                                                                            Physics.ctrl_bounds(u_nom): what agrees
                                                                                            with feedback_rollouts(clamp=True))
+    jax.grad / Gauss-Newton hessian of the cost  ->  Physics.cost_expand(cost, dx, ctrl, sensordata, columns)
+                                                                                          (the cost dict of cost_rollouts about a
+                                                                                           nominal run in, lx, lu, lxx, luu, lux of
+                                                                                           lqr_backward out; one launch, nothing of
+                                                                                           the env is read;
+                                                                                           Physics.differentiate_state forms dx)
     a Kalman filter / RTS smoother over a log   ->  Physics.kalman_smooth(columns, dy, r, q, P0)
                                                                                           (A_t, C_t of trajectory_fd and measured
                                                                                            minus nominal sensordata in, filtered and
@@ -753,6 +759,85 @@ class Physics:
                         C.byref(cs), K, T, nsteps, flags, C.byref(ptrs), C.byref(co), checked=True, hold=(c, *rows, *leaves))
         return {**mine, **res}
 
+    def cost_expand(self, cost, dx=None, ctrl=None, sensordata=None, columns=None, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """The cost model of an iLQR iteration from the one statement of the cost: the `cost` dict of cost_rollouts expanded to
+        second order about a nominal run, into exactly what lqr_backward takes:
+            phys.lqr_backward(fd["columns"], **phys.cost_expand(cost, dx=..., ctrl=..., sensordata=..., columns=fd["columns"])).
+        M independent problems, one launch with one wave per (slot, step); nothing of the env is read: the handle gives nv and
+        nu, M and T come from the cost rows and ny from w_sensor.  All float32 tensors on the env's device, nx = 2 nv:
+        cost: the weights w_qpos, w_qvel [M, T, nv], w_ctrl [M, T, nu], w_sensor [M, T, ny] (1 <= ny <= 64; a weight not given:
+        that term is off; at least one must be) and the references ctrl_ref [M, T, nu], sensor_ref [M, T, ny] (not given: zeros);
+        qpos_ref and qvel_ref are accepted and ignored, so that the same dict serves both calls: the state residual arrives
+        formed, as dx.  dx [M, T, nx]: dq | dv at the end of control step t on the nominal run, the "dx" rows of
+        cost_rollouts(..., residual=True) for the nominal sample (differentiate_state gives the same from states); needed by
+        w_qpos / w_qvel.  ctrl [M, T, nu]: the control that was applied; needed by w_ctrl.  sensordata [M, T, ny] and columns
+        [M, T, nx + nu, w], w >= nx + ny (trajectory_fd(...)["columns"] as it is: its C and D blocks are the sensor entries of
+        the rows): needed by w_sensor.  An input its terms do not need is not read.  Returns lx [M, T+1, nx], lu [M, T, nu],
+        lxx [M, T+1, nx, nx], luu [M, T, nu, nu], lux [M, T, nu, nx], every element written: the state terms of cost row t land
+        on index t + 1 (row T is the terminal cost), its ctrl and sensor terms on index t, the sensor terms through the
+        Gauss-Newton products C^T W C, D^T W C, D^T W D and the gradients C^T W ds, D^T W ds.  The expansion is exact for the
+        ctrl, qvel, hinge, slide and translation terms; for a free joint's rotation the Jacobian of dq is taken as the identity,
+        which is first order in the rotation error (trajectory_fd perturbs in the same local frame), and the sensors' second
+        derivatives are dropped.  fp32 in a fixed order (include/rsr_physics.h): a problem's numbers depend on its own inputs
+        alone, bit for bit; lxx and luu are symmetric bit for bit; with w_sensor off the outputs are the plain products and
+        exactly diagonal matrices.  `out`: caller-owned float32 tensors under those names to fill instead of new ones.  Writes
+        nothing else."""
+        who = "cost_expand"
+        d = self.dims
+        nv, nu = int(d.nv), int(d.nu)
+        nx, ncol = 2 * nv, 2 * nv + nu
+        names = _lib.COST_WEIGHTS + _lib.COST_REFS
+        if not isinstance(cost, dict):
+            raise ValueError(f"{who}: cost must be a dict with some of {names}, got {type(cost).__name__}")
+        unknown = sorted(set(cost) - set(names))
+        if unknown:
+            raise ValueError(f"{who}: cost has {unknown}; it may hold {names}")
+        cost = {k: v for k, v in cost.items() if v is not None and k not in ("qpos_ref", "qvel_ref")}
+        given = [w for w in _lib.COST_WEIGHTS if w in cost]
+        if not given:
+            raise ValueError(f"{who}: cost gives no weight: at least one of {_lib.COST_WEIGHTS} is needed")
+        first = cost[given[0]]
+        self._f32(f"{who} expects cost[{given[0]!r}] as", first, "(M >= 1, T >= 1, width)",
+                  lambda t: t.dim() == 3 and t.shape[0] >= 1 and t.shape[1] >= 1, False)
+        M, T = int(first.shape[0]), int(first.shape[1])
+        if M * (T + 1) >= 2 ** 31:
+            raise ValueError(f"{who}: M * (T + 1) must stay below 2^31")
+        ny = 0
+        if "w_sensor" in cost:
+            self._f32(f"{who} expects cost['w_sensor'] as", cost["w_sensor"], f"({M}, {T}, 1 <= ny <= {_lib.MAX_SENSORDATA})",
+                      lambda t: t.dim() == 3 and 1 <= t.shape[2] <= _lib.MAX_SENSORDATA, False)
+            ny = int(cost["w_sensor"].shape[2])
+        width = dict(ctrl_ref=nu, sensor_ref=ny, w_qpos=nv, w_qvel=nv, w_ctrl=nu, w_sensor=ny)
+        cs, held = _lib.Cost(), []
+        for name, t in cost.items():
+            if name == "sensor_ref" and "w_sensor" not in cost:      # (its term is off: not read)
+                continue
+            shape = (M, T, width[name])
+            self._f32(f"{who} expects cost[{name!r}] as", t, str(shape), shape, False)
+            t = t.contiguous()
+            setattr(cs, name, t.data_ptr())
+            held.append(t)
+        nom = _lib.CostNominal()
+        needs = (("dx", dx, (M, T, nx), ("w_qpos", "w_qvel")), ("ctrl", ctrl, (M, T, nu), ("w_ctrl",)),
+                 ("sensordata", sensordata, (M, T, ny), ("w_sensor",)))
+        for name, t, shape, by in needs:
+            by = [w for w in by if w in cost]
+            if by:
+                self._f32(f"{who} expects {name} (needed by {by[0]}) as", t, f"{shape} (M and T as the cost rows have them)", shape, True)
+                setattr(nom, name, t.data_ptr())
+                held.append(t)
+        col_ptr, w = None, 0
+        if "w_sensor" in cost:
+            self._f32(f"{who} expects columns (needed by w_sensor) as", columns, f"({M}, {T}, {ncol}, w >= {nx + ny})",
+                      lambda t: t.dim() == 4 and tuple(t.shape[:3]) == (M, T, ncol) and t.shape[3] >= nx + ny, True)
+            col_ptr, w = C.c_void_p(columns.data_ptr()), int(columns.shape[3])
+            held.append(columns)
+        res = self._outputs(who, dict(lx=(M, T + 1, nx), lu=(M, T, nu), lxx=(M, T + 1, nx, nx), luu=(M, T, nu, nu), lux=(M, T, nu, nx)), out, True)
+        ptrs = _lib.CostExpansion(**{f: t.data_ptr() for f, t in res.items()})
+        self._held[who] = tuple(held)
+        _lib.check(_lib.lib().rsr_physics_cost_expand(self._h, M, T, col_ptr, w, ny, C.byref(cs), C.byref(nom), C.byref(ptrs), self._stream()))
+        return res
+
     def trajectory_fd(self, ctrl, nsteps: Optional[int] = None, eps: float = 1e-3, centered: bool = True, env_ids=None,
                       nominal: bool = True, out: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """What the backward pass of iLQR, a time-varying LQR, linearised MPC and an EKF smoother ask: transition_fd at every
@@ -988,6 +1073,45 @@ class Physics:
             else:
                 raise ValueError(f"{who}: joint {j} has type {jt}; only free, slide and hinge joints are supported")
         return out, qvel + dx[..., nv:]
+
+    def differentiate_state(self, qpos, qvel, qpos_ref, qvel_ref):
+        """The inverse of integrate_state: the tangent-space deviation dx [..., 2 nv] = (mj_differentiatePos(qpos_ref -> qpos)
+        with dt = 1 | qvel - qvel_ref) of a state from a reference, in torch, for any leading dims (qpos, qpos_ref [..., nq],
+        qvel, qvel_ref [..., nv], the same leading dims): dq | dv as cost_rollouts(..., residual=True) forms them, for a caller who
+        has states but no rollout (a terminal row of their own for cost_expand, say).  A free joint's rotation dofs are the
+        body-frame rotation vector of conj(q_ref) q, exactly 0 where the two quaternions are equal.  Nothing of the batch is read
+        but the model's joint table, and nothing is written."""
+        import math
+        import torch
+        who = "differentiate_state"
+        nq, nv = int(self.dims.nq), int(self.dims.nv)
+        for name, t, n in (("qpos", qpos, nq), ("qvel", qvel, nv), ("qpos_ref", qpos_ref, nq), ("qvel_ref", qvel_ref, nv)):
+            if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() < 1 or t.shape[-1] != n:
+                raise ValueError(f"{who} expects {name} as a floating-point tensor of shape (..., {n})")
+        if not (qpos.shape[:-1] == qvel.shape[:-1] == qpos_ref.shape[:-1] == qvel_ref.shape[:-1]):
+            raise ValueError(f"{who}: qpos, qvel, qpos_ref and qvel_ref must have the same leading dims")
+        A = self.env.sys.arrays
+        dq = qpos.new_zeros(qpos.shape[:-1] + (nv,))
+        for j in range(len(A["jnt_type"])):
+            jt, qa, da = int(A["jnt_type"][j]), int(A["jnt_qposadr"][j]), int(A["jnt_dofadr"][j])
+            if jt == 0:                                   # free: translation, then the rotation vector of conj(q_ref) q
+                dq[..., da:da + 3] = qpos[..., qa:qa + 3] - qpos_ref[..., qa:qa + 3]
+                w1, x1, y1, z1 = qpos_ref[..., qa + 3], -qpos_ref[..., qa + 4], -qpos_ref[..., qa + 5], -qpos_ref[..., qa + 6]
+                w2, x2, y2, z2 = (qpos[..., qa + 3 + k] for k in range(4))
+                # (each component sums its two w terms first, then its cross pair: at equal quaternions each pair cancels exactly)
+                w = w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2
+                v = torch.stack([w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2, w1 * y2 + y1 * w2 - x1 * z2 + z1 * x2,
+                                 w1 * z2 + z1 * w2 + x1 * y2 - y1 * x2], -1)
+                sn = v.norm(dim=-1)
+                ang = 2.0 * torch.atan2(sn, w)
+                ang = torch.where(ang > math.pi, ang - 2.0 * math.pi, ang)
+                f = torch.where(sn > 0, ang / torch.where(sn > 0, sn, torch.ones_like(sn)), torch.zeros_like(sn))
+                dq[..., da + 3:da + 6] = v * f[..., None]
+            elif jt in (2, 3):                            # slide, hinge
+                dq[..., da] = qpos[..., qa] - qpos_ref[..., qa]
+            else:
+                raise ValueError(f"{who}: joint {j} has type {jt}; only free, slide and hinge joints are supported")
+        return torch.cat([dq, qvel - qvel_ref], dim=-1)
 
     def ik(self, sites, target_pos, target_quat=None, pos_weight=1.0, rot_weight=None, dofs=None, qpos0=None, damping=1e-3,
            iters: int = 20, tol_pos: float = 1e-4, tol_rot: float = 1e-3, max_step: float = 0.3, limits: bool = True,
